@@ -11,9 +11,11 @@ as the checker only.  Nothing under tutel_amd/ imports it; the product fails lou
 HIP library is missing instead of falling back to this code.
 
 How it is pinned (so that "parity" means parity with the reference, not with ourselves):
-  * tests/test_oracle_vs_reference.py runs the reference itself in this container (python
-    package from /root/reference + its C++ CPU kernels compiled into oracle/_ref/ by
-    oracle/Makefile) and checks every function below against it on seeded inputs;
+  * tests/test_oracle_vs_reference.py runs the reference itself where its tree is present (python
+    package + its C++ CPU kernels compiled into oracle/_ref/ by oracle/Makefile) and checks every
+    function below against it on seeded inputs; on any box tests/test_reference_checks.py and
+    test_reference_kernels_equal_the_port replay the same checks against the reference's stored
+    observations (tests/golden/reference_checks.npz, tests/golden/ref_kernels.npz);
   * tests/golden/*.npz are outputs of that reference (generator tests/golden/make_golden.py)
     and are replayed against this oracle on any box (tests/test_oracle_golden.py);
   * the reference's own golden-loss file tests/test_baseline.json (head committed as

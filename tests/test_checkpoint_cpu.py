@@ -1,14 +1,13 @@
 """tutel.checkpoint.gather / scatter: per-rank expert-parallel checkpoints <-> one full
-checkpoint.  Pure host logic; compared against the reference's own CLI tools when /root/reference exists."""
+checkpoint.  Pure host logic; compared against what the reference's own CLI tools wrote for the same inputs
+(tests/golden/checkpoint_reference_tools.npz, made by tests/golden/make_golden_checkpoint.py)."""
 import os
-import subprocess
-import sys
 
+import numpy as np
 import pytest
 import torch
 
-REF = os.environ.get("TUTEL_REFERENCE", "/root/reference")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _rank_states(size, E_global, H=6, M=4, seed=0):
@@ -76,21 +75,19 @@ def test_gather_scatter_round_trip_and_reference_tools(tmp_path, size, E_global,
         full2 = unwrap(torch.load(str(tmp_path / "full2.pt")))
         assert all(torch.equal(full[k], full2[k]) for k in full)
 
-    if not os.path.isdir(os.path.join(REF, "tutel")):
-        return
-    # the reference's own tools on the same files
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REF, os.path.join(ROOT, "oracle", "_ref")]))
-    ref_full = str(tmp_path / "ref_full.pt")
-    subprocess.check_call([sys.executable, "-m", "tutel.checkpoint.gather", f"--input_size={size}", f"--inputs={inputs}",
-                           f"--output={ref_full}", f"--namespace={namespace}"], env=env, cwd=str(tmp_path), stdout=subprocess.DEVNULL)
-    rf = unwrap(torch.load(ref_full))
+    # the reference's own tools on the same files (their outputs: tests/golden/make_golden_checkpoint.py)
+    z = np.load(os.path.join(GOLD, "checkpoint_reference_tools.npz"))
+    p = f"{size}_{E_global}_{namespace.replace('/', '.') or '-'}|"
+    assert float(sum(t.double().abs().sum() for sd in states for t in sd.values())) == float(z[p + "in_checksum"][0]), \
+        "seeded inputs must regenerate bit-identically"
+
+    def ref_state(part):
+        return {n[len(p + part + "|"):]: torch.from_numpy(z[n]) for n in z.files if n.startswith(p + part + "|")}
+    rf = ref_state("gather")
     assert set(rf) == set(full) and all(torch.equal(rf[k], full[k]) for k in full), "gather differs from the reference tool"
     if E_global % other == 0:
-        subprocess.check_call([sys.executable, "-m", "tutel.checkpoint.scatter", f"--output_size={other}", f"--input={ref_full}",
-                               f"--outputs={tmp_path}/refhalf/r{{rank}}-of-{{size}}.pt", f"--namespace={namespace}"],
-                              env=env, cwd=str(tmp_path), stdout=subprocess.DEVNULL)
         for r, f in enumerate(outs):
-            mine, ref = unwrap(torch.load(f)), unwrap(torch.load(f"{tmp_path}/refhalf/r{r}-of-{other}.pt"))
+            mine, ref = unwrap(torch.load(f)), ref_state(f"scatter{r}")
             assert set(mine) == set(ref) and all(torch.equal(mine[k], ref[k]) for k in mine), "scatter differs from the reference tool"
 
 

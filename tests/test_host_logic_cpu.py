@@ -798,3 +798,34 @@ def test_bench_starts_itself_under_the_launcher_when_asked_for_more_than_one_gpu
     finally:
         os.environ.clear()
         os.environ.update(old)
+
+
+def test_bench_dump_outputs_size_bound_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; an output set that fits is written whole; one that does not is cut to a fixed,
+    seeded, ascending sample of rows (the last axis kept, indices in <name>_rows.npy) so that the files stay within the limit and two
+    runs pick the same rows."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    y = torch.randn([4, 50, 16], generator=g).to(torch.bfloat16)
+    l_aux = torch.tensor(0.25)
+
+    def files(d):
+        return {f: os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)}
+    rep = bench.dump_outputs(str(tmp_path / "whole"), {"y": y, "l_aux": l_aux})
+    assert rep["y"] == {"shape": [4, 50, 16], "sampled_rows": None} and set(files(tmp_path / "whole")) == {"y.npy", "l_aux.npy"}
+    got = np.load(tmp_path / "whole" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.float().numpy()) and float(np.load(tmp_path / "whole" / "l_aux.npy")) == 0.25
+    limit = 4096
+    runs = []
+    for name in ("a", "b"):
+        rep = bench.dump_outputs(str(tmp_path / name), {"y": y, "l_aux": l_aux}, limit=limit)
+        assert sum(files(tmp_path / name).values()) <= limit and 0 < rep["y"]["sampled_rows"] < 200
+        rows, sample = np.load(tmp_path / name / "y_rows.npy"), np.load(tmp_path / name / "y.npy")
+        assert rows.dtype == np.float64 and sample.dtype == np.float32 and sample.shape == (rep["y"]["sampled_rows"], 16)
+        assert np.all(np.diff(rows) > 0) and np.array_equal(sample, y.float().reshape(-1, 16).numpy()[rows.astype(np.int64)])
+        runs.append(rows)
+    assert np.array_equal(runs[0], runs[1])
