@@ -450,6 +450,49 @@ typedef struct {
 #define TUTEL_AMD_ENOTSUP 1001 /* reserved: "this entry point does not take the shape, nothing was launched" */
 int tutel_amd_moe_forward(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_args_t *args, tutel_stream_t stream);
 
+/* ---- dropless forward without a host synchronisation: the PACKED layout (single rank, inference) ----------------------
+ * tutel_amd_moe_forward with capacity_factor <= 0 reads the maximum expert load back to shape [E, C, *].  This entry point
+ * lays the experts' rows out back to back instead, sized on the device:
+ *   kept_e = min(dispatch_count[e], L)      L = round_up(capacity_limit, alignment) when capacity_limit > 0, else no limit
+ *                                           (exactly the (choice, token) entries the padded path keeps: loc < C there)
+ *   rows_e = round_up(kept_e, alignment)    expert e owns packed rows [off[e], off[e] + rows_e), off = exclusive prefix sum
+ * Every buffer and grid is sized by a bound computed on the host from (T, E, k, capacity_limit, alignment) alone:
+ *   rows  <= rows_bound  = min(k*T + min(E, k*T)*(alignment - 1), E*L)
+ *   tiles <= tiles_bound = floor(rows_bound / tile_rows) + min(E, k*T)     (tiles of tile_rows packed rows, per expert)
+ * so nothing depends on the routing and the whole call -- routing, layout, both expert GEMMs, decode -- can be captured in a
+ * HIP graph and replayed for batches of any load.  Inside the call there is no allocation, no copy to the host and no
+ * synchronisation.  The results are bit-identical to tutel_amd_moe_forward's dropless path on the same input (same rows,
+ * same K order, same K-tile rotation: it follows the device capacity).
+ *
+ * Arguments: args as for tutel_amd_moe_forward with ep.capacity = 0 (ignored), capacity_limit / alignment as there; unused:
+ * ep.slot_map / enc / recv / hid / send / back / row_counts (megablocks row counts are the alignment here), max_capacity,
+ * capacity_out, fl_ws.  Required: comm == NULL, ep.world == 1, ep.is_postscore, ep.w2_kmajor, ep.zero_row (>= M zeros).
+ * packed->ws: tutel_amd_moe_packed_workspace_bytes(...) bytes (16-byte aligned) -- the packed slot map, tile table, fc1 and fc2
+ * outputs.  Outputs: offsets [E + 1] (off; offsets[E] = rows used), capacity [1] = max_e rows_e, the value the padded path reads
+ * back (0 for T == 0), plus everything tutel_amd_moe_forward writes (y, idx, loc, gates, dispatch_count, stats, l_aux).
+ * Covered: 16-bit experts, H and M_out >= 128, M and H multiples of 64, 1 <= k <= 16, E <= 4096, operands below 2 GiB;
+ * tutel_amd_packed_plan returns TUTEL_AMD_ENOTSUP (reason in tutel_amd_last_error) for anything else, and so does the
+ * forward, with nothing launched. */
+typedef struct {
+  void *ws;                /* device workspace */
+  size_t ws_bytes;
+  int32_t *offsets;        /* out [num_experts + 1] */
+  int32_t *capacity;       /* out [1] */
+} tutel_amd_packed_args_t;
+typedef struct {
+  int rows_bound;          /* packed rows any routing can need */
+  int tiles_bound;         /* grid M-tiles any routing can need */
+  int tile_rows;           /* rows per M-tile of the packed expert GEMMs (a function of the shape only) */
+  int row_limit;           /* L above; 0 = none */
+  size_t ws_bytes;         /* = tutel_amd_moe_packed_workspace_bytes */
+} tutel_amd_packed_plan_t;
+int tutel_amd_packed_plan(int T, int E, int k, int M, int H, int M_out, int dtype, int capacity_limit, int alignment,
+                          tutel_amd_packed_plan_t *out);
+size_t tutel_amd_moe_packed_workspace_bytes(int T, int E, int k, int M, int H, int M_out, int dtype, int capacity_limit,
+                                            int alignment); /* 0: not covered / bad sizes */
+int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_args_t *args,
+                                 const tutel_amd_packed_args_t *packed, tutel_stream_t stream);
+
 /* stage markers: roctx ranges (rocprofv3 --marker-trace); the pipeline above emits tutel_amd.fast_encode /
  * all_to_all / expert_fc1 / expert_fc2 / fast_decode itself.  No-ops when libroctx64 is not in the process
  * (set TUTEL_AMD_ROCTX=1 to load it).  The reference's only tracing is system.record_time (system.py:73-79). */

@@ -72,8 +72,21 @@ class MoeArgs(ctypes.Structure):
                 ("fl_ws", _vp), ("fl_ws_bytes", _sz)]
 
 
+class PackedArgs(ctypes.Structure):
+    """tutel_amd_packed_args_t"""
+    _fields_ = [("ws", _vp), ("ws_bytes", _sz), ("offsets", _vp), ("capacity", _vp)]
+
+
+class PackedPlan(ctypes.Structure):
+    """tutel_amd_packed_plan_t"""
+    _fields_ = [("rows_bound", _i), ("tiles_bound", _i), ("tile_rows", _i), ("row_limit", _i), ("ws_bytes", _sz)]
+
+
 SIGNATURES.update({
     "tutel_amd_moe_forward": (_i, [_vp, ctypes.POINTER(MoeArgs), _vp]),
+    "tutel_amd_packed_plan": (_i, [_i] * 9 + [ctypes.POINTER(PackedPlan)]),
+    "tutel_amd_moe_packed_workspace_bytes": (_sz, [_i] * 9),
+    "tutel_amd_moe_forward_packed": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp]),
     "tutel_amd_ep_load_rccl": (_i, [ctypes.c_char_p]),
     "tutel_amd_ep_unique_id": (_i, [_vp, _sz]),
     "tutel_amd_ep_comm_create": (_i, [_vp, _sz, _i, _i, ctypes.POINTER(_vp)]),

@@ -85,6 +85,20 @@ struct RouteFinish;
 void tutel_route_finish_args(int T, int E, int k, void *ws, RouteFinish *out);  // routing.hip
 int tutel_decode_finish_launch(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype, int T, int M,
                                int k, int capacity, int num_experts, void *out, const RouteFinish &fin, hipStream_t st);
+// Packed dropless layout (dropless.hip).  Rows of the packed expert GEMMs per M-tile: a function of the shape alone (see
+// tutel_amd_packed_plan); the expert GEMM side (expert_gemm.hip) supports exactly this height.
+#define PK_TILE_ROWS 256
+// expert_gemm.hip: grouped GEMM over the packed layout, k-major weights.  Rows are global packed rows: A row r at A + r*lda
+// (a_rows != NULL: token a_rows[r] % T of A, -1 = zero_row), D row r at D + r*ldd.  Tile table tiles[2*i] = expert,
+// tiles[2*i+1] = first row; *ntiles live entries (device); off[E+1]: the experts' row ranges; cap: the device capacity (the
+// K-tile rotation follows it, so the bits are those of the padded launch).  Grid: tiles_bound x N-tiles.
+int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int64_t w_stride_e,
+                             int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
+                             int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
+                             hipStream_t st);
+// dispatch.hip: fast_decode over the packed layout: row off[e] + loc, entries with loc >= row_limit dropped
+int tutel_decode_packed_launch(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype, int T,
+                               int M, int k, int row_limit, const int32_t *off, void *out, hipStream_t st);
 // routing.hip: top-k on logits (`in`) or on the gate projection's split-K partial sums, optionally leaving a byte copy of idx
 // (idx8 [k * T], E <= 128) for the fused-location expert GEMM
 int tutel_gate_topk_launch(const void *in, const float *partials, int splits, int dtype, int T, int E, int k, int normalize_gate,

@@ -144,7 +144,8 @@ template <typename T, int KMAX, int SPLIT, bool NTS>
 __device__ __forceinline__ void decode_body(const T *__restrict__ buf, const int32_t *__restrict__ idx,
                                             const int32_t *__restrict__ loc, const void *__restrict__ gates,
                                             int gate_dtype, int Tn, int M, int k, int capacity, int num_experts,
-                                            int chunk_rows, int expert_slice, int ep_world, T *__restrict__ out, int bid, int nblk) {
+                                            int chunk_rows, int expert_slice, int ep_world, T *__restrict__ out, int bid, int nblk,
+                                            const int32_t *__restrict__ pk_off = nullptr) {
   constexpr int VN = Vec<T>::N;
   const int lane = threadIdx.x & 63;
   const int wave = bid * DP_WAVES + (threadIdx.x >> 6);
@@ -173,6 +174,7 @@ __device__ __forceinline__ void decode_body(const T *__restrict__ buf, const int
           }
           size_t r = (chunk_rows > 0) ? ((size_t)(l / chunk_rows) * num_experts + e) * chunk_rows + (l % chunk_rows)
                                       : (size_t)e * capacity + l;
+          if (pk_off != nullptr) r = (size_t)pk_off[e] + l;  // packed dropless layout: expert e's rows start at off[e]
           rows[j] = buf + r * M;
           g[j] = gates ? load_gate(gates, gate_dtype, (size_t)j * Tn + t) : 1.0f;
         }
@@ -265,6 +267,16 @@ __global__ __launch_bounds__(DP_THREADS) void decode_kernel(const T *__restrict_
                                                            int chunk_rows, int expert_slice, int ep_world, T *__restrict__ out) {
   decode_body<T, KMAX, SPLIT, NTS>(buf, idx, loc, gates, gate_dtype, Tn, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, out,
                                    (int)blockIdx.x, (int)gridDim.x);
+}
+
+// packed dropless layout (dropless.hip): row off[e] + loc; `capacity` is the row limit L (entries with loc >= L were dropped)
+template <typename T, int KMAX, int SPLIT, bool NTS>
+__global__ __launch_bounds__(DP_THREADS) void decode_packed_kernel(const T *__restrict__ buf, const int32_t *__restrict__ idx,
+                                                                  const int32_t *__restrict__ loc, const void *__restrict__ gates,
+                                                                  int gate_dtype, int Tn, int M, int k, int capacity, int num_experts,
+                                                                  const int32_t *__restrict__ off, T *__restrict__ out) {
+  decode_body<T, KMAX, SPLIT, NTS>(buf, idx, loc, gates, gate_dtype, Tn, M, k, capacity, num_experts, 0, 0, 1, out, (int)blockIdx.x,
+                                   (int)gridDim.x, off);
 }
 
 // decode + the routing "finish" in one launch (fused-location path, ep.hip): block 0 -- dispatched first: the finish is a longer
@@ -421,9 +433,17 @@ extern "C" int tutel_amd_fast_encode(const void *x, int dtype, const int32_t *sl
 template <typename T, int SPLIT, bool NTS>
 static void launch_decode_cfg(const void *buf, const int32_t *idx, const int32_t *loc, const void *gates,
                               int gate_dtype, int Tn, int M, int k, int capacity, int num_experts, int chunk_rows, int expert_slice,
-                              int ep_world, void *out, hipStream_t st) {
+                              int ep_world, void *out, hipStream_t st, const int32_t *pk_off) {
   int grid = dp_grid(Tn * SPLIT);
-#define DEC(KM) hipLaunchKernelGGL((decode_kernel<T, KM, SPLIT, NTS>), dim3(grid), dim3(DP_THREADS), 0, st, (const T *)buf, idx, loc, gates, gate_dtype, Tn, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, (T *)out)
+#define DEC(KM)                                                                                                                              \
+  do {                                                                                                                                       \
+    if (pk_off != nullptr)                                                                                                                   \
+      hipLaunchKernelGGL((decode_packed_kernel<T, KM, SPLIT, NTS>), dim3(grid), dim3(DP_THREADS), 0, st, (const T *)buf, idx, loc, gates,   \
+                         gate_dtype, Tn, M, k, capacity, num_experts, pk_off, (T *)out);                                                     \
+    else                                                                                                                                     \
+      hipLaunchKernelGGL((decode_kernel<T, KM, SPLIT, NTS>), dim3(grid), dim3(DP_THREADS), 0, st, (const T *)buf, idx, loc, gates,          \
+                         gate_dtype, Tn, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, (T *)out);                         \
+  } while (0)
   switch (k) {
     case 1: DEC(1); break;
     case 2: DEC(2); break;
@@ -444,11 +464,11 @@ static void launch_decode_cfg(const void *buf, const int32_t *idx, const int32_t
 template <typename T>
 static void launch_decode(const void *buf, const int32_t *idx, const int32_t *loc, const void *gates,
                           int gate_dtype, int Tn, int M, int k, int capacity, int num_experts, int chunk_rows, int expert_slice,
-                          int ep_world, void *out, hipStream_t st) {
+                          int ep_world, void *out, hipStream_t st, const int32_t *pk_off = nullptr) {
   int mode = tutel_get_option(TUTEL_OPT_DECODE);
   if (mode < 0) mode = TUTEL_DECODE_DEFAULT;
   const bool split = (mode & 1) && (size_t)M * sizeof(T) >= 2048;  // rows of at least two 1 KiB wave-loads
-#define GO(S, N) launch_decode_cfg<T, S, N>(buf, idx, loc, gates, gate_dtype, Tn, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, out, st)
+#define GO(S, N) launch_decode_cfg<T, S, N>(buf, idx, loc, gates, gate_dtype, Tn, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, out, st, pk_off)
   if (split) { if (mode & 2) GO(2, true); else GO(2, false); }
   else { if (mode & 2) GO(1, true); else GO(1, false); }
 #undef GO
@@ -489,6 +509,22 @@ extern "C" int tutel_amd_fast_decode(const void *buf, int dtype, const int32_t *
   else if (dtype == TUTEL_BF16) launch_decode<bf16_t>(buf, idx, loc, gates, gate_dtype, T, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, out, st);
   else launch_decode<f16_t>(buf, idx, loc, gates, gate_dtype, T, M, k, capacity, num_experts, chunk_rows, expert_slice, ep_world, out, st);
   TUTEL_CHECK_LAUNCH("tutel_amd_fast_decode");
+  return 0;
+}
+
+// internal (common.h): fast_decode of the packed dropless layout (dropless.hip): token t's choice j reads row off[idx] + loc, an entry
+// with loc >= row_limit was dropped by the capacity limit and contributes zero -- the same products and sums as the padded decode
+int tutel_decode_packed_launch(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype, int T,
+                               int M, int k, int row_limit, const int32_t *off, void *out, hipStream_t st) {
+  TUTEL_REQUIRE((dtype == TUTEL_BF16 || dtype == TUTEL_F16) && (gates == nullptr || dtype_ok(gate_dtype)) && k >= 1 && k <= 16 && M >= 1 &&
+                    row_limit >= 1 && off != nullptr,
+                "tutel_decode_packed_launch: bad arguments");
+  if (T == 0) return 0;
+  TUTEL_REQUIRE(buf && idx && loc && out && ((uintptr_t)buf % 16) == 0 && ((uintptr_t)out % 16) == 0, "tutel_decode_packed_launch: bad pointers");
+  StageScope stage(TUTEL_STAGE_DECODE, st);
+  if (dtype == TUTEL_BF16) launch_decode<bf16_t>(buf, idx, loc, gates, gate_dtype, T, M, k, row_limit, 0, 0, 0, 1, out, st, off);
+  else launch_decode<f16_t>(buf, idx, loc, gates, gate_dtype, T, M, k, row_limit, 0, 0, 0, 1, out, st, off);
+  TUTEL_CHECK_LAUNCH("tutel_decode_packed_launch");
   return 0;
 }
 

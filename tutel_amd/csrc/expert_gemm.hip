@@ -445,7 +445,7 @@ __global__ __launch_bounds__(BM * 2, 2) void expert_gemm_big_kernel(GemmArgs p) 
 // same whichever workgroup performs it) and run the epilogue on 64 x 128 each.  The hand-over is 128 KB out and 128 KB in per
 // workgroup.  Results differ from the unsplit kernel's in the last bits of the fp32 sum (two half sums added instead of one
 // running sum); a split launch is deterministic and reproduces itself.
-template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false, bool SPLITK = false>
+template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false, bool SPLITK = false, bool PACKED = false>
 __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint16_t *lds = reinterpret_cast<uint16_t *>(smem);  // [2][ tokens 2*GL_STAGE | weights 2*GL_STAGE ]
@@ -454,7 +454,16 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;  // 64-row group, 128-column group
 
-  const int nb = gridDim.x;
+  // PACKED (its own instantiation: the padded kernels compile as before): the grid is sized by the host's tile bound; the live
+  // blocks are the first *pk_ntiles x ntn (dispatched first, spread over every XCD by the hardware's round robin), numbered by the
+  // same XCD-contiguous remap over the live count
+  static_assert(!(PACKED && SPLITK), "the packed layout never splits K");
+  constexpr bool packed = PACKED;
+  int nb = gridDim.x;
+  if (packed) {
+    nb = min(nb, __builtin_amdgcn_readfirstlane(*p.pk_ntiles) * p.ntn);
+    if ((int)blockIdx.x >= nb) return;
+  }
   int w;
   {
     const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
@@ -463,17 +472,28 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
   const int half = SPLITK ? (w & 1) : 0;  // which half of K this workgroup multiplies (and which 128-column group it finishes)
   if (SPLITK) w >>= 1;
   const int tile_id = w;
-  const int mt = w % p.ntm;
-  const int nt = (w / p.ntm) % p.ntn;
-  const int e = w / (p.ntm * p.ntn);
-  const int m0 = mt * GB_BM, n0 = nt * 256;
-
-  int row_limit = p.R;
-  if (p.row_counts != nullptr) {
-    int c = p.row_counts[e];
-    c = (c + p.row_align - 1) / p.row_align * p.row_align;
-    row_limit = min(row_limit, c);
+  int e, nt, m0, row_limit;
+  bool rot_on = p.rot_on;
+  if constexpr (packed) {  // expert-major like the padded order: tile i's N-tiles are neighbours
+    const int ti = w / p.ntn;
+    nt = w % p.ntn;
+    e = __builtin_amdgcn_readfirstlane(p.pk_tiles[2 * ti]);
+    m0 = __builtin_amdgcn_readfirstlane(p.pk_tiles[2 * ti + 1]);
+    row_limit = __builtin_amdgcn_readfirstlane(p.pk_off[e + 1]);
+    rot_on = __builtin_amdgcn_readfirstlane(*p.pk_cap) < GB_BM;
+  } else {
+    const int mt = w % p.ntm;
+    nt = (w / p.ntm) % p.ntn;
+    e = w / (p.ntm * p.ntn);
+    m0 = mt * GB_BM;
+    row_limit = p.R;
+    if (p.row_counts != nullptr) {
+      int c = p.row_counts[e];
+      c = (c + p.row_align - 1) / p.row_align * p.row_align;
+      row_limit = min(row_limit, c);
+    }
   }
+  const int n0 = nt * 256;
   if (m0 >= row_limit) return;
 
   const uint16_t *Ae = reinterpret_cast<const uint16_t *>(p.A) + (size_t)e * p.a_stride_e;
@@ -494,7 +514,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
   int gr4[4], slot4[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) gr4[i] = min(m0 + 8 * ((i >> 1) * 16 + 2 * wid + (i & 1)) + (lane >> 3), p.R - 1);
-  gather_rows4(p, e, gr4, slot4);
+  gather_rows4(p, packed ? 0 : e, gr4, slot4);  // (packed: the slot map is indexed by the global row)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int piece = (i >> 1) * 16 + 2 * wid + (i & 1);
@@ -549,7 +569,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
 
   const int nk = SPLITK ? p.K / (2 * GL_BK) : p.K / GL_BK;  // K-tiles of THIS workgroup
   const int kt0 = SPLITK ? half * nk : 0;                   // its first K-tile (split launches never rotate: R >= 256)
-  const int rot = (!SPLITK && p.rot_on) ? (int)(((long long)(nt + 3 * e) * nk / p.ntn) % nk) : 0;
+  const int rot = (!SPLITK && rot_on) ? (int)(((long long)(nt + 3 * e) * nk / p.ntn) % nk) : 0;
 
 #define PP_KOFF(J, KO)                                     \
   int KO;                                                  \
@@ -846,6 +866,25 @@ static int launch_pp(const GemmArgs &a, hipStream_t st) {
   return ragged ? launch_pp_cfg<T, ACT, false, true>(b, st) : (early ? launch_pp_cfg<T, ACT, false, false, true>(b, st) : launch_pp_cfg<T, ACT, false>(b, st));
 }
 
+// packed dropless layout: the 256 x 256 ping-pong kernel over the tile table (see tutel_expert_gemm_packed).  Always the RAGGED form
+// (an expert's last tile is partial); W_ONCE by the padded path's rule with one tile per expert, which is what the grid shape says
+// when the experts cover the chip -- an expert with more rows than one tile then streams its weights once per tile, as padded does.
+template <typename T, int ACT>
+static int launch_pp_packed(const GemmArgs &a, int tiles_bound, hipStream_t st) {
+  GemmArgs b = a;
+  b.ntm = 1;
+  b.ntn = (a.N + 255) / 256;
+  const long long grid = (long long)tiles_bound * b.ntn;
+  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_expert_gemm_packed: grid too large");
+  const size_t lds = (size_t)8 * 64 * EP_PITCH;
+  auto kern = (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, true, true, false, false, true>
+                                                 : expert_gemm_pp_kernel<T, ACT, false, true, false, false, true>;
+  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GB_THREADS), lds, st, b);
+  TUTEL_CHECK_LAUNCH("tutel_expert_gemm_packed");
+  return 0;
+}
+
 template <typename T, bool KM, int ACT, int NI, int NS = 2, bool BUF = false, int BM = GB_BM, bool FL = false>
 static int launch_big(const GemmArgs &a, hipStream_t st) {
   GemmArgs b = a;
@@ -1063,6 +1102,7 @@ int tutel_gemm_args(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a
                 "tutel_amd_expert_gemm_gather: need a_rows_mod >= 1 and a 16-byte aligned zero row");
   a.ntm = (R + GM_BM - 1) / GM_BM;
   a.ntn = (N + GM_BN - 1) / GM_BN;
+  a.pk_off = a.pk_tiles = a.pk_ntiles = a.pk_cap = nullptr;
   return 0;
 }
 
@@ -1158,4 +1198,34 @@ extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_
   return expert_gemm_impl(X, 0, 0, R > 0 ? R : 1, ldx, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, D,
                           d_stride_e, 0, R > 0 ? R : 1, ldd, E_loc, R, N, K, dtype, act, row_counts, row_align,
                           slot_map, T, zero_row, nullptr, stream);
+}
+
+// internal (common.h): the grouped GEMM over the packed dropless layout (dropless.hip).  Rows are global packed rows of ONE array per
+// operand (stride between experts 0, one "rank" of rows_bound rows), so the kernel's row addressing, the out-of-range zero rows and
+// the row limit work unchanged; what changes per block is where its tile, expert and row limit come from (the device tile table).
+int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int64_t w_stride_e,
+                             int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
+                             int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
+                             hipStream_t st) {
+  TUTEL_REQUIRE(off && tiles && ntiles && cap && tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1),
+                "tutel_expert_gemm_packed: bad arguments");
+  GemmArgs a;
+  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W, 1, w_stride_e, ldw, bias, bias_stride_e, D, 0, 0, rows_bound, ldd, E, rows_bound,
+                                  N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, nullptr, nullptr, 0, nullptr, nullptr,
+                                  0, nullptr, &a);
+  if (brc != 0) return brc < 0 ? brc : 0;
+  if (!a.fits32) {
+    tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
+    return TUTEL_AMD_ENOTSUP;
+  }
+  a.pk_off = off; a.pk_tiles = tiles; a.pk_ntiles = ntiles; a.pk_cap = cap;
+  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  const bool bf = dtype == TUTEL_BF16;
+  switch (act) {
+    case TUTEL_ACT_NONE: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_NONE>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_NONE>(a, tiles_bound, st);
+    case TUTEL_ACT_RELU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_RELU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_RELU>(a, tiles_bound, st);
+    case TUTEL_ACT_GELU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_GELU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_GELU>(a, tiles_bound, st);
+    case TUTEL_ACT_SILU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_SILU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_SILU>(a, tiles_bound, st);
+    default: tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1;
+  }
 }

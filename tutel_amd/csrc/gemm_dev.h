@@ -93,6 +93,10 @@ struct GemmArgs {
   float *sk_ws; uint32_t *sk_flags;                           // split-K ping-pong kernel: partial accumulators + hand-over flags (see launch_pp_splitk)
   int ntm, ntn;
   int act_rt;                                                 // the activation when the tile is instantiated with GEMM_ACT_RUNTIME (expert_ffn.hip)
+  // packed dropless layout (the PACKED ping-pong kernel only; dropless.hip): rows are global packed rows, M-tile i of the
+  // launch is (expert pk_tiles[2i], first row pk_tiles[2i+1]), *pk_ntiles of them live; expert e owns rows [pk_off[e], pk_off[e+1]);
+  // the K-tile rotation is on when the device capacity *pk_cap is below 256 rows (what the padded launch of that capacity does)
+  const int32_t *pk_off, *pk_tiles, *pk_ntiles, *pk_cap;
 };
 
 // address of output row m of expert e (elements of 2 bytes).  Plain: D + e*stride_e + (m / rpw)*stride_w + (m % rpw)*ldd.

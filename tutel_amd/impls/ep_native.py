@@ -758,3 +758,142 @@ def forward_from_logits(layer, x, logits, k, capacity, degree, normalize_gate, w
         layer.protected_shape = torch.Size([layer.num_local_experts, W * used, ex.output_dim])
         return y, (l_aux[0] if l_aux is not None else None), cnt, used
     raise _lib.TutelAmdError("tutel_amd_moe_forward: the dropless capacity kept growing")
+
+
+# ---------------------------------------------------------------------------------------------
+# dropless routing without a host synchronisation: the packed layout (tutel_amd_moe_forward_packed, csrc/dropless.hip)
+# ---------------------------------------------------------------------------------------------
+def packed_plan(T, E, k, M, H, M_out, dtype, capacity_limit, alignment):
+    """tutel_amd_packed_plan as a dict (host arithmetic only, no GPU), or (None, reason) when the shape is not covered"""
+    p = _lib.PackedPlan()
+    rc = _lib.lib().tutel_amd_packed_plan(int(T), int(E), int(k), int(M), int(H), int(M_out), ops._DT[dtype] if isinstance(dtype, torch.dtype)
+                                          else int(dtype), int(capacity_limit), int(alignment), ctypes.byref(p))
+    if rc == _lib.ENOTSUP:
+        return None, _lib.lib().tutel_amd_last_error().decode("utf-8", "replace")
+    _lib.check(rc, "tutel_amd_packed_plan")
+    return {n: int(getattr(p, n)) for n, _ in _lib.PackedPlan._fields_}, None
+
+
+def packed_unsupported(layer, T, E, k, M, dtype, capacity_limit, alignment):
+    """why this layer's dropless forward cannot take the packed layout (None: it can)"""
+    ex = layer.experts
+    if layer.world_size != 1:
+        return "the packed dropless layout runs on a single rank only"
+    if not layer.is_postscore:
+        return "the packed dropless layout needs is_postscore=True (gates applied in the decode)"
+    if not ex.w2_kmajor_now():
+        return "the packed dropless layout needs the k-major fc2 copy of inference (eval mode, no gradient)"
+    plan, why = packed_plan(T, E, k, M, ex.batched_fc1_w.size(1), ex.output_dim, dtype, capacity_limit, alignment)
+    return why if plan is None else None
+
+
+class _PackedWorkspace:
+    """routing buffers + the packed workspace of tutel_amd_moe_forward_packed, sized by the host bound for T_cap tokens: nothing
+    in it depends on the routing, so a captured forward replays for any batch of the same token count"""
+
+    def __init__(self, layer, x, logits, k, T_cap, capacity_limit, alignment):
+        ex = layer.experts
+        E, dev, dt = logits.shape[1], x.device, x.dtype
+        M, H, Mo = x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim
+        self.T_cap = int(T_cap)
+        plan, why = packed_plan(T_cap, E, k, M, H, Mo, dt, capacity_limit, alignment)
+        if plan is None:
+            raise _lib.TutelAmdError(why)
+        self.pk_bytes = plan["ws_bytes"]
+        self.packed = torch.empty([max(self.pk_bytes, 256)], dtype=torch.uint8, device=dev)
+        self.offsets = torch.empty([E + 1], dtype=torch.int32, device=dev)
+        self.capacity = torch.zeros([1], dtype=torch.int32, device=dev)
+        self.idx = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
+        self.loc = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
+        self.gates = torch.empty([k, T_cap], dtype=logits.dtype, device=dev)
+        self.stats = torch.empty([1], dtype=torch.int32, device=dev)
+        rb = max(int(_lib.lib().tutel_amd_routing_workspace_bytes(64 * 128, E, k)),
+                 int(_lib.lib().tutel_amd_routing_workspace_bytes(T_cap, E, k)), 4)
+        self.ws = torch.empty([rb], dtype=torch.uint8, device=dev)
+        z = _zero_rows.get((dev, dt))
+        if z is None or z.numel() < M:
+            z = _zero_rows[(dev, dt)] = torch.zeros([max(M, 8192)], dtype=dt, device=dev)
+        self.zero_row = z
+        self.gate_partials, self.gate_partials_keep = None, []
+        a = _lib.EpArgs()
+        a.M, a.H, a.M_out, a.num_experts, a.world, a.k, a.degree = M, H, Mo, E, 1, k, 1
+        a.allow_sliced, a.dtype, a.act = 1, ops._DT[dt], ops.ACT_CODES[ex.fused_activation()]
+        a.is_postscore, a.fuse_encode, a.capacity = int(bool(layer.is_postscore)), 1, 0
+        a.idx, a.loc, a.gates, a.zero_row = self.idx.data_ptr(), self.loc.data_ptr(), self.gates.data_ptr(), z.data_ptr()
+        m = _lib.MoeArgs()
+        m.ep = a
+        m.logits_dtype = ops._DT[logits.dtype]
+        m.ws, m.ws_bytes, m.stats = self.ws.data_ptr(), self.ws.numel(), self.stats.data_ptr()
+        m.capacity_limit, m.alignment = int(capacity_limit), int(alignment)
+        pk = _lib.PackedArgs()
+        pk.ws, pk.ws_bytes = self.packed.data_ptr(), self.packed.numel()
+        pk.offsets, pk.capacity = self.offsets.data_ptr(), self.capacity.data_ptr()
+        self.margs, self.pargs = m, pk
+
+
+def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignment, gate_w=None):
+    """Dropless forward on the packed layout: x [T, M], logits [T, E] -> (y [T, M_out], l_aux, dispatch_count [E], capacity [1]),
+    all on the device -- no read-back, no retry, capturable.  None when the layout does not cover this layer / shape (the caller
+    then takes the padded path, whose results are the same bits)."""
+    ex = layer.experts
+    T, E = logits.shape
+    if packed_unsupported(layer, T, E, k, x.shape[1], x.dtype, capacity_limit, alignment) is not None:
+        return None
+    import collections
+    # (the limit is not part of the key: it follows T, and a workspace serves every call whose bound it holds)
+    key = ("packed", x.shape[1], x.dtype, x.device, E, logits.dtype, k, bool(layer.is_postscore), ex.fused_activation(), ops._stream(),
+           int(alignment))
+    plan = packed_plan(T, E, k, x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim, x.dtype, capacity_limit, alignment)[0]
+    need = plan["ws_bytes"]
+    cache = layer.__dict__.get("_ep_workspaces")
+    if not isinstance(cache, collections.OrderedDict):
+        cache = layer.__dict__["_ep_workspaces"] = collections.OrderedDict()
+    ws = None
+    for ck, w in cache.items():
+        if ck[0] == key and w.T_cap >= T and w.pk_bytes >= need:
+            cache.move_to_end(ck)
+            ws = w
+            break
+    if ws is None:
+        T_cap = _bucket_tokens(T)
+        ws = _PackedWorkspace(layer, x, logits, k, T_cap, capacity_limit, alignment)
+        cache[(key, T_cap, 0)] = ws
+        layer.__dict__["_ep_workspace_allocations"] = layer.__dict__.get("_ep_workspace_allocations", 0) + 1
+        while len(cache) > WS_MAX:
+            cache.popitem(last=False)
+    m, pk = ws.margs, ws.pargs
+    a = m.ep
+    a.T = T
+    m.capacity_limit = int(capacity_limit)
+    w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
+    dev = x.device
+    y = torch.empty([T, ex.output_dim], dtype=x.dtype, device=dev)
+    cnt = torch.empty([E], dtype=torch.int32, device=dev)
+    l_aux = torch.empty([1], dtype=logits.dtype, device=dev)
+    a.w2_kmajor = int(kmajor)
+    a.x, a.w1, a.w2, a.y = x.data_ptr(), w1.data_ptr(), w2.data_ptr(), y.data_ptr()
+    a.b1 = b1.data_ptr() if b1 is not None else None
+    a.b2 = b2.data_ptr() if b2 is not None else None
+    m.normalize_gate = int(bool(normalize_gate))
+    if gate_w is None:
+        m.logits, m.gate_w, m.logits_out = logits.data_ptr(), None, None
+    else:   # `logits` is a meta tensor: the projection runs inside the call, as in forward_from_logits
+        need_p = ops.gate_proj_splits(T, x.shape[1], E, x.dtype) * T * E
+        if ws.gate_partials is None or ws.gate_partials.numel() < need_p:
+            ws.gate_partials_keep.append(ws.gate_partials)   # a captured graph may still hold the old pointer
+            ws.gate_partials = torch.empty([need_p], dtype=torch.float32, device=dev)
+        m.logits, m.gate_w, m.logits_out = None, gate_w.data_ptr(), None
+        m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
+    m.dispatch_count, m.l_aux = cnt.data_ptr(), l_aux.data_ptr()
+    rc = _lib.lib().tutel_amd_moe_forward_packed(None, ctypes.byref(m), ctypes.byref(pk), ops._stream())
+    if rc == _lib.ENOTSUP:
+        return None
+    _lib.check(rc, "tutel_amd_moe_forward_packed")
+    if getattr(layer, "_keep_routing", False):
+        n = k * T
+        layer.last_routing = (ws.idx.view(-1)[:n].view(k, -1).clone(), ws.loc.view(-1)[:n].view(k, -1).clone())
+    # protected_shape in this mode: [local experts, host bound of the packed rows of ALL experts, M_out] -- the middle entry is a
+    # bound, not the capacity (that one stays on the device: layer.dropless_capacity)
+    layer.protected_shape = torch.Size([layer.num_local_experts, plan["rows_bound"], ex.output_dim])
+    layer.dropless_offsets = ws.offsets
+    return y, l_aux[0], cnt, ws.capacity

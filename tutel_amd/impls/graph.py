@@ -8,23 +8,50 @@ once and replayed with zero per-step host work:
     graphed = GraphedForward(layer, example_input)     # captures on a side stream
     y = graphed(x)                                     # copies x into the static input, replays
 
-The static input/output buffers are owned by the wrapper; `y` is valid until the next call."""
+The static input/output buffers are owned by the wrapper; `y` is valid until the next call.
+
+Dropless layers (capacity_factor <= 0) are captured on the packed layout only (csrc/dropless.hip: every buffer and grid sized by a
+host bound, the capacity kept on the device), and only when asked for:
+
+    graphed = GraphedForward(layer, example_input, capacity_factor=0.0, dropless_packed=True)
+
+Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes."""
 import torch
 
 
 class GraphedForward:
-    def __init__(self, layer, example, warmup=3, **forward_kwargs):
+    def __init__(self, layer, example, warmup=3, dropless_packed=False, **forward_kwargs):
         assert example.is_cuda, "HIP-graph capture needs a device tensor"
-        if forward_kwargs.get("capacity_factor", getattr(layer.gates[0], "capacity_factor", 1.0)) <= 0:
-            raise ValueError("dropless routing (capacity_factor <= 0) reads the capacity back to the host and cannot be captured")
+        if forward_kwargs.get("capacity_factor", getattr(layer.gates[0], "capacity_factor", 1.0)) <= 0 and not dropless_packed:
+            raise ValueError("dropless routing (capacity_factor <= 0) reads the capacity back to the host and cannot be captured "
+                             "(pass dropless_packed=True for the packed layout)")
+        # what the forward will run (MOELayer.forward: capacity_factor or the gate's own)
+        gate = layer.gates[forward_kwargs.get("gate_index", 0)]
+        dropless = (forward_kwargs.get("capacity_factor") or getattr(gate, "capacity_factor", 1.0)) <= 0
         self.layer, self.kwargs = layer, forward_kwargs
+        packed_before = getattr(layer, "dropless_packed", False)
+        if dropless:
+            layer.dropless_packed = True
+        try:
+            self._capture(layer, example, warmup, dropless, forward_kwargs)
+        finally:
+            if dropless:
+                layer.dropless_packed = packed_before
+
+    def _capture(self, layer, example, warmup, dropless, forward_kwargs):
         self._ep = getattr(layer, "world_size", 1) > 1
         self.static_in = example.clone()
         self.stream = torch.cuda.Stream(device=example.device)
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.no_grad(), torch.cuda.stream(self.stream):
-            for _ in range(warmup):
+            for i in range(max(warmup, 1) if dropless else warmup):
                 layer(self.static_in, **forward_kwargs)
+                ran = layer.__dict__.get("_dropless_packed_ran")
+                if dropless and i == 0 and ran is not True:
+                    torch.cuda.synchronize()
+                    raise ValueError("GraphedForward: this dropless forward cannot take the packed layout: " +
+                                     (ran or "it does not run through the one-call native path (autocast, training, batch-prioritised "
+                                             "routing, a non-gshard loss, fp32 or custom experts ...)"))
             torch.cuda.synchronize()
             # W > 1: only the IPC transport (plain kernels + events, epochs counted on the device) replays safely.  Captured RCCL
             # collectives replay ~200-400 times and then never complete (RCCL 2.26.6 in torch 2.10, profiles/r03_ep_streams.txt):

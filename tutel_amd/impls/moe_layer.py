@@ -94,6 +94,10 @@ class MOELayer(torch.nn.Module):
         self.use_2dh = use_2dh
         self.megablocks_size = 0
         self.protected_shape = None
+        # dropless (capacity_factor <= 0) on the PACKED layout (csrc/dropless.hip): no host read-back of the capacity, capturable in
+        # a HIP graph; same bits as the padded layout.  The capacity then stays on the device: self.dropless_capacity (int32 [1])
+        self.dropless_packed = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED", "0")) != 0
+        self.dropless_capacity = None
 
         experts = dict(experts)
         n_local = experts.pop("count_per_node", 1) if "count_per_node" in experts else experts.pop("num_experts_per_device", 1)
@@ -303,6 +307,18 @@ class MOELayer(torch.nn.Module):
         k = min(top_k, E)
         spe = (T + E - 1) // E
         xc = x if x.is_contiguous() else x.contiguous()
+        if cf <= 0 and self.dropless_packed:   # dropless on the packed layout: the capacity never leaves the device
+            limit = k * int(-cf * spe) if cf < 0 else 0
+            why = ep_native.packed_unsupported(self, T, E, k, xc.shape[1], xc.dtype, limit, alignment)
+            res = None if why is not None else ep_native.forward_packed(self, xc, logits.contiguous(), k, self.normalize_gate, limit,
+                                                                         alignment, gate_w=gate_w)
+            self._dropless_packed_ran = True if res is not None else (why or "the packed layout does not cover this shape")
+            if res is not None:
+                y, l_aux, cnt, cap = res
+                self.megablocks_size = megablocks_size
+                self.dispatch_count = cnt
+                self.dropless_capacity = cap
+                return y, l_aux
         if cf <= 0:   # dropless: capacity = max expert load, read back inside the native call (fast_dispatch.py:191-199)
             guess = (k * spe * 3 // 2 + 31) // 32 * 32
             res = ep_native.forward_from_logits(self, xc, logits.contiguous(), k, guess, 1, self.normalize_gate, want_loss=True,
@@ -355,6 +371,7 @@ class MOELayer(torch.nn.Module):
 
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
+        self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
         if self.skip_moe:
             out = input
             out.l_aux = None
