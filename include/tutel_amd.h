@@ -253,6 +253,18 @@ int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int64_t a_strid
                               int act, const int32_t *row_counts, int row_align,
                               tutel_stream_t stream);
 
+/* Fused gate/up form of a SwiGLU expert: D = round(act(A @ W_gate^T)) * (A @ W_up^T), rounded once to `dtype` -- ONE launch
+ * for what tutel_amd_expert_gemm (act, on W_gate) followed by tutel_amd_expert_gemm_glu (act = none, on W_up, G = the first
+ * result) compute, with the same bits: each workgroup streams one token tile and the same 128 features of both weights, so the
+ * gating operand never goes through memory and the token rows are read once.
+ *   W_gate, W_up  [E_loc, N, K] k-major (the eval-mode copies of W_fc1 / W_fc2), both with stride w_stride_e / ldw; no bias
+ * A, D, row_counts / row_align and the other arguments as tutel_amd_expert_gemm.  Operands past 2 GiB return
+ * TUTEL_AMD_ENOTSUP with nothing launched. */
+int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
+                                  const void *W_gate, const void *W_up, int64_t w_stride_e, int ldw, void *D, int64_t d_stride_e,
+                                  int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
+                                  const int32_t *row_counts, int row_align, tutel_stream_t stream);
+
 /* ---- expert-parallel pipeline ----------------------------------------
  * Replaces the reference's native all-to-all layer: the private NCCL communicator
  * (get_nccl_unique_id / init_nccl, custom_kernel.cpp:341-365), its stream + event table (:327-338,
@@ -492,6 +504,16 @@ size_t tutel_amd_moe_packed_workspace_bytes(int T, int E, int k, int M, int H, i
                                             int alignment); /* 0: not covered / bad sizes */
 int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_args_t *args,
                                  const tutel_amd_packed_args_t *packed, tutel_stream_t stream);
+/* tutel_amd_moe_forward_packed for SwiGLU experts (y = (act(x @ W_fc1) * (x @ W_fc2)) @ W_fc3 per expert, no biases):
+ *   args->ep.w1  W_gate = k-major W_fc1 [E, H, M];   w_up = k-major W_fc2 [E, H, M];   args->ep.w2 = k-major W_fc3 [E, M, H]
+ *   args->ep.b1 / b2 NULL, ep.act the gate activation, ep.M_out = M, ep.w2_kmajor = 1.
+ * Launches: routing -> layout -> the fused gate/up GEMM (tutel_amd_expert_gemm_gate_up's kernel on the packed rows) -> the W_fc3
+ * GEMM -> decode.  Preconditions, workspace (tutel_amd_moe_packed_workspace_bytes with H and M_out = M), outputs and
+ * TUTEL_AMD_ENOTSUP as tutel_amd_moe_forward_packed.  The results are bit-identical to the padded dropless SwiGLU forward
+ * (buckets [E, C, M] with C read back, then tutel_amd_expert_gemm(act) on W_fc1, tutel_amd_expert_gemm_glu on W_fc2 and
+ * tutel_amd_expert_gemm on W_fc3): same rows, same K order and rotation, act(x @ W_fc1) rounded before the product. */
+int tutel_amd_moe_forward_packed_glu(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_args_t *args,
+                                     const tutel_amd_packed_args_t *packed, const void *w_up, tutel_stream_t stream);
 
 /* stage markers: roctx ranges (rocprofv3 --marker-trace); the pipeline above emits tutel_amd.fast_encode /
  * all_to_all / expert_fc1 / expert_fc2 / fast_decode itself.  No-ops when libroctx64 is not in the process

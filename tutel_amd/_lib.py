@@ -43,6 +43,8 @@ SIGNATURES = {
                                   _i, _i, _i, _i, _i, _i, _i, _vp]),
     "tutel_amd_expert_gemm_glu": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _i64,
                                        _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "tutel_amd_expert_gemm_gate_up": (_i, [_vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i, _i,
+                                           _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "tutel_amd_set_option": (_i, [_i, _i]),
     "tutel_amd_probe_tr16": (_i, [_vp, _vp]),
 }
@@ -87,6 +89,7 @@ SIGNATURES.update({
     "tutel_amd_packed_plan": (_i, [_i] * 9 + [ctypes.POINTER(PackedPlan)]),
     "tutel_amd_moe_packed_workspace_bytes": (_sz, [_i] * 9),
     "tutel_amd_moe_forward_packed": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp]),
+    "tutel_amd_moe_forward_packed_glu": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp, _vp]),
     "tutel_amd_ep_load_rccl": (_i, [ctypes.c_char_p]),
     "tutel_amd_ep_unique_id": (_i, [_vp, _sz]),
     "tutel_amd_ep_comm_create": (_i, [_vp, _sz, _i, _i, ctypes.POINTER(_vp)]),

@@ -167,8 +167,10 @@ extern "C" size_t tutel_amd_moe_packed_workspace_bytes(int T, int E, int k, int 
   return tutel_amd_packed_plan(T, E, k, M, H, M_out, dtype, capacity_limit, alignment, &pl) == 0 ? pl.ws_bytes : 0;
 }
 
-extern "C" int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, const tutel_amd_packed_args_t *pk,
-                                            tutel_stream_t stream) {
+// w_up == NULL: the ffn experts (fc1 = act(x @ w1^T + b1), fc2); else SwiGLU experts: the fused gate/up GEMM on (w1, w_up), then
+// w2 (the down projection) -- no biases
+static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, const tutel_amd_packed_args_t *pk, const void *w_up,
+                          tutel_stream_t stream) {
   TUTEL_REQUIRE(m != nullptr && pk != nullptr, "tutel_amd_moe_forward_packed: null arguments");
   const tutel_amd_ep_args_t &a = m->ep;
   const int T = a.T, E = a.num_experts, k = a.k, M = a.M, H = a.H, Mo = a.M_out;
@@ -200,6 +202,12 @@ extern "C" int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *c, const tutel_
   TUTEL_REQUIRE(m->ws_bytes >= tutel_amd_routing_workspace_bytes(T, E, k), "tutel_amd_moe_forward_packed: routing workspace too small (%zu bytes, need %zu)",
                 m->ws_bytes, tutel_amd_routing_workspace_bytes(T, E, k));
   TUTEL_REQUIRE(a.act >= TUTEL_ACT_NONE && a.act <= TUTEL_ACT_SILU, "tutel_amd_moe_forward_packed: unknown activation %d", a.act);
+  TUTEL_REQUIRE(w_up == nullptr || (a.b1 == nullptr && a.b2 == nullptr && ((uintptr_t)w_up & 15) == 0),
+                "tutel_amd_moe_forward_packed_glu: SwiGLU experts take no biases, and w_up must be 16-byte aligned");
+  if (w_up != nullptr && a.act != TUTEL_ACT_RELU && a.act != TUTEL_ACT_GELU && a.act != TUTEL_ACT_SILU) {
+    tutel_set_error("tutel_amd_moe_forward_packed_glu: not covered: the gate activation must be relu, gelu or silu");
+    return TUTEL_AMD_ENOTSUP;
+  }
   auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
   TUTEL_REQUIRE(al16(a.x) && al16(a.w1) && al16(a.w2) && al16(a.y) && al16(a.zero_row) && ((uintptr_t)a.b1 & 7) == 0 && ((uintptr_t)a.b2 & 7) == 0,
                 "tutel_amd_moe_forward_packed: x / weights / y / zero_row must be 16-byte aligned (biases 8-byte)");
@@ -247,11 +255,26 @@ extern "C" int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *c, const tutel_
                        m->alignment, pl.rows_bound, pl.tiles_bound, pk->offsets, tiles, ntiles, pk->capacity, slot);
     TUTEL_CHECK_LAUNCH("tutel_amd_moe_forward_packed (layout)");
   }
-  rc = tutel_expert_gemm_packed(a.x, M, slot, T, a.zero_row, a.w1, (int64_t)H * M, M, a.b1, H, hid, H, E, pl.rows_bound, H, M, a.dtype,
-                                a.act, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
+  if (w_up != nullptr)
+    rc = tutel_expert_gemm_gate_up_packed(a.x, M, slot, T, a.zero_row, a.w1, w_up, (int64_t)H * M, M, hid, H, E, pl.rows_bound, H, M, a.dtype,
+                                          a.act, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
+  else
+    rc = tutel_expert_gemm_packed(a.x, M, slot, T, a.zero_row, a.w1, (int64_t)H * M, M, a.b1, H, hid, H, E, pl.rows_bound, H, M, a.dtype,
+                                  a.act, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
   if (rc) return rc;
   rc = tutel_expert_gemm_packed(hid, H, nullptr, 0, nullptr, a.w2, (int64_t)Mo * H, H, a.b2, Mo, outb, Mo, E, pl.rows_bound, Mo, H, a.dtype,
                                 TUTEL_ACT_NONE, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
   if (rc) return rc;
   return tutel_decode_packed_launch(outb, a.dtype, a.idx, a.loc, a.gates, m->logits_dtype, T, Mo, k, L, pk->offsets, a.y, st);
+}
+
+extern "C" int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, const tutel_amd_packed_args_t *pk,
+                                            tutel_stream_t stream) {
+  return forward_packed(c, m, pk, nullptr, stream);
+}
+
+extern "C" int tutel_amd_moe_forward_packed_glu(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, const tutel_amd_packed_args_t *pk,
+                                                const void *w_up, tutel_stream_t stream) {
+  TUTEL_REQUIRE(w_up != nullptr, "tutel_amd_moe_forward_packed_glu: null w_up");
+  return forward_packed(c, m, pk, w_up, stream);
 }

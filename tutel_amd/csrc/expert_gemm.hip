@@ -445,7 +445,19 @@ __global__ __launch_bounds__(BM * 2, 2) void expert_gemm_big_kernel(GemmArgs p) 
 // same whichever workgroup performs it) and run the epilogue on 64 x 128 each.  The hand-over is 128 KB out and 128 KB in per
 // workgroup.  Results differ from the unsplit kernel's in the last bits of the fp32 sum (two half sums added instead of one
 // running sum); a split launch is deterministic and reproduces itself.
-template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false, bool SPLITK = false, bool PACKED = false>
+//
+// GATE_UP: the gate and up products of a SwiGLU expert in one pass, h = round(act(x @ Wg^T)) * (x @ Wu^T) rounded once
+// (tutel_amd_expert_gemm_gate_up).  The 256 weight rows of a K-tile are 128 features of Wg (strips 0, 1: the first DMA half) and
+// the SAME 128 features of Wu (strips 2, 3: the second half, through a second descriptor), laid out so that wave (wm, wn) holds
+// gate strip s in acc[s] and up strip s in acc[s + 2] for features n0 + wn*64 + s*32 + 0..31: the same (row, feature) in the same
+// lane and register.  The GLU is then elementwise in registers and the 256 x 128 output tile leaves through the NI = 2 LDS
+// epilogue.  Same DMA pieces, phases, waits and barriers as the plain kernel; per output element the same MFMAs in the same K
+// order as the act GEMM on Wg and the gated GEMM on Wu -- the rotation is keyed on the feature's 256-column tile (nt >> 1 of
+// ceil(N / 128) tiles here), and the activation is rounded to T before the product, as the stored gating operand is -- so the
+// bits are those of the two launches.  The GLU is applied while the tile is staged (gemm_epilogue_lds<.., GATE_UP>), 4 values at
+// a time: computed over all 64 values before staging, or switched on the activation at run time, GELU spilled 28-40 bytes.
+template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false, bool SPLITK = false, bool PACKED = false,
+          bool GATE_UP = false>
 __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint16_t *lds = reinterpret_cast<uint16_t *>(smem);  // [2][ tokens 2*GL_STAGE | weights 2*GL_STAGE ]
@@ -458,6 +470,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
   // blocks are the first *pk_ntiles x ntn (dispatched first, spread over every XCD by the hardware's round robin), numbered by the
   // same XCD-contiguous remap over the live count
   static_assert(!(PACKED && SPLITK), "the packed layout never splits K");
+  static_assert(!GATE_UP || (!SPLITK && !EARLY_BIAS), "the gate/up form: no split, no bias");
   constexpr bool packed = PACKED;
   int nb = gridDim.x;
   if (packed) {
@@ -493,7 +506,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
       row_limit = min(row_limit, c);
     }
   }
-  const int n0 = nt * 256;
+  const int n0 = nt * (GATE_UP ? 128 : 256);
   if (m0 >= row_limit) return;
 
   const uint16_t *Ae = reinterpret_cast<const uint16_t *>(p.A) + (size_t)e * p.a_stride_e;
@@ -531,7 +544,8 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
       a_off[i] = (int)(unsigned)(off * 2 + c * 16);
     }
     {
-      const int col = ((r >> 5) & 1) * 128 + (r >> 6) * 32 + (r & 31);  // LDS row r -> column of the 256-column tile
+      // LDS row r -> column of the 256-column tile; GATE_UP: feature of the 128-column tile (strips 2, 3 repeat 0, 1 on Wu)
+      const int col = GATE_UP ? ((r >> 5) & 1) * 64 + ((r >> 6) & 1) * 32 + (r & 31) : ((r >> 5) & 1) * 128 + (r >> 6) * 32 + (r & 31);
       const int gn = min(n0 + col, p.N - 1);
       w_off[i] = (int)(unsigned)(((size_t)gn * p.ldw) * 2 + c * 16);
     }
@@ -542,6 +556,10 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
       const_cast<uint16_t *>(p.a_rows != nullptr ? reinterpret_cast<const uint16_t *>(p.A) : Ae), 0,
       p.a_span_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(We), 0, -1, 0x00020000);
+  // GATE_UP: the second DMA half (strips 2, 3) reads Wu at the same offsets
+  const __amdgpu_buffer_rsrc_t rs_u = GATE_UP ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(reinterpret_cast<const uint16_t *>(p.w_up) +
+                                                                                                           (size_t)e * p.w_stride_e), 0, -1, 0x00020000)
+                                              : rs_w;
   const int piece_lo = 2 * wid * 512, piece_hi = (16 + 2 * wid) * 512;  // element offsets of the wave's pieces in a 32 KB tile
   // W_ONCE (one M-tile per expert and the chip covered): every weight byte is fetched by exactly one block ->
   // no-allocate loads (see expert_gemm_big_kernel); a template axis so the issue path has no branch
@@ -569,7 +587,8 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
 
   const int nk = SPLITK ? p.K / (2 * GL_BK) : p.K / GL_BK;  // K-tiles of THIS workgroup
   const int kt0 = SPLITK ? half * nk : 0;                   // its first K-tile (split launches never rotate: R >= 256)
-  const int rot = (!SPLITK && rot_on) ? (int)(((long long)(nt + 3 * e) * nk / p.ntn) % nk) : 0;
+  // (GATE_UP: p.ntn counts 128-column tiles; the rotation is that of the 256-column tile holding the features)
+  const int rot = (!SPLITK && rot_on) ? (int)(((long long)((GATE_UP ? nt >> 1 : nt) + 3 * e) * nk / (GATE_UP ? (p.ntn + 1) >> 1 : p.ntn)) % nk) : 0;
 
 #define PP_KOFF(J, KO)                                     \
   int KO;                                                  \
@@ -589,8 +608,8 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
   do {                                                                                   \
     PP_KOFF(J, ko_);                                                                     \
     uint16_t *d_ = lds + (BUF) * PP_BUF + 2 * GL_STAGE + ((HALF) ? piece_hi : piece_lo); \
-    bdma16<W_ONCE>(rs_w, w_off[2 * (HALF)], ko_, d_);                                    \
-    bdma16<W_ONCE>(rs_w, w_off[2 * (HALF) + 1], ko_, d_ + 512);                          \
+    bdma16<W_ONCE>(GATE_UP && (HALF) ? rs_u : rs_w, w_off[2 * (HALF)], ko_, d_);         \
+    bdma16<W_ONCE>(GATE_UP && (HALF) ? rs_u : rs_w, w_off[2 * (HALF) + 1], ko_, d_ + 512); \
   } while (0)
 
   u32x4 fa[4][2], fw[4];
@@ -731,14 +750,21 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) __hip_atomic_store(p.sk_flags + pslot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // consumed: the slot is free for the next launch
   }
-  if (!EARLY_BIAS) PP_LOAD_BIAS();
-#undef PP_LOAD_BIAS
-  if ((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15)) {
-    gemm_epilogue<T, ACT, 4>(p, acc, bias_r, e, m0, n0, wm, wn, l31, kg, row_limit);  // rows not 16-byte aligned
-    return;
+  if constexpr (GATE_UP) {
+    // up * round_T(act(gate)) per (row, feature), rounded once, 64 x 64 per wave through the NI = 2 LDS epilogue (the host takes
+    // 16-byte aligned output rows only: the direct-store epilogue is not instantiated)
+    uint2 no_bias[2][4] = {};
+    gemm_epilogue_lds<T, ACT, 2, true>(p, acc, no_bias, smem + wid * (64 * (2 * 64 + 16)), e, m0, n0, wm, wn, lane, row_limit);
+  } else {
+    if (!EARLY_BIAS) PP_LOAD_BIAS();
+    if ((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15)) {
+      gemm_epilogue<T, ACT, 4>(p, acc, bias_r, e, m0, n0, wm, wn, l31, kg, row_limit);  // rows not 16-byte aligned
+      return;
+    }
+    // after the final barrier no wave reads the K-tile buffers any more and every DMA has landed: LDS is free
+    gemm_epilogue_lds<T, ACT>(p, acc, bias_r, smem + wid * (64 * EP_PITCH), e, m0, n0, wm, wn, lane, row_limit);
   }
-  // after the final barrier no wave reads the K-tile buffers any more and every DMA has landed: LDS is free
-  gemm_epilogue_lds<T, ACT>(p, acc, bias_r, smem + wid * (64 * EP_PITCH), e, m0, n0, wm, wn, lane, row_limit);
+#undef PP_LOAD_BIAS
 }
 
 // > 64 KB of dynamic LDS needs hipFuncSetAttribute -- once per (kernel, DEVICE): the attribute belongs to the function object
@@ -882,6 +908,26 @@ static int launch_pp_packed(const GemmArgs &a, int tiles_bound, hipStream_t st) 
   if (!tutel_lds_optin((const void *)kern, lds)) return -1;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GB_THREADS), lds, st, b);
   TUTEL_CHECK_LAUNCH("tutel_expert_gemm_packed");
+  return 0;
+}
+
+// fused gate/up GEMM (GATE_UP ping-pong kernel): 256 x 128 output tiles, ntn = ceil(N / 128).  Padded: grid E_loc x M-tiles x N-tiles;
+// packed: tiles_bound x N-tiles over the tile table.  Always the RAGGED form (dropless row counts).  The packed form (the layer's hot
+// path) takes W_ONCE by the padded rule -- one M-tile per expert and the chip covered: every weight byte is fetched by one block --
+// the padded entry point never does (one instantiation fewer per activation; the hint changes no bits).
+template <typename T, int ACT, bool PACKED>
+static int launch_gate_up(const GemmArgs &a, int tiles_bound, hipStream_t st) {
+  GemmArgs b = a;
+  b.ntm = PACKED ? 1 : (a.R + GB_BM - 1) / GB_BM;
+  b.ntn = (a.N + 127) / 128;
+  const long long grid = PACKED ? (long long)tiles_bound * b.ntn : (long long)a.E_loc * b.ntm * b.ntn;
+  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_gate_up: grid too large");
+  const size_t lds = (size_t)8 * 64 * EP_PITCH;
+  auto kern = PACKED && (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, PACKED, true, false, false, PACKED, true>
+                                                          : expert_gemm_pp_kernel<T, ACT, false, true, false, false, PACKED, true>;
+  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GB_THREADS), lds, st, b);
+  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_gate_up");
   return 0;
 }
 
@@ -1103,6 +1149,7 @@ int tutel_gemm_args(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a
   a.ntm = (R + GM_BM - 1) / GM_BM;
   a.ntn = (N + GM_BN - 1) / GM_BN;
   a.pk_off = a.pk_tiles = a.pk_ntiles = a.pk_cap = nullptr;
+  a.w_up = nullptr;
   return 0;
 }
 
@@ -1228,4 +1275,62 @@ int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int 
     case TUTEL_ACT_SILU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_SILU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_SILU>(a, tiles_bound, st);
     default: tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1;
   }
+}
+
+// ---- fused gate/up GEMM of a SwiGLU expert (GATE_UP ping-pong kernel) -------------------------------------------------------------
+static int gate_up_notsup(const char *why) {
+  tutel_set_error("tutel_amd_expert_gemm_gate_up: not covered: %s", why);
+  return TUTEL_AMD_ENOTSUP;
+}
+
+template <bool PACKED>
+static int gate_up_act(const GemmArgs &a, int dtype, int act, int tiles_bound, hipStream_t st) {
+  const bool bf = dtype == TUTEL_BF16;
+  switch (act) {
+    case TUTEL_ACT_RELU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_RELU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_RELU, PACKED>(a, tiles_bound, st);
+    case TUTEL_ACT_GELU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_GELU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_GELU, PACKED>(a, tiles_bound, st);
+    case TUTEL_ACT_SILU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_SILU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_SILU, PACKED>(a, tiles_bound, st);
+    default: return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  }
+}
+
+extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
+                                             const void *W_gate, const void *W_up, int64_t w_stride_e, int ldw, void *D, int64_t d_stride_e,
+                                             int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
+                                             const int32_t *row_counts, int row_align, tutel_stream_t stream) {
+  if (act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  GemmArgs a;
+  const int brc = tutel_gemm_args(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W_gate, 1, w_stride_e, ldw, nullptr, 0, D, d_stride_e, d_stride_w,
+                                  d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, row_counts, row_align, nullptr, 0, nullptr, nullptr, nullptr, 0,
+                                  nullptr, nullptr, 0, nullptr, &a);
+  if (brc != 0) return brc < 0 ? brc : 0;
+  TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_amd_expert_gemm_gate_up: W_up must be a 16-byte aligned pointer");
+  if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
+  if ((ldd & 7) || (d_stride_e & 7) || (d_stride_w & 7) || ((uintptr_t)D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
+  a.w_up = W_up;
+  hipStream_t st = (hipStream_t)stream;
+  StageScope stage(TUTEL_STAGE_FC1, st);
+  return gate_up_act<false>(a, dtype, act, 0, st);
+}
+
+// internal (common.h): the same over the packed dropless layout, arguments as tutel_expert_gemm_packed plus W_up
+int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,
+                                     const void *W_up, int64_t w_stride_e, int ldw, void *D, int ldd, int E, int rows_bound, int N, int K,
+                                     int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap,
+                                     int tiles_bound, hipStream_t st) {
+  TUTEL_REQUIRE(off && tiles && ntiles && cap && tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1),
+                "tutel_expert_gemm_gate_up_packed: bad arguments");
+  if (act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  GemmArgs a;
+  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W_gate, 1, w_stride_e, ldw, nullptr, 0, D, 0, 0, rows_bound, ldd, E, rows_bound,
+                                  N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, nullptr, nullptr, 0, nullptr, nullptr,
+                                  0, nullptr, &a);
+  if (brc != 0) return brc < 0 ? brc : 0;
+  TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
+  if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
+  if ((ldd & 7) || ((uintptr_t)D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
+  a.w_up = W_up;
+  a.pk_off = off; a.pk_tiles = tiles; a.pk_ntiles = ntiles; a.pk_cap = cap;
+  StageScope stage(TUTEL_STAGE_FC1, st);
+  return gate_up_act<true>(a, dtype, act, tiles_bound, st);
 }

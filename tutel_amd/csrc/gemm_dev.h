@@ -97,6 +97,8 @@ struct GemmArgs {
   // launch is (expert pk_tiles[2i], first row pk_tiles[2i+1]), *pk_ntiles of them live; expert e owns rows [pk_off[e], pk_off[e+1]);
   // the K-tile rotation is on when the device capacity *pk_cap is below 256 rows (what the padded launch of that capacity does)
   const int32_t *pk_off, *pk_tiles, *pk_ntiles, *pk_cap;
+  // fused gate/up GEMM of a SwiGLU expert (the GATE_UP ping-pong kernel only): the up-projection weights, W's layout and strides
+  const void *w_up;
 };
 
 // address of output row m of expert e (elements of 2 bytes).  Plain: D + e*stride_e + (m / rpw)*stride_w + (m % rpw)*ldd.
@@ -218,9 +220,12 @@ __device__ __forceinline__ void bdma16(__amdgpu_buffer_rsrc_t rs, int voff, int 
 // 256-byte row segments, 16 bytes per lane, 4 rows per instruction: 16 store instructions per wave.
 // Values are computed exactly as in gemm_epilogue (fp32 bias add, activation, optional gating product, one
 // rounding) -- only the path to memory differs.
+// GATE_UP (the fused gate/up ping-pong kernel, expert_gemm.hip): acc holds 2 * NI column tiles, the gate products in [0, NI) and the
+// up products of the same features in [NI, 2 * NI); the value of column tile ni is up * g, g = act(gate) rounded to T -- what the
+// act launch stores and the gated launch multiplies by (`v *= mul` below) -- with no bias and no gating operand.
 #define EP_PITCH 272   // NI = 4 (128 columns per wave); NI = 2: 144
-template <typename T, int ACT, int NI = 4>
-__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&acc)[NI][2], uint2 (&bias_r)[NI][4],
+template <typename T, int ACT, int NI = 4, bool GATE_UP = false>
+__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&acc)[GATE_UP ? 2 * NI : NI][2], uint2 (&bias_r)[NI][4],
                                                   unsigned char *stage, int e, int m0, int n0, int wm, int wn,
                                                   int lane, int row_limit) {
   constexpr int PITCH = NI * 64 + 16;  // bytes per staged row (NI*32 features + 16 B: see EP_PITCH)
@@ -244,6 +249,18 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = acc[ni][mi][rg * 4 + r];
+        if constexpr (GATE_UP) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            // the fp32 activation is materialised before it is rounded: for fp16 hipcc otherwise folds GELU's last multiply and the
+            // rounding into one v_fma_mixlo_f16 -- a single rounding of the exact product, not the act launch's two
+            float a = activate<ACT>(v[r]);
+            asm("" : "+v"(a));
+            const T g = Elem<T>::from_f32(a);
+            v[r] = acc[NI + ni][mi][rg * 4 + r];
+            v[r] *= Elem<T>::to_f32(g);
+          }
+        } else {
         if (has_bias) {
           const uint2 bb = bias_r[ni][rg];
           uint16_t b4[4] = {(uint16_t)(bb.x & 0xffff), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffff), (uint16_t)(bb.y >> 16)};
@@ -256,6 +273,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = activate<ACT>(v[r]);
+        }
         if (Me) {
           const int n = min(n0 + wn * (NI * 32) + ni * 32 + rg * 8 + kg * 4, p.N - 4);
           const uint2 mm = *reinterpret_cast<const uint2 *>(Me + roff + n);

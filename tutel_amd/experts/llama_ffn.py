@@ -12,6 +12,8 @@ Forward:
     grouped GEMM (tutel_amd_expert_gemm): the activation is fused into the W_fc1 launch and the
     gating product into the W_fc2 launch (its epilogue multiplies by the stored act(x @ W_fc1));
   * anything else -> ATen matmuls, op for op as the reference.
+A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
+the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.
 """
 import torch
 
@@ -70,12 +72,19 @@ class LlamaFFNNetwork(torch.nn.Module):
         return (x.dim() == 3 and x.dtype == self.W_fc1.dtype and ops.gemm_supported(x.dtype, H, M)
                 and ops.gemm_supported(x.dtype, M, H) and self.fused_activation() is not None)
 
+    def kmajor_weights(self):
+        """the eval-mode k-major copies (W_fc1 and W_fc2 [E, H, M], W_fc3 [E, M, H]) that forward_fused runs on: the operands of the
+        packed dropless forward (impls/ep_native.py, tutel_amd_moe_forward_packed_glu)"""
+        w1, w2, w3 = (self.W_fc1.view(self.W_fc1_full_shape), self.W_fc2.view(self.W_fc2_full_shape),
+                      self.W_fc3.view(self.W_fc3_full_shape))
+        return self._kmajor.get("fc1", w1), self._kmajor.get("fc2", w2), self._kmajor.get("fc3", w3)
+
     def forward_fused(self, x):
         w1, w2, w3 = (self.W_fc1.view(self.W_fc1_full_shape), self.W_fc2.view(self.W_fc2_full_shape),
                       self.W_fc3.view(self.W_fc3_full_shape))
         km = _PREPACK and not self.training  # eval: weights laid out k-major once (see KMajorCache)
         if km:
-            w1, w2, w3 = self._kmajor.get("fc1", w1), self._kmajor.get("fc2", w2), self._kmajor.get("fc3", w3)
+            w1, w2, w3 = self.kmajor_weights()
         g = ops.expert_gemm(x, w1, None, km, act=self.fused_activation())
         h = ops.expert_gemm(x, w2, None, km, mul=g)
         return ops.expert_gemm(h, w3, None, km)

@@ -774,6 +774,31 @@ def packed_plan(T, E, k, M, H, M_out, dtype, capacity_limit, alignment):
     return {n: int(getattr(p, n)) for n, _ in _lib.PackedPlan._fields_}, None
 
 
+def _swiglu(ex):
+    """SwiGLU experts (experts/llama_ffn.py): the packed forward runs the fused gate/up GEMM (tutel_amd_moe_forward_packed_glu)"""
+    from ..experts.llama_ffn import LlamaFFNNetwork
+    return isinstance(ex, LlamaFFNNetwork)
+
+
+def _hidden_size(ex):
+    return ex.W_fc1_full_shape[2] if _swiglu(ex) else ex.batched_fc1_w.size(1)
+
+
+def _swiglu_unsupported(ex, dtype):
+    from ..experts import ffn
+    if ex.training or (torch.is_grad_enabled() and any(p.requires_grad for p in ex.parameters())):
+        return "the packed SwiGLU forward is inference only (eval mode, no autograd)"
+    if ex.sharded_count > 1:
+        return "the packed SwiGLU forward needs unsharded experts (sharded_count = 1)"
+    if ex.fused_activation() not in ("relu", "gelu", "silu"):
+        return "the packed SwiGLU forward needs a gate activation the fused GEMM recognises (relu, gelu or silu)"
+    if ex.W_fc1.dtype != dtype:
+        return "the packed SwiGLU forward needs the expert weights in the tokens' dtype"
+    if not ffn._PREPACK:
+        return "the packed SwiGLU forward needs the k-major weight copies (TUTEL_AMD_PREPACK=0 switches them off)"
+    return None
+
+
 def packed_unsupported(layer, T, E, k, M, dtype, capacity_limit, alignment):
     """why this layer's dropless forward cannot take the packed layout (None: it can)"""
     ex = layer.experts
@@ -781,9 +806,13 @@ def packed_unsupported(layer, T, E, k, M, dtype, capacity_limit, alignment):
         return "the packed dropless layout runs on a single rank only"
     if not layer.is_postscore:
         return "the packed dropless layout needs is_postscore=True (gates applied in the decode)"
-    if not ex.w2_kmajor_now():
+    if _swiglu(ex):
+        why = _swiglu_unsupported(ex, dtype)
+        if why is not None:
+            return why
+    elif not ex.w2_kmajor_now():
         return "the packed dropless layout needs the k-major fc2 copy of inference (eval mode, no gradient)"
-    plan, why = packed_plan(T, E, k, M, ex.batched_fc1_w.size(1), ex.output_dim, dtype, capacity_limit, alignment)
+    plan, why = packed_plan(T, E, k, M, _hidden_size(ex), ex.output_dim, dtype, capacity_limit, alignment)
     return why if plan is None else None
 
 
@@ -794,7 +823,7 @@ class _PackedWorkspace:
     def __init__(self, layer, x, logits, k, T_cap, capacity_limit, alignment):
         ex = layer.experts
         E, dev, dt = logits.shape[1], x.device, x.dtype
-        M, H, Mo = x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim
+        M, H, Mo = x.shape[1], _hidden_size(ex), ex.output_dim
         self.T_cap = int(T_cap)
         plan, why = packed_plan(T_cap, E, k, M, H, Mo, dt, capacity_limit, alignment)
         if plan is None:
@@ -841,9 +870,10 @@ def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignmen
         return None
     import collections
     # (the limit is not part of the key: it follows T, and a workspace serves every call whose bound it holds)
-    key = ("packed", x.shape[1], x.dtype, x.device, E, logits.dtype, k, bool(layer.is_postscore), ex.fused_activation(), ops._stream(),
+    swiglu = _swiglu(ex)
+    key = ("packed_glu" if swiglu else "packed", x.shape[1], x.dtype, x.device, E, logits.dtype, k, bool(layer.is_postscore), ex.fused_activation(), ops._stream(),
            int(alignment))
-    plan = packed_plan(T, E, k, x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim, x.dtype, capacity_limit, alignment)[0]
+    plan = packed_plan(T, E, k, x.shape[1], _hidden_size(ex), ex.output_dim, x.dtype, capacity_limit, alignment)[0]
     need = plan["ws_bytes"]
     cache = layer.__dict__.get("_ep_workspaces")
     if not isinstance(cache, collections.OrderedDict):
@@ -865,7 +895,12 @@ def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignmen
     a = m.ep
     a.T = T
     m.capacity_limit = int(capacity_limit)
-    w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
+    if swiglu:   # k-major W_fc1 (gate), W_fc2 (up), W_fc3 (down); no biases
+        w1, w_up, w2 = ex.kmajor_weights()
+        b1 = b2 = None
+        kmajor = True
+    else:
+        w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
     dev = x.device
     y = torch.empty([T, ex.output_dim], dtype=x.dtype, device=dev)
     cnt = torch.empty([E], dtype=torch.int32, device=dev)
@@ -885,7 +920,10 @@ def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignmen
         m.logits, m.gate_w, m.logits_out = None, gate_w.data_ptr(), None
         m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
     m.dispatch_count, m.l_aux = cnt.data_ptr(), l_aux.data_ptr()
-    rc = _lib.lib().tutel_amd_moe_forward_packed(None, ctypes.byref(m), ctypes.byref(pk), ops._stream())
+    if swiglu:
+        rc = _lib.lib().tutel_amd_moe_forward_packed_glu(None, ctypes.byref(m), ctypes.byref(pk), w_up.data_ptr(), ops._stream())
+    else:
+        rc = _lib.lib().tutel_amd_moe_forward_packed(None, ctypes.byref(m), ctypes.byref(pk), ops._stream())
     if rc == _lib.ENOTSUP:
         return None
     _lib.check(rc, "tutel_amd_moe_forward_packed")

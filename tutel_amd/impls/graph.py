@@ -15,7 +15,8 @@ host bound, the capacity kept on the device), and only when asked for:
 
     graphed = GraphedForward(layer, example_input, capacity_factor=0.0, dropless_packed=True)
 
-Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes."""
+Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes.  Both expert types
+take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM)."""
 import torch
 
 

@@ -31,6 +31,7 @@ from .overlap import a2a_ffn_overlap_forward, a2a_ffn_overlap_fused
 from . import ep_native
 from .. import ops
 from ..experts.ffn import FusedExpertsNetwork
+from ..experts.llama_ffn import LlamaFFNNetwork
 from ..gates.top import LinearTopKGate
 
 
@@ -241,10 +242,13 @@ class MOELayer(torch.nn.Module):
     def _plan(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
               original_dtype, crit=None, allow_native=True):
         W = self.world_size
-        fusable = (x.is_cuda and len(reserve_shape) == 1 and isinstance(self.experts, FusedExpertsNetwork) and not C.SKIP_A2A
-                   and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
+        # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
+        # reason: ep_native.packed_unsupported, checked in _run_native_moe)
+        swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
+        fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or isinstance(self.experts, FusedExpertsNetwork))
+                   and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
                    and (x.dtype == logits.dtype or (logits.dtype == torch.float32 and x.dtype == original_dtype))
-                   and self.experts.can_fuse(x, self))
+                   and (swiglu_packed or self.experts.can_fuse(x, self)))
         if not fusable:
             return "generic"
         native = (allow_native and ep_native.ENABLED and not _FORCE_OVERLAP and degree <= 32 and (degree == 1 or not self.use_2dh)
@@ -319,6 +323,8 @@ class MOELayer(torch.nn.Module):
                 self.dispatch_count = cnt
                 self.dropless_capacity = cap
                 return y, l_aux
+            if isinstance(self.experts, LlamaFFNNetwork):
+                return None   # no padded one-call path for SwiGLU experts: the caller routes and runs the experts as before
         if cf <= 0:   # dropless: capacity = max expert load, read back inside the native call (fast_dispatch.py:191-199)
             guess = (k * spe * 3 // 2 + 31) // 32 * 32
             res = ep_native.forward_from_logits(self, xc, logits.contiguous(), k, guess, 1, self.normalize_gate, want_loss=True,

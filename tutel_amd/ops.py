@@ -318,6 +318,26 @@ def expert_gemm(a, w, bias, w_kmajor, act="none", E_loc=None, R=None, a_layout=N
     return out
 
 
+def expert_gemm_gate_up(a, w_gate, w_up, act="silu", row_counts=None, row_align=1):
+    """SwiGLU gate and up products in ONE launch: D[e,r,:] = act(A[e,r,:] @ Wg[e]^T) * (A[e,r,:] @ Wu[e]^T), the activation rounded
+    to the dtype before the product and the result rounded once -- the bits of expert_gemm(a, w_gate, None, True, act=act) followed by
+    expert_gemm(a, w_up, None, True, mul=<that>).  a [E, R, K]; w_gate, w_up k-major [E, N, K] -> [E, R, N].  Rows past
+    ceil(row_counts[e] / row_align) * row_align are left unwritten, as there.  act: relu, gelu or silu."""
+    _dev(a, w_gate, w_up, row_counts)
+    assert a.dim() == 3 and a.is_contiguous() and w_gate.dim() == 3 and w_gate.is_contiguous()
+    assert w_up.shape == w_gate.shape and w_up.is_contiguous() and w_gate.dtype == a.dtype and w_up.dtype == a.dtype
+    E, N, K = w_gate.shape
+    assert a.shape[0] == E and a.shape[2] == K
+    a = _a16(a)
+    R = a.shape[1]
+    out = torch.empty([E, R, N], dtype=a.dtype, device=a.device)
+    _lib.check(_lib.lib().tutel_amd_expert_gemm_gate_up(
+        _ptr(a), R * K, 0, R, K, _ptr(w_gate), _ptr(w_up), w_gate.stride(0), w_gate.stride(1),
+        _ptr(out), R * N, 0, R, N, E, R, N, K, _code(a), ACT_CODES[act],
+        _ptr(row_counts), int(row_align), _stream()), "tutel_amd_expert_gemm_gate_up")
+    return out
+
+
 _zero_rows = {}
 
 
