@@ -515,6 +515,50 @@ int tutel_amd_moe_forward_packed(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_
 int tutel_amd_moe_forward_packed_glu(tutel_amd_ep_comm_t *comm, const tutel_amd_moe_args_t *args,
                                      const tutel_amd_packed_args_t *packed, const void *w_up, tutel_stream_t stream);
 
+/* ---- training on the packed layout (single rank; the backward of tutel_amd_moe_forward_packed's ffn experts) -------------
+ * The launches of a packed training step, one by one, each over buffers the caller sized from tutel_amd_packed_plan.  Nothing
+ * here reads a routing-dependent size on the host: every extent per expert comes from the device offsets, so a whole training
+ * step can be captured in a HIP graph.  Packed rows past offsets[E] are never read; the pad rows of the backward operands
+ * (tutel_amd_fast_encode of the gradient through the packed slot map) are exact zeros.  Each entry point returns
+ * TUTEL_AMD_ENOTSUP (reason in tutel_amd_last_error) with nothing launched when it does not take the shape.
+ *
+ * tutel_amd_packed_layout: the layout launch of tutel_amd_moe_forward_packed alone.  From dispatch_count [E] and idx / loc [k, T]
+ * (tutel_amd_gate_topk + tutel_amd_compute_location) it writes offsets [E + 1], the tile table tiles [2 * tiles_bound], the live
+ * tile count ntiles [1], the device capacity [1] (max_e rows_e) and the packed slot map slot_map [rows_bound] (j*T + t of the
+ * entry in each kept row, -1 in pad rows and past offsets[E]).  rows_bound / tiles_bound at least the plan's. */
+int tutel_amd_packed_layout(const int32_t *dispatch_count, const int32_t *idx, const int32_t *loc, int T, int E, int k,
+                            int capacity_limit, int alignment, int rows_bound, int tiles_bound, int32_t *offsets, int32_t *tiles,
+                            int32_t *ntiles, int32_t *capacity, int32_t *slot_map, tutel_stream_t stream);
+/* tutel_amd_expert_gemm_packed: D[r, :] = act(A[r, :] @ op(W[e]) + bias[e, :]) [* mul[r, :]] for the packed rows r of expert e,
+ * rounded once.  A row r is A + r*lda, or, with a_rows (the packed slot map), token a_rows[r] % T of A (zero_row for -1).  W[e]
+ * at W + e*w_stride_e: w_kmajor = 1 [N][K] (the 256-row ping-pong kernel of the forward), 0 [K][N] as stored (the 128 x 128
+ * register-staged kernel, transposing LDS read; act none or relu, no mul).  mul: optional gating operand with D's layout
+ * (k-major only), e.g. the ReLU mask of the backward.  offsets / tiles / ntiles / capacity from tutel_amd_packed_layout. */
+int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W,
+                                 int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul,
+                                 void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
+                                 const int32_t *tiles, const int32_t *ntiles, const int32_t *capacity, int tiles_bound,
+                                 tutel_stream_t stream);
+/* tutel_amd_expert_wgrad_packed: the weight gradient D[e] = A[rows(e)]^T . B[rows(e)] -> [E, N_a, N_b] in dtype, rows(e) =
+ * [offsets[e], offsets[e+1]), fp32 accumulation in a fixed order (deterministic, no atomics), one rounding.  A [*, N_a] row r at
+ * A + r*lda, B [*, N_b] row r at B + r*ldb; gather = 1 (A) or 2 (B): that operand is the token array [T, *] read through
+ * rows_map (the packed slot map: token rows_map[r] % T, zero_row, >= 8 zeros, for -1); 0: none.  An expert with no rows gets
+ * zeros.  N_a, N_b, lda, ldb multiples of 8; 16-byte aligned operands. */
+int tutel_amd_expert_wgrad_packed(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                                  const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype,
+                                  const int32_t *offsets, tutel_stream_t stream);
+/* tutel_amd_expert_bgrad_packed: the bias gradient D[e, :] = sum over rows(e) of B [*, N] (fp32 in row order, rounded once). */
+int tutel_amd_expert_bgrad_packed(const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
+                                  tutel_stream_t stream);
+/* tutel_amd_gate_grad_packed: ggate[j*T + t] = <x[t], buf[offsets[e] + loc]> (fp32) for choice j of token t routed to expert e,
+ * 0 for an entry dropped by the row limit (loc >= row_limit; pass INT_MAX for none): tutel_amd_gate_grad on the packed rows. */
+int tutel_amd_gate_grad_packed(const void *x, const void *buf, int dtype, const int32_t *idx, const int32_t *loc, int T, int M,
+                               int k, int row_limit, const int32_t *offsets, float *ggate, tutel_stream_t stream);
+/* tutel_amd_fast_decode_packed: out[t] = sum_j g[j, t] * buf[offsets[idx] + loc] (gates NULL: g = 1), the decode of
+ * tutel_amd_moe_forward_packed; without gates it is the backward of the packed gather (dx from the packed dx rows). */
+int tutel_amd_fast_decode_packed(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype,
+                                 int T, int M, int k, int row_limit, const int32_t *offsets, void *out, tutel_stream_t stream);
+
 /* stage markers: roctx ranges (rocprofv3 --marker-trace); the pipeline above emits tutel_amd.fast_encode /
  * all_to_all / expert_fc1 / expert_fc2 / fast_decode itself.  No-ops when libroctx64 is not in the process
  * (set TUTEL_AMD_ROCTX=1 to load it).  The reference's only tracing is system.record_time (system.py:73-79). */

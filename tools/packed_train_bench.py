@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""One dropless training step at the configs[2] shape (T = 4096, M = H = 2048, E = 64, top-2, bf16, capacity_factor = 0):
+forward, loss = y.float().square().mean() + l_aux, backward.  Three variants, interleaved round-robin so that clock and thermal
+drift hit all of them alike: the padded eager step (dropless_packed off), the packed eager step, and the packed step replayed
+from a torch.cuda.graph capture.  Each step is timed with device events; the median over the steps is printed as one JSON line.
+
+    python tools/packed_train_bench.py [--steps 50] [--warmup 10]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--T", type=int, default=4096)
+    ap.add_argument("--dim", type=int, default=2048)
+    ap.add_argument("--E", type=int, default=64)
+    args = ap.parse_args()
+    from tutel import moe
+    T, M, E = args.T, args.dim, args.E
+    torch.manual_seed(0)
+    torch.set_default_dtype(torch.bfloat16)
+    layer = moe.moe_layer(gate_type={"type": "top", "k": 2, "capacity_factor": 0.0},
+                          experts={"type": "ffn", "num_experts_per_device": E, "hidden_size_per_expert": M,
+                                   "activation_fn": lambda t: torch.nn.functional.relu(t)}, model_dim=M)
+    torch.set_default_dtype(torch.float32)
+    layer = layer.cuda().train()
+    params = list(layer.parameters())
+    x = torch.randn(T, M, device="cuda", dtype=torch.bfloat16)
+
+    def step(packed):
+        layer.dropless_packed = packed
+        for p in params:
+            p.grad = None
+        y = layer(x)
+        loss = y.float().square().mean() + y.l_aux.float()
+        loss.backward()
+
+    # capture FIRST: warmed up on a side stream, before any eager step on the default stream -- an autograd graph kept alive by the
+    # layer's l_aux would otherwise hold AccumulateGrad nodes bound to the default stream into the capture (torch.cuda.graph docs)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            step(True)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    for p in params:
+        p.grad = None
+    with torch.cuda.graph(g):
+        step(True)
+    layer.l_aux = None
+    assert layer._dropless_packed_ran is True, layer._dropless_packed_ran
+    for _ in range(3):
+        step(False)
+        step(True)
+    variants = {"padded_eager": lambda: step(False), "packed_eager": lambda: step(True), "packed_graph": g.replay}
+    times = {n: [] for n in variants}
+    for i in range(args.warmup + args.steps):
+        for n, fn in variants.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= args.warmup:
+                times[n].append(a.elapsed_time(b))
+    print(json.dumps({"shape": {"T": T, "M": M, "H": M, "E": E, "k": 2, "dtype": "bf16"}, "steps": args.steps,
+                      "median_ms": {n: round(statistics.median(v), 4) for n, v in times.items()},
+                      "min_ms": {n: round(min(v), 4) for n, v in times.items()}}))
+
+
+if __name__ == "__main__":
+    main()

@@ -90,6 +90,12 @@ SIGNATURES.update({
     "tutel_amd_moe_packed_workspace_bytes": (_sz, [_i] * 9),
     "tutel_amd_moe_forward_packed": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp]),
     "tutel_amd_moe_forward_packed_glu": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp, _vp]),
+    "tutel_amd_packed_layout": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 6),
+    "tutel_amd_expert_gemm_packed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp] + [_i] * 7 + [_vp] * 4 + [_i, _vp]),
+    "tutel_amd_expert_wgrad_packed": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
+    "tutel_amd_expert_bgrad_packed": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "tutel_amd_gate_grad_packed": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp]),
+    "tutel_amd_fast_decode_packed": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp]),
     "tutel_amd_ep_load_rccl": (_i, [ctypes.c_char_p]),
     "tutel_amd_ep_unique_id": (_i, [_vp, _sz]),
     "tutel_amd_ep_comm_create": (_i, [_vp, _sz, _i, _i, ctypes.POINTER(_vp)]),

@@ -96,6 +96,12 @@ int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int 
                              int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
                              int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
                              hipStream_t st);
+// expert_gemm.hip: the same with the weight layout (w_kmajor 0: W[e] is [K][N], the register-staged kernel's transposing read) and an
+// optional gating operand `mul` with D's layout (D = act(A @ W + bias) * mul, the padded `mul=` form)
+int tutel_expert_gemm_packed_ex(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
+                                int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
+                                int rows_bound, int N, int K, int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles,
+                                const int32_t *cap, int tiles_bound, hipStream_t st);
 // expert_gemm.hip: the fused gate/up GEMM of a SwiGLU expert over the packed layout, D = round(act(A @ W_gate^T)) * (A @ W_up^T)
 // (tutel_amd_expert_gemm_gate_up's kernel); arguments as tutel_expert_gemm_packed, W_up with W_gate's strides, no bias
 int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,

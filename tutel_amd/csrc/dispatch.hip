@@ -343,7 +343,8 @@ __global__ __launch_bounds__(DP_THREADS) void gate_grad_kernel(const T *__restri
                                                               const int32_t *__restrict__ idx,
                                                               const int32_t *__restrict__ loc,
                                                               int Tn, int M, int k, int capacity,
-                                                              float *__restrict__ ggate) {
+                                                              float *__restrict__ ggate,
+                                                              const int32_t *__restrict__ pk_off = nullptr) {
   constexpr int VN = Vec<T>::N;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * DP_WAVES + (threadIdx.x >> 6);
@@ -356,7 +357,8 @@ __global__ __launch_bounds__(DP_THREADS) void gate_grad_kernel(const T *__restri
     int e = idx[q], l = loc[q];
     float acc = 0.f;
     if (l < capacity && e >= 0 && l >= 0) {
-      const T *row = buf + ((size_t)e * capacity + l) * M;
+      // (packed dropless layout: expert e's rows start at off[e], `capacity` is the row limit L)
+      const T *row = buf + (pk_off != nullptr ? (size_t)pk_off[e] + l : (size_t)e * capacity + l) * M;
       const T *xr = x + (size_t)t * M;
       if (vec_ok) {
         for (int i = lane; i < nvec; i += 64) {
@@ -582,3 +584,36 @@ extern "C" int tutel_amd_gate_grad(const void *x, const void *buf, int dtype, co
   return 0;
 }
 
+
+// ---- packed dropless layout (dropless.hip), the backward of its decode / gather -------------------------------------------------
+extern "C" int tutel_amd_gate_grad_packed(const void *x, const void *buf, int dtype, const int32_t *idx, const int32_t *loc, int T, int M,
+                                          int k, int row_limit, const int32_t *offsets, float *ggate, tutel_stream_t stream) {
+  TUTEL_REQUIRE(dtype == TUTEL_BF16 || dtype == TUTEL_F16, "tutel_amd_gate_grad_packed: dtype must be bf16 or fp16 (got %d)", dtype);
+  TUTEL_REQUIRE(T >= 0 && M >= 1 && k >= 1 && row_limit >= 1, "tutel_amd_gate_grad_packed: bad sizes T=%d M=%d k=%d limit=%d", T, M, k, row_limit);
+  if (T == 0) return 0;
+  TUTEL_REQUIRE(x && buf && idx && loc && offsets && ggate, "tutel_amd_gate_grad_packed: null pointer");
+  TUTEL_REQUIRE(((uintptr_t)buf % 16) == 0 && ((uintptr_t)x % 16) == 0, "tutel_amd_gate_grad_packed: x/buf must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  StageScope stage(TUTEL_STAGE_OTHER, st);
+  const int grid = dp_grid(k * T);
+  if (dtype == TUTEL_BF16)
+    hipLaunchKernelGGL(gate_grad_kernel<bf16_t>, dim3(grid), dim3(DP_THREADS), 0, st, (const bf16_t *)x, (const bf16_t *)buf, idx, loc, T, M, k,
+                       row_limit, ggate, offsets);
+  else
+    hipLaunchKernelGGL(gate_grad_kernel<f16_t>, dim3(grid), dim3(DP_THREADS), 0, st, (const f16_t *)x, (const f16_t *)buf, idx, loc, T, M, k,
+                       row_limit, ggate, offsets);
+  TUTEL_CHECK_LAUNCH("tutel_amd_gate_grad_packed");
+  return 0;
+}
+
+extern "C" int tutel_amd_fast_decode_packed(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype,
+                                            int T, int M, int k, int row_limit, const int32_t *offsets, void *out, tutel_stream_t stream) {
+  TUTEL_REQUIRE(dtype == TUTEL_BF16 || dtype == TUTEL_F16, "tutel_amd_fast_decode_packed: dtype must be bf16 or fp16 (got %d)", dtype);
+  if (k > 16) {
+    tutel_set_error("tutel_amd_fast_decode_packed: not covered: k <= 16");
+    return TUTEL_AMD_ENOTSUP;
+  }
+  TUTEL_REQUIRE(T >= 0 && M >= 1 && k >= 1 && row_limit >= 1 && (gates == nullptr || dtype_ok(gate_dtype)),
+                "tutel_amd_fast_decode_packed: bad arguments T=%d M=%d k=%d limit=%d", T, M, k, row_limit);
+  return tutel_decode_packed_launch(buf, dtype, idx, loc, gates, gate_dtype, T, M, k, row_limit, offsets, out, (hipStream_t)stream);
+}

@@ -161,6 +161,36 @@ extern "C" int tutel_amd_packed_plan(int T, int E, int k, int M, int H, int M_ou
   return 0;
 }
 
+// the layout launch (packed_layout_kernel) of tutel_amd_moe_forward_packed, over buffers the caller sized from tutel_amd_packed_plan
+static void launch_layout(const int32_t *cnt, const int32_t *idx, const int32_t *loc, int T, int E, int k, int L, int alignment, int rows_bound,
+                          int tiles_bound, int32_t *off, int32_t *tiles, int32_t *ntiles, int32_t *cap, int32_t *slot, hipStream_t st) {
+  const long long work = (long long)k * T > rows_bound ? (long long)k * T : rows_bound;
+  long long grid = (work + 4 * LY_THREADS - 1) / (4 * LY_THREADS);
+  grid = grid < 1 ? 1 : (grid > 256 ? 256 : grid);
+  hipLaunchKernelGGL(packed_layout_kernel, dim3((unsigned)grid), dim3(LY_THREADS), 0, st, cnt, idx, loc, k * T, E, L, alignment, rows_bound,
+                     tiles_bound, off, tiles, ntiles, cap, slot);
+}
+
+extern "C" int tutel_amd_packed_layout(const int32_t *dispatch_count, const int32_t *idx, const int32_t *loc, int T, int E, int k,
+                                       int capacity_limit, int alignment, int rows_bound, int tiles_bound, int32_t *offsets, int32_t *tiles,
+                                       int32_t *ntiles, int32_t *capacity, int32_t *slot_map, tutel_stream_t stream) {
+  TUTEL_REQUIRE(T >= 1 && E >= 1 && k >= 1 && capacity_limit >= 0 && alignment >= 1, "tutel_amd_packed_layout: bad sizes T=%d E=%d k=%d limit=%d alignment=%d",
+                T, E, k, capacity_limit, alignment);
+  tutel_amd_packed_plan_t pl;
+  // (M, H, M_out = 128 and bf16: the bounds depend on (T, E, k, limit, alignment) alone)
+  const int rc = tutel_amd_packed_plan(T, E, k, 128, 128, 128, TUTEL_BF16, capacity_limit, alignment, &pl);
+  if (rc) return rc;
+  TUTEL_REQUIRE(rows_bound >= pl.rows_bound && tiles_bound >= pl.tiles_bound, "tutel_amd_packed_layout: buffers below the plan's bounds (rows %d < %d or tiles %d < %d)",
+                rows_bound, pl.rows_bound, tiles_bound, pl.tiles_bound);
+  TUTEL_REQUIRE(dispatch_count && idx && loc && offsets && tiles && ntiles && capacity && slot_map, "tutel_amd_packed_layout: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  StageScope sc(TUTEL_STAGE_OTHER, st);
+  launch_layout(dispatch_count, idx, loc, T, E, k, pl.row_limit > 0 ? pl.row_limit : INT_MAX, alignment, rows_bound, tiles_bound, offsets, tiles,
+                ntiles, capacity, slot_map, st);
+  TUTEL_CHECK_LAUNCH("tutel_amd_packed_layout");
+  return 0;
+}
+
 extern "C" size_t tutel_amd_moe_packed_workspace_bytes(int T, int E, int k, int M, int H, int M_out, int dtype, int capacity_limit,
                                                        int alignment) {
   tutel_amd_packed_plan_t pl;

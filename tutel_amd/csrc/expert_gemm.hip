@@ -39,7 +39,10 @@
 
 // Register-staged 128 x 128 kernel: K-tile depth 64, double-buffered LDS (one barrier per K-tile), 2 blocks per CU.
 // NT = non-temporal weight loads, ROT = K-tile rotation when the problem asks for it.
-template <typename T, bool W_KMAJOR, int ACT, bool NT, bool ROT>
+// PACKED (its own instantiation): the packed dropless layout's tile table drives the grid (tutel_expert_gemm_packed_ex, n-major
+// weights): M-tile 2i + h of the launch is rows [pk_tiles[2i+1] + 128 h, +128) of expert pk_tiles[2i]; rows past the expert's
+// last row off[e+1] read that last row instead (never stored), so no row past off[E] is read.
+template <typename T, bool W_KMAJOR, int ACT, bool NT, bool ROT, bool PACKED = false>
 __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) {
   constexpr int BK = 64, NBUF = 2;
   constexpr int LDK = BK + 8;                                       // padded [rows][k] LDS row (elements)
@@ -58,23 +61,38 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) 
 
   // ---- XCD-aware work order: consecutive work items (same expert, neighbouring tiles) go to
   // the same XCD (hardware places block b on XCD b % 8; speed only, never correctness).
-  const int nb = gridDim.x;
+  int nb = gridDim.x;
+  if (PACKED) {
+    nb = min(nb, __builtin_amdgcn_readfirstlane(*p.pk_ntiles) * 2 * p.ntn);
+    if ((int)blockIdx.x >= nb) return;
+  }
   int w;
   {
     const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
     w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
   }
-  const int mt = w % p.ntm;
-  const int nt = (w / p.ntm) % p.ntn;
-  const int e = w / (p.ntm * p.ntn);
-  const int m0 = mt * GM_BM, n0 = nt * GM_BN;
-
-  int row_limit = p.R;
-  if (p.row_counts != nullptr) {
-    int c = p.row_counts[e];
-    c = (c + p.row_align - 1) / p.row_align * p.row_align;
-    row_limit = min(row_limit, c);
+  int nt, e, m0, row_limit;
+  bool rot_on = p.rot_on;
+  if (PACKED) {
+    const int h = w / p.ntn, ti = h >> 1;
+    nt = w % p.ntn;
+    e = __builtin_amdgcn_readfirstlane(p.pk_tiles[2 * ti]);
+    m0 = __builtin_amdgcn_readfirstlane(p.pk_tiles[2 * ti + 1]) + (h & 1) * GM_BM;
+    row_limit = __builtin_amdgcn_readfirstlane(p.pk_off[e + 1]);
+    rot_on = __builtin_amdgcn_readfirstlane(*p.pk_cap) < GB_BM;
+  } else {
+    const int mt = w % p.ntm;
+    nt = (w / p.ntm) % p.ntn;
+    e = w / (p.ntm * p.ntn);
+    m0 = mt * GM_BM;
+    row_limit = p.R;
+    if (p.row_counts != nullptr) {
+      int c = p.row_counts[e];
+      c = (c + p.row_align - 1) / p.row_align * p.row_align;
+      row_limit = min(row_limit, c);
+    }
   }
+  const int n0 = nt * GM_BN;
   if (m0 >= row_limit) return;
 
   const uint16_t *Ae = reinterpret_cast<const uint16_t *>(p.A) + (size_t)e * p.a_stride_e;
@@ -89,10 +107,10 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) 
 #pragma unroll
     for (int i = 0; i < NLA; ++i) {
       int r = rbase + RPP * i;
-      int gr = min(m0 + r, p.R - 1);
+      int gr = min(m0 + r, (PACKED ? row_limit : p.R) - 1);
       a_src[i] = Ae + (size_t)(gr / p.a_rpw) * p.a_stride_w + (size_t)(gr % p.a_rpw) * p.lda + kc * 8;
       if (p.a_rows != nullptr) {  // fused fast_encode: bucket row -> token row of x (or the zero row)
-        const int q = p.a_rows[(size_t)e * p.R + gr];
+        const int q = p.a_rows[(size_t)(PACKED ? 0 : e) * p.R + gr];
         a_src[i] = (q >= 0 ? reinterpret_cast<const uint16_t *>(p.A) + (size_t)(q % p.a_rows_mod) * p.lda
                            : reinterpret_cast<const uint16_t *>(p.a_zero)) + kc * 8;
       }
@@ -144,7 +162,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) 
   // K-tile rotation per PAIR of N-tiles: the 256-column kernel below shares one token tile between the
   // pair and therefore one k order; using the same order here makes every kernel produce bit-identical
   // sums for a given output element, whatever tile size the row count selects
-  const int rot = (ROT && p.rot_on) ? (int)(((long long)((nt >> 1) + 3 * e) * nk / ((p.ntn + 1) >> 1)) % nk) : 0;
+  const int rot = (ROT && rot_on) ? (int)(((long long)((nt >> 1) + 3 * e) * nk / ((p.ntn + 1) >> 1)) % nk) : 0;
 
   // Prefetch registers: straight-line unrolled code over fixed-size arrays (no lambdas, no
   // conditionals around the loads -- hipcc otherwise demotes them to scratch / waits vmcnt(0)).
@@ -1254,12 +1272,37 @@ int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int 
                              int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
                              int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
                              hipStream_t st) {
+  return tutel_expert_gemm_packed_ex(A, lda, a_rows, T, zero_row, W, 1, w_stride_e, ldw, bias, bias_stride_e, nullptr, D, ldd, E, rows_bound, N,
+                                     K, dtype, act, off, tiles, ntiles, cap, tiles_bound, st);
+}
+
+// n-major weights over the packed layout: the register-staged 128 x 128 kernel (its transposing LDS read takes W [K][N] as stored),
+// two 128-row M-tiles per entry of the 256-row tile table, grid sized by the host's tile bound
+template <typename T, int ACT>
+static int launch_packed_nmajor(const GemmArgs &a, int tiles_bound, hipStream_t st) {
+  GemmArgs b = a;
+  b.ntm = 1;
+  b.ntn = (a.N + GM_BN - 1) / GM_BN;
+  const long long grid = (long long)tiles_bound * 2 * b.ntn;
+  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_packed: grid too large");
+  const size_t lds = gemm_lds_bytes(false);
+  auto kern = expert_gemm_kernel<T, false, ACT, true, true, true>;
+  if (lds > 65536 && !tutel_lds_optin((const void *)kern, lds)) return -1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GM_THREADS), lds, st, b);
+  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_packed");
+  return 0;
+}
+
+int tutel_expert_gemm_packed_ex(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
+                                int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
+                                int rows_bound, int N, int K, int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles,
+                                const int32_t *cap, int tiles_bound, hipStream_t st) {
   TUTEL_REQUIRE(off && tiles && ntiles && cap && tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1),
                 "tutel_expert_gemm_packed: bad arguments");
   GemmArgs a;
-  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W, 1, w_stride_e, ldw, bias, bias_stride_e, D, 0, 0, rows_bound, ldd, E, rows_bound,
-                                  N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, nullptr, nullptr, 0, nullptr, nullptr,
-                                  0, nullptr, &a);
+  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, D, 0, 0, rows_bound, ldd, E,
+                                  rows_bound, N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, mul, nullptr, 0, nullptr,
+                                  nullptr, 0, nullptr, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   if (!a.fits32) {
     tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
@@ -1268,6 +1311,13 @@ int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int 
   a.pk_off = off; a.pk_tiles = tiles; a.pk_ntiles = ntiles; a.pk_cap = cap;
   StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
   const bool bf = dtype == TUTEL_BF16;
+  if (!w_kmajor) {
+    switch (act) {
+      case TUTEL_ACT_NONE: return bf ? launch_packed_nmajor<bf16_t, TUTEL_ACT_NONE>(a, tiles_bound, st) : launch_packed_nmajor<f16_t, TUTEL_ACT_NONE>(a, tiles_bound, st);
+      case TUTEL_ACT_RELU: return bf ? launch_packed_nmajor<bf16_t, TUTEL_ACT_RELU>(a, tiles_bound, st) : launch_packed_nmajor<f16_t, TUTEL_ACT_RELU>(a, tiles_bound, st);
+      default: tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP;
+    }
+  }
   switch (act) {
     case TUTEL_ACT_NONE: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_NONE>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_NONE>(a, tiles_bound, st);
     case TUTEL_ACT_RELU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_RELU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_RELU>(a, tiles_bound, st);

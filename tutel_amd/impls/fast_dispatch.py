@@ -179,6 +179,17 @@ def _topk_aten(work, k, apply_softmax, normalize_gate):
     return top.t().contiguous().to(torch.int32), torch.stack(gl).contiguous(), sc
 
 
+def gates_from_scores(sc, idx2d, normalize_gate):
+    """the k differentiable gate vectors [T] of the chosen experts idx2d [k, T] (ATen ops: autograd reaches the scores sc [T, E]),
+    normalised to sum 1 per token when normalize_gate and k > 1 (fast_dispatch.py:173-175 of the reference)"""
+    k = idx2d.shape[0]
+    gate_list = [sc.gather(1, idx2d[j].long().unsqueeze(-1)).squeeze(-1) for j in range(k)]
+    if k > 1 and normalize_gate:
+        denom = torch.clamp(sum(gate_list), min=torch.finfo(gate_list[0].dtype).eps)
+        gate_list = [g / denom for g in gate_list]
+    return gate_list
+
+
 def extract_critical(scores, top_k, loss_fn=losses.gshard_loss, capacity_factor=1.0,
                      batch_prioritized_routing=False, normalize_gate=True, alignment=1, group=None,
                      inequivalent_tokens=False, _logits=None):
@@ -278,10 +289,7 @@ def extract_critical(scores, top_k, loss_fn=losses.gshard_loss, capacity_factor=
         sc = scores if scores is not None else torch.softmax(_logits, dim=1)
         if not needs_grad:
             sc = sc.detach()
-        gate_list = [sc.gather(1, idx2d[j].long().unsqueeze(-1)).squeeze(-1) for j in range(k)]
-        if k > 1 and normalize_gate:
-            denom = torch.clamp(sum(gate_list), min=torch.finfo(gate_list[0].dtype).eps)
-            gate_list = [g / denom for g in gate_list]
+        gate_list = gates_from_scores(sc, idx2d, normalize_gate)
     elif gates2d.dtype != src.dtype:
         gates2d = gates2d.to(src.dtype)
 

@@ -16,7 +16,22 @@ host bound, the capacity kept on the device), and only when asked for:
     graphed = GraphedForward(layer, example_input, capacity_factor=0.0, dropless_packed=True)
 
 Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes.  Both expert types
-take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM)."""
+take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM).
+
+GraphedForward is forward-only.  A dropless TRAINING step of `ffn` experts (ReLU, bf16 / fp16) on the packed layout
+(`layer.dropless_packed = True`, impls/packed_train.py) needs no host synchronisation in its forward or backward either, so
+forward + backward are captured with plain torch.cuda.graph.  Warm up on a side stream BEFORE any eager step on the default
+stream (the layer keeps `l_aux`, whose autograd graph would hold gradient-accumulation nodes of the default stream):
+
+    s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            step()                                 # zero grads (set to None), y = layer(static_x), loss.backward()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        step()
+    static_x.copy_(x); g.replay()                  # the parameters' .grad hold this batch's gradients"""
 import torch
 
 

@@ -29,6 +29,7 @@ from . import losses
 from .fast_dispatch import RoutingPlan, extract_critical, fast_decode, fast_encode, get_dispatch_count
 from .overlap import a2a_ffn_overlap_forward, a2a_ffn_overlap_fused
 from . import ep_native
+from . import packed_train
 from .. import ops
 from ..experts.ffn import FusedExpertsNetwork
 from ..experts.llama_ffn import LlamaFFNNetwork
@@ -445,6 +446,17 @@ class MOELayer(torch.nn.Module):
             res = self._run_native_moe(x, logits, top_k, cf, degree, alignment, megablocks_size)
             if res is not None:
                 return finish(*res)
+
+        # dropless training on the packed layout (impls/packed_train.py): forward + backward without a host synchronisation
+        if cf <= 0 and self.dropless_packed and packed_train.autograd_live(self, x):
+            why = packed_train.unsupported(self, gate, x.shape[0], logits.shape[-1], min(top_k, logits.shape[-1]), x.shape[1], x.dtype, cf,
+                                           alignment, reserve_dims=len(reserve_shape), on_device=x.is_cuda and logits.dim() == 2)
+            self._dropless_packed_ran = True if why is None else why
+            if why is None:
+                with torch.autocast("cuda", enabled=False):
+                    y, l_aux = packed_train.forward(self, gate, x, logits, min(top_k, logits.shape[-1]), cf, alignment)
+                self.megablocks_size = megablocks_size
+                return finish(y, l_aux)
 
         def routing():
             noisy = logits

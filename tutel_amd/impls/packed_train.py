@@ -1,0 +1,158 @@
+"""A dropless training step of ffn experts on the packed layout: forward AND backward without a host synchronisation.
+
+The padded dropless step (MOELayer's generic path) reads the maximum expert load back to the host to shape [E, C, *] buckets
+(extract_critical), and its weight gradients are library batched GEMMs over those buckets.  Here the experts' rows lie back to
+back (csrc/dropless.hip), every buffer is sized by the host bound of tutel_amd_packed_plan, and every per-expert extent comes
+from the device offsets -- so the whole step, loss.backward() included, can be captured with torch.cuda.graph.
+
+    routing   : top-k + locations (the HIP kernels extract_critical runs) on logits.detach(); the differentiable gates and
+                l_aux from the same ATen ops as extract_critical's training branch (fast_dispatch.gates_from_scores)
+    layout    : ops.packed_layout -> offsets, tile table, packed slot map, device capacity
+    forward   : hid = relu(x[slot] @ W1^T + b1)   (ops.expert_gemm_packed, k-major, rows gathered from the tokens)
+                Y   = hid @ W2 + b2               (n-major: W2 [E, H, M_out] as stored)
+                y   = sum_j g[j, t] * Y[off[e] + loc]
+    backward  : dY   = g * dy scattered to the packed rows (ops.fast_encode through the packed slot map: pad rows are zeros)
+                dg   = <dy[t], Y[off[e] + loc]>                       (ops.gate_grad_packed)
+                dW2  = hid^T dY, db2 = sum dY                       (ops.expert_wgrad_packed / expert_bgrad_packed)
+                dhid = (dY @ W2^T) * [hid > 0]                        (k-major, gated epilogue)
+                dW1  = dhid^T x[slot], db1 = sum dhid
+                dx   = sum_j (dhid @ W1)[off[e] + loc]                (n-major GEMM, then the packed decode without gates)
+"""
+import torch
+
+from . import ep_native, losses
+from .fast_dispatch import gates_from_scores
+from .. import ops
+from ..gates.top import LinearTopKGate
+
+
+def _experts_kind(ex):
+    from ..experts.ffn import FusedExpertsNetwork
+    from ..experts.llama_ffn import LlamaFFNNetwork
+    if isinstance(ex, LlamaFFNNetwork):
+        return "swiglu"
+    if isinstance(ex, FusedExpertsNetwork):
+        return "ffn"
+    return None
+
+
+def autograd_live(layer, x):
+    """grad enabled, and the input or an expert parameter requires grad"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in layer.experts.parameters()))
+
+
+def unsupported(layer, gate, T, E, k, M, dtype, cf, alignment, reserve_dims=1, on_device=True):
+    """why this layer's dropless training step cannot take the packed layout (None: it can): T tokens of M features in `dtype`
+    (as MOELayer.forward hands them to the experts), E experts, top-k, capacity factor cf; host arithmetic only."""
+    ex = layer.experts
+    kind = _experts_kind(ex)
+    if kind == "swiglu":
+        return ep_native._swiglu_unsupported(ex, dtype) or "the packed training step covers ffn experts only (not SwiGLU)"
+    if kind is None:
+        return "the packed training step covers ffn experts (FusedExpertsNetwork) only"
+    if cf > 0:
+        return "the packed training step is dropless only (capacity_factor <= 0)"
+    if layer.world_size != 1:
+        return "the packed training step runs on a single rank only"
+    if not layer.is_postscore:
+        return "the packed training step needs is_postscore=True (gates applied in the decode)"
+    if type(gate) is not LinearTopKGate or gate.gate_noise > 0:
+        return "the packed training step needs a LinearTopKGate without gate noise"
+    if layer.batch_prioritized_routing:
+        return "the packed training step does not cover batch-prioritised routing"
+    if not layer.is_gshard_loss:
+        return "the packed training step needs the gshard loss"
+    if ex.skip_expert or ex.sharded_count > 1 or layer.adaptive_degree != 1 or reserve_dims != 1:
+        return "the packed training step needs unsharded local experts (sharded_count = 1, adaptive_r = 1, reserve_dims = 1)"
+    w1 = ex.batched_fc1_w
+    if torch.is_autocast_enabled() and w1.dtype == torch.float32:
+        return "the packed training step does not cover autocast over fp32 master weights"
+    if w1.dtype not in (torch.bfloat16, torch.float16) or dtype != w1.dtype:
+        return "the packed training step needs bf16 / fp16 experts and tokens in their dtype"
+    if ex.fused_activation() != "relu":
+        return "the packed training step needs the ReLU activation"
+    if not on_device or T == 0:
+        return "the packed training step needs a non-empty batch on the HIP device"
+    if ex.output_dim % 64 != 0:
+        return "the packed training step needs M_out a multiple of 64 (the backward contracts over it)"
+    limit = k * int(-cf * ((T + E - 1) // E)) if cf < 0 else 0
+    plan, why = ep_native.packed_plan(T, E, k, M, w1.size(1), ex.output_dim, dtype, limit, alignment)
+    return why if plan is None else None
+
+
+class _PackedFFNTrain(torch.autograd.Function):
+    """y from (x, gates) over one packed layout; see the module docstring for the launches"""
+
+    @staticmethod
+    def forward(ctx, x, gates2d, w1, b1, w2, b2, lay, idx, loc, zero_row):
+        hid = ops.expert_gemm_packed(x, w1, b1, True, lay, act="relu", gather=True, zero_row=zero_row)
+        yp = ops.expert_gemm_packed(hid, w2, b2, False, lay)
+        y = ops.fast_decode_packed(yp, idx, loc, gates2d, lay)
+        ctx.save_for_backward(x, gates2d, w1, w2, hid, yp)
+        ctx.lay, ctx.idx, ctx.loc, ctx.zero_row = lay, idx, loc, zero_row
+        ctx.has_bias = (b1 is not None, b2 is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gates2d, w1, w2, hid, yp = ctx.saved_tensors
+        lay, idx, loc = ctx.lay, ctx.idx, ctx.loc
+        gy = gy.contiguous()
+        need_x, need_g, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:6]
+        gx = gg = gw1 = gb1 = gw2 = gb2 = None
+        if need_g:
+            gg = ops.gate_grad_packed(gy, yp, idx, loc, lay).to(gates2d.dtype)
+        dyp = ops.fast_encode(gy, lay.slot_map, gates2d.detach(), lay.rows_bound)
+        if need_w2:
+            gw2 = ops.expert_wgrad_packed(hid, dyp, lay)
+        if need_b2 and ctx.has_bias[1]:
+            gb2 = ops.expert_bgrad_packed(dyp, lay)
+        if need_x or need_w1 or (need_b1 and ctx.has_bias[0]):
+            dhid = ops.expert_gemm_packed(dyp, w2, None, True, lay, mul=(hid > 0).to(hid.dtype))
+            if need_w1:
+                gw1 = ops.expert_wgrad_packed(dhid, x, lay, gather="b", zero_row=ctx.zero_row)
+            if need_b1 and ctx.has_bias[0]:
+                gb1 = ops.expert_bgrad_packed(dhid, lay)
+            if need_x:
+                gx = ops.fast_decode_packed(ops.expert_gemm_packed(dhid, w1, None, False, lay), idx, loc, None, lay)
+        return gx, gg, gw1, gb1, gw2, gb2, None, None, None, None
+
+
+
+def forward(layer, gate, x, logits, k, cf, alignment):
+    """One dropless training forward of `layer` on the packed layout: x [T, M], logits [T, E] (with autograd) -> (y [T, M_out], l_aux).
+    Sets dispatch_count, dropless_capacity (device int32 [1]), dropless_offsets and protected_shape as the packed forward does."""
+    ex = layer.experts
+    T, E = logits.shape
+    M, H, Mo = x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim
+    limit = k * int(-cf * ((T + E - 1) // E)) if cf < 0 else 0
+    plan, why = ep_native.packed_plan(T, E, k, M, H, Mo, x.dtype, limit, alignment)
+    if plan is None:
+        raise RuntimeError(why)
+    # routing: the kernels extract_critical runs (same idx / loc / counts), on the detached logits
+    work = logits if ops.routing_dtype(logits.dtype) else logits.float()
+    l_dt = logits.dtype if ops.supported_dtype(logits.dtype) else torch.float32
+    if torch.is_grad_enabled() and logits.requires_grad:
+        idx2d, _, ws, _ = ops.gate_topk(work.detach(), k, apply_softmax=True, normalize_gate=layer.normalize_gate, want_scores=True)
+        loc2d, cnt, _, _, _ = ops.compute_location(idx2d, E, ws=ws, capacity=0, want_l_aux=False, l_aux_dtype=l_dt)
+        # the differentiable gates and the loss: extract_critical's training branch, op for op
+        gates2d = torch.stack(gates_from_scores(torch.softmax(logits, dim=1), idx2d, layer.normalize_gate))
+        l_aux = losses.gshard_loss(torch.softmax(logits, dim=1), idx2d.t().long())
+    else:
+        # a frozen router: the kernel gates and the fused gshard loss, as extract_critical takes them then
+        idx2d, gk, ws, _ = ops.gate_topk(work.detach(), k, apply_softmax=True, normalize_gate=layer.normalize_gate)
+        loc2d, cnt, _, lk, _ = ops.compute_location(idx2d, E, ws=ws, capacity=0, want_l_aux=True, l_aux_dtype=l_dt)
+        gates2d = gk if gk.dtype == logits.dtype else gk.to(logits.dtype)
+        l_aux = lk[0] if lk.dtype == logits.dtype else lk[0].to(logits.dtype)
+    lay = ops.packed_layout(cnt, idx2d, loc2d, limit, alignment, plan["rows_bound"], plan["tiles_bound"], plan["row_limit"])
+    zero_row = torch.zeros([max(M, 8)], dtype=x.dtype, device=x.device)
+    xc = x if x.is_contiguous() else x.contiguous()
+    y = _PackedFFNTrain.apply(xc, gates2d, ex.batched_fc1_w, ex.batched_fc1_bias, ex.batched_fc2_w, ex.batched_fc2_bias, lay, idx2d,
+                              loc2d, zero_row)
+    layer.dispatch_count = cnt
+    layer.dropless_capacity = lay.capacity
+    layer.dropless_offsets = lay.offsets
+    layer.protected_shape = torch.Size([layer.num_local_experts, plan["rows_bound"], Mo])
+    if getattr(layer, "_keep_routing", False):
+        layer.last_routing = (idx2d.clone(), loc2d.clone())
+    return y, l_aux

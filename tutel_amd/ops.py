@@ -403,6 +403,117 @@ _OPT_ENV = {_lib.OPT_GEMM_IMPL: "TUTEL_AMD_GEMM_IMPL", _lib.OPT_GEMM_TILE: "TUTE
 _opts = {}
 
 
+# ---------------------------------------------------------------------------------------------
+# packed dropless layout: the launches of a training step (include/tutel_amd.h, "training on the packed layout")
+# ---------------------------------------------------------------------------------------------
+class PackedLayout:
+    """Device tables of one packed layout (tutel_amd_packed_layout), sized by the host bounds: offsets [E + 1], tiles [2 * tiles_bound],
+    ntiles [1], capacity [1] (max rows of an expert), slot_map [rows_bound]; row_limit = L (0: none)."""
+
+    def __init__(self, E, rows_bound, tiles_bound, row_limit, device):
+        self.E, self.rows_bound, self.tiles_bound, self.row_limit = int(E), int(rows_bound), int(tiles_bound), int(row_limit)
+        self.offsets = torch.empty([E + 1], dtype=torch.int32, device=device)
+        self.tiles = torch.empty([2 * max(tiles_bound, 1)], dtype=torch.int32, device=device)
+        self.ntiles = torch.empty([1], dtype=torch.int32, device=device)
+        self.capacity = torch.empty([1], dtype=torch.int32, device=device)
+        self.slot_map = torch.empty([max(rows_bound, 1)], dtype=torch.int32, device=device)
+
+    @property
+    def decode_limit(self):
+        """the row limit the packed decode / gate gradient take (none: INT_MAX)"""
+        return self.row_limit if self.row_limit > 0 else 0x7fffffff
+
+
+def packed_layout(dispatch_count, idx, loc, capacity_limit, alignment, rows_bound, tiles_bound, row_limit, out=None):
+    """tutel_amd_packed_layout: dispatch_count [E], idx / loc [k, T] int32 -> PackedLayout (written into `out` when given)."""
+    _dev(dispatch_count, idx, loc)
+    k, T = idx.shape
+    E = dispatch_count.numel()
+    lay = out if out is not None else PackedLayout(E, rows_bound, tiles_bound, row_limit, idx.device)
+    _lib.check(_lib.lib().tutel_amd_packed_layout(_ptr(dispatch_count), _ptr(idx), _ptr(loc), T, E, k, int(capacity_limit), int(alignment),
+                                                  lay.rows_bound, lay.tiles_bound, _ptr(lay.offsets), _ptr(lay.tiles), _ptr(lay.ntiles),
+                                                  _ptr(lay.capacity), _ptr(lay.slot_map), _stream()), "tutel_amd_packed_layout")
+    return lay
+
+
+def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, zero_row=None, mul=None):
+    """Packed rows: D[r] = act(A[r] @ op(W[e]) + bias[e]) [* mul[r]] for the rows r of expert e -> [rows_bound, N].
+    a [rows_bound, K], or with gather=True the token array [T, K] read through layout.slot_map (zero_row for pad rows);
+    w [E, N, K] (w_kmajor) or [E, K, N] as stored.  Rows past layout.offsets[E] are left unwritten."""
+    _dev(a, w, bias, mul)
+    assert a.dim() == 2 and a.is_contiguous() and w.dim() == 3 and w.is_contiguous() and w.dtype == a.dtype
+    E, N, K = (w.shape[0], w.shape[1], w.shape[2]) if w_kmajor else (w.shape[0], w.shape[2], w.shape[1])
+    assert a.shape[1] == K and E == layout.E
+    if bias is not None:
+        assert bias.is_contiguous() and bias.shape[-1] == N and bias.dtype == a.dtype
+    if mul is not None:
+        assert mul.shape == (layout.rows_bound, N) and mul.is_contiguous() and mul.dtype == a.dtype
+    a = _a16(a)
+    out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
+    _lib.check(_lib.lib().tutel_amd_expert_gemm_packed(
+        _ptr(a), K, _ptr(layout.slot_map) if gather else None, a.shape[0] if gather else 0, _ptr(zero_row) if gather else None,
+        _ptr(w), int(bool(w_kmajor)), w.stride(0), w.stride(1), _ptr(bias), (bias.stride(0) if bias is not None else 0), _ptr(mul),
+        _ptr(out), N, E, layout.rows_bound, N, K, _code(a), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles),
+        _ptr(layout.capacity), layout.tiles_bound, _stream()), "tutel_amd_expert_gemm_packed")
+    return out
+
+
+def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None):
+    """Weight gradient over the packed rows: D[e] = A[rows(e)]^T @ B[rows(e)] -> [E, N_a, N_b], fp32 sums in a fixed order.
+    a [rows_bound, N_a], b [rows_bound, N_b]; gather="a" or "b": that operand is the token array [T, *] read through
+    layout.slot_map (zero_row, >= 8 zeros, for pad rows)."""
+    _dev(a, b)
+    assert a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype
+    assert gather in (None, "a", "b")
+    a, b = _a16(a), _a16(b)
+    Na, Nb = a.shape[1], b.shape[1]
+    g = {None: 0, "a": 1, "b": 2}[gather]
+    T = (a if gather == "a" else b).shape[0] if gather else 0
+    out = torch.empty([layout.E, Na, Nb], dtype=a.dtype, device=a.device)
+    _lib.check(_lib.lib().tutel_amd_expert_wgrad_packed(
+        _ptr(a), Na, _ptr(b), Nb, _ptr(layout.slot_map) if g else None, g, T, _ptr(zero_row) if g else None,
+        _ptr(out), layout.E, layout.rows_bound, Na, Nb, _code(a), _ptr(layout.offsets), _stream()), "tutel_amd_expert_wgrad_packed")
+    return out
+
+
+def expert_bgrad_packed(b, layout):
+    """Bias gradient over the packed rows: D[e] = sum of b[rows(e)] -> [E, N]."""
+    _dev(b)
+    assert b.dim() == 2 and b.is_contiguous()
+    out = torch.empty([layout.E, b.shape[1]], dtype=b.dtype, device=b.device)
+    _lib.check(_lib.lib().tutel_amd_expert_bgrad_packed(_ptr(b), b.shape[1], _ptr(out), layout.E, b.shape[1], _code(b), _ptr(layout.offsets),
+                                                        _stream()), "tutel_amd_expert_bgrad_packed")
+    return out
+
+
+def gate_grad_packed(x, buf, idx, loc, layout):
+    """ggate [k, T] fp32 = <x[t], buf[off[e] + loc]> (0 for an entry dropped by the row limit)."""
+    _dev(x, buf, idx, loc)
+    assert x.is_contiguous() and buf.is_contiguous() and x.dtype == buf.dtype
+    x, buf = _a16(x), _a16(buf)
+    k, T = idx.shape
+    out = torch.empty([k, T], dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().tutel_amd_gate_grad_packed(_ptr(x), _ptr(buf), _code(x), _ptr(idx), _ptr(loc), T, x.shape[1], k, layout.decode_limit,
+                                                     _ptr(layout.offsets), _ptr(out), _stream()), "tutel_amd_gate_grad_packed")
+    return out
+
+
+def fast_decode_packed(buf, idx, loc, gates, layout):
+    """out[t] = sum_j g[j, t] * buf[off[idx] + loc] (gates None: 1) -> [T, M]."""
+    _dev(buf, idx, loc, gates)
+    assert buf.is_contiguous()
+    buf = _a16(buf)
+    k, T = idx.shape
+    M = buf.shape[1]
+    out = torch.empty([T, M], dtype=buf.dtype, device=buf.device)
+    if gates is not None:
+        assert gates.is_contiguous() and gates.shape == (k, T)
+    _lib.check(_lib.lib().tutel_amd_fast_decode_packed(_ptr(buf), _code(buf), _ptr(idx), _ptr(loc), _ptr(gates),
+                                                       _code(gates) if gates is not None else 0, T, M, k, layout.decode_limit,
+                                                       _ptr(layout.offsets), _ptr(out), _stream()), "tutel_amd_fast_decode_packed")
+    return out
+
+
 def set_option(key, value):
     """Tuning knob (_lib.OPT_*): -1 automatic, 0 / 1 forced.  For A/B runs and tests."""
     _lib.check(_lib.lib().tutel_amd_set_option(int(key), int(value)), "tutel_amd_set_option")
