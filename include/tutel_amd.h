@@ -533,7 +533,12 @@ int tutel_amd_packed_layout(const int32_t *dispatch_count, const int32_t *idx, c
  * rounded once.  A row r is A + r*lda, or, with a_rows (the packed slot map), token a_rows[r] % T of A (zero_row for -1).  W[e]
  * at W + e*w_stride_e: w_kmajor = 1 [N][K] (the 256-row ping-pong kernel of the forward), 0 [K][N] as stored (the 128 x 128
  * register-staged kernel, transposing LDS read; act none or relu, no mul).  mul: optional gating operand with D's layout
- * (k-major only), e.g. the ReLU mask of the backward.  offsets / tiles / ntiles / capacity from tutel_amd_packed_layout. */
+ * (k-major only), e.g. the ReLU mask of the backward.  offsets / tiles / ntiles / capacity from tutel_amd_packed_layout.
+ * Shapes: K a multiple of 64, N any multiple of 8 from 8 up, in both weight layouts -- also below the 128 columns from which
+ * tutel_amd_packed_plan takes a layer and the padded dispatcher picks the 256-row kernel: a column tile that reaches past N clamps
+ * its weight rows (k-major) / 8-column chunks (n-major), its bias and its gating-operand loads into [0, N) and stores only whole
+ * 8-column groups below N, so the narrow shapes cost idle MFMA columns, not correctness.  Any other N or K is an error (not
+ * TUTEL_AMD_ENOTSUP) reported before anything is enqueued. */
 int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W,
                                  int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul,
                                  void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,

@@ -203,7 +203,9 @@ extern "C" int tutel_amd_expert_bgrad_packed(const void *B, int ldb, void *D, in
   return 0;
 }
 
-// the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed_ex (expert_gemm.hip)
+// the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed_ex (expert_gemm.hip).  N is any multiple of 8
+// from 8 up (tutel_gemm_args refuses the rest before a launch): below the plan's 128 columns both kernels clamp every weight, bias
+// and gating-operand load of a column tile into [0, N) and store whole 8-column groups below N only (include/tutel_amd.h)
 extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W,
                                             int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul,
                                             void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,

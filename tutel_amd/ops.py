@@ -436,10 +436,11 @@ def packed_layout(dispatch_count, idx, loc, capacity_limit, alignment, rows_boun
     return lay
 
 
-def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, zero_row=None, mul=None):
+def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, zero_row=None, mul=None, out=None):
     """Packed rows: D[r] = act(A[r] @ op(W[e]) + bias[e]) [* mul[r]] for the rows r of expert e -> [rows_bound, N].
     a [rows_bound, K], or with gather=True the token array [T, K] read through layout.slot_map (zero_row for pad rows);
-    w [E, N, K] (w_kmajor) or [E, K, N] as stored.  Rows past layout.offsets[E] are left unwritten."""
+    w [E, N, K] (w_kmajor) or [E, K, N] as stored; N any multiple of 8.  Rows past layout.offsets[E] are left unwritten
+    (out: a contiguous [rows_bound, N] tensor to write into instead of a fresh one)."""
     _dev(a, w, bias, mul)
     assert a.dim() == 2 and a.is_contiguous() and w.dim() == 3 and w.is_contiguous() and w.dtype == a.dtype
     E, N, K = (w.shape[0], w.shape[1], w.shape[2]) if w_kmajor else (w.shape[0], w.shape[2], w.shape[1])
@@ -449,7 +450,11 @@ def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, ze
     if mul is not None:
         assert mul.shape == (layout.rows_bound, N) and mul.is_contiguous() and mul.dtype == a.dtype
     a = _a16(a)
-    out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
+    if out is None:
+        out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
+    else:
+        _dev(out)
+        assert out.shape == (layout.rows_bound, N) and out.is_contiguous() and out.dtype == a.dtype
     _lib.check(_lib.lib().tutel_amd_expert_gemm_packed(
         _ptr(a), K, _ptr(layout.slot_map) if gather else None, a.shape[0] if gather else 0, _ptr(zero_row) if gather else None,
         _ptr(w), int(bool(w_kmajor)), w.stride(0), w.stride(1), _ptr(bias), (bias.stride(0) if bias is not None else 0), _ptr(mul),
