@@ -555,6 +555,16 @@ int tutel_amd_expert_wgrad_packed(const void *A, int lda, const void *B, int ldb
 /* tutel_amd_expert_bgrad_packed: the bias gradient D[e, :] = sum over rows(e) of B [*, N] (fp32 in row order, rounded once). */
 int tutel_amd_expert_bgrad_packed(const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
                                   tutel_stream_t stream);
+/* tutel_amd_expert_wgrad_packed_f32 / tutel_amd_expert_bgrad_packed_f32: the two gradients above with an fp32 result, for fp32
+ * master weights trained under autocast: the same fp32 sums in the same order, stored WITHOUT the final rounding to dtype (so
+ * rounding D to dtype gives the 16-bit entry point's bits, and a sum past the 16-bit type's range stays finite).  Arguments as
+ * their 16-bit siblings': dtype still names the operands' 16-bit type, D is float [E, N_a, N_b] / [E, N] at a 16-byte aligned
+ * address (a lane stores 4 consecutive N_b outputs as one 16-byte vector).  Same refusals before any launch. */
+int tutel_amd_expert_wgrad_packed_f32(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                                      const void *zero_row, float *D, int E, int rows_bound, int Na, int Nb, int dtype,
+                                      const int32_t *offsets, tutel_stream_t stream);
+int tutel_amd_expert_bgrad_packed_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
+                                      tutel_stream_t stream);
 /* tutel_amd_gate_grad_packed: ggate[j*T + t] = <x[t], buf[offsets[e] + loc]> (fp32) for choice j of token t routed to expert e,
  * 0 for an entry dropped by the row limit (loc >= row_limit; pass INT_MAX for none): tutel_amd_gate_grad on the packed rows. */
 int tutel_amd_gate_grad_packed(const void *x, const void *buf, int dtype, const int32_t *idx, const int32_t *loc, int T, int M,

@@ -3,10 +3,14 @@
 forward, loss = y.float().square().mean() + l_aux, backward.  Three variants, interleaved round-robin so that clock and thermal
 drift hit all of them alike: the padded eager step (dropless_packed off), the packed eager step, and the packed step replayed
 from a torch.cuda.graph capture.  Each step is timed with device events; the median over the steps is printed as one JSON line.
+--amp bf16|fp16: fp32 master weights and an fp32 input, the step under torch.autocast (examples/helloworld_amp.py) -- the packed
+step then casts its 16-bit compute copies per call and takes fp32 weight gradients straight from the accumulators.
+--reps N: the timed window N times over in the same process (same capture), one median per repetition: the spread.
 
-    python tools/packed_train_bench.py [--steps 50] [--warmup 10]
+    python tools/packed_train_bench.py [--steps 50] [--warmup 10] [--amp bf16] [--reps 5]
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -24,25 +28,29 @@ def main():
     ap.add_argument("--T", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=2048)
     ap.add_argument("--E", type=int, default=64)
+    ap.add_argument("--amp", choices=["bf16", "fp16"], default=None, help="fp32 master weights, the step under torch.autocast in this dtype")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the timed window (the median of each is reported)")
     args = ap.parse_args()
     from tutel import moe
     T, M, E = args.T, args.dim, args.E
     torch.manual_seed(0)
-    torch.set_default_dtype(torch.bfloat16)
+    amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
+    torch.set_default_dtype(torch.float32 if amp is not None else torch.bfloat16)
     layer = moe.moe_layer(gate_type={"type": "top", "k": 2, "capacity_factor": 0.0},
                           experts={"type": "ffn", "num_experts_per_device": E, "hidden_size_per_expert": M,
                                    "activation_fn": lambda t: torch.nn.functional.relu(t)}, model_dim=M)
     torch.set_default_dtype(torch.float32)
     layer = layer.cuda().train()
     params = list(layer.parameters())
-    x = torch.randn(T, M, device="cuda", dtype=torch.bfloat16)
+    x = torch.randn(T, M, device="cuda", dtype=torch.float32 if amp is not None else torch.bfloat16)
 
     def step(packed):
         layer.dropless_packed = packed
         for p in params:
             p.grad = None
-        y = layer(x)
-        loss = y.float().square().mean() + y.l_aux.float()
+        with (torch.autocast("cuda", dtype=amp) if amp is not None else contextlib.nullcontext()):
+            y = layer(x)
+            loss = y.float().square().mean() + y.l_aux.float()
         loss.backward()
 
     # capture FIRST: warmed up on a side stream, before any eager step on the default stream -- an autograd graph kept alive by the
@@ -64,19 +72,28 @@ def main():
         step(False)
         step(True)
     variants = {"padded_eager": lambda: step(False), "packed_eager": lambda: step(True), "packed_graph": g.replay}
-    times = {n: [] for n in variants}
-    for i in range(args.warmup + args.steps):
-        for n, fn in variants.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= args.warmup:
-                times[n].append(a.elapsed_time(b))
-    print(json.dumps({"shape": {"T": T, "M": M, "H": M, "E": E, "k": 2, "dtype": "bf16"}, "steps": args.steps,
-                      "median_ms": {n: round(statistics.median(v), 4) for n, v in times.items()},
-                      "min_ms": {n: round(min(v), 4) for n, v in times.items()}}))
+    reps = {n: [] for n in variants}
+    for rep in range(max(args.reps, 1)):
+        times = {n: [] for n in variants}
+        for i in range(args.warmup + args.steps):
+            for n, fn in variants.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                if i >= args.warmup:
+                    times[n].append(a.elapsed_time(b))
+        for n, v in times.items():
+            reps[n].append((statistics.median(v), min(v)))
+    out = {"shape": {"T": T, "M": M, "H": M, "E": E, "k": 2, "dtype": args.amp or "bf16", "masters": "fp32" if amp is not None else "bf16"},
+           "amp": args.amp, "steps": args.steps,
+           "median_ms": {n: round(statistics.median(m for m, _ in v), 4) for n, v in reps.items()},
+           "min_ms": {n: round(min(lo for _, lo in v), 4) for n, v in reps.items()}}
+    if args.reps > 1:
+        out["reps"] = args.reps
+        out["rep_median_ms"] = {n: [round(m, 4) for m, _ in v] for n, v in reps.items()}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

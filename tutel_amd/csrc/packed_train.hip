@@ -11,7 +11,9 @@
 // TRANSPOSED, [column][row] (row pitch 64 + 8 elements: the 16-byte fragment reads of 32 consecutive columns are conflict-free):
 // one thread fetches an 8-row x 8-column block (eight 16-byte loads down the rows), transposes it in registers and writes 8
 // 16-byte LDS rows.  The B fragment is the MFMA's "A" so that a lane ends up with 4 consecutive N_b outputs of one N_a row:
-// 8-byte stores, the layout of the parameters [E, N_a, N_b].
+// 8-byte stores, the layout of the parameters [E, N_a, N_b].  With OT = float (the *_f32 entry points: fp32 master weights under
+// autocast) the same four accumulators leave unrounded as one 16-byte store; everything before the epilogue is shared, so the
+// fp32 form is the 16-bit form's sum without its final rounding.
 // One workgroup owns one output tile and walks its expert's rows in order: fp32 sums in a fixed order, no atomics, the same bits
 // run after run.  An expert without rows stores zeros; nothing at or past off[E] is read.  One operand may be gathered through
 // the packed slot map (pad rows -> the zero row), as the forward fc1 gathers its rows, so no packed copy of x exists.
@@ -26,10 +28,11 @@
 #define WG_LD (WG_BK + 8)
 #define WG_THREADS 256
 
-template <typename T>
+// OT: the output element, T's 16 bits (D as uint16_t) or float
+template <typename T, typename OT>
 __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint16_t *__restrict__ A, int lda, const uint16_t *__restrict__ B, int ldb,
                                                                     const int32_t *__restrict__ rows_map, int gather_b, int t_mod,
-                                                                    const uint16_t *__restrict__ zero_row, uint16_t *__restrict__ D, int Na,
+                                                                    const uint16_t *__restrict__ zero_row, OT *__restrict__ D, int Na,
                                                                     int Nb, int tna, int tnb, const int32_t *__restrict__ off) {
   __shared__ __attribute__((aligned(16))) uint16_t sA[WG_T * WG_LD];
   __shared__ __attribute__((aligned(16))) uint16_t sB[WG_T * WG_LD];
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint1
   }
 
   // lane: output row i = i0 + wa*64 + mi*32 + l31, columns j = j0 + wb*64 + nj*32 + rg*8 + kg*4 + 0..3
-  uint16_t *De = D + (size_t)e * Na * Nb;
+  OT *De = D + (size_t)e * Na * Nb;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
     const int i = i0 + wa * 64 + mi * 32 + l31;
@@ -123,84 +126,123 @@ __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint1
       for (int rg = 0; rg < 4; ++rg) {
         const int j = j0 + wb * 64 + nj * 32 + rg * 8 + kg * 4;
         if (j >= Nb) continue;
-        uint16_t o[4];
+        if constexpr (sizeof(OT) == 4) {  // fp32: the accumulators as they are, 16 bytes (N_b % 8 == 0 and D 16-byte aligned)
+          *reinterpret_cast<float4 *>(De + (size_t)i * Nb + j) =
+              float4{acc[nj][mi][rg * 4], acc[nj][mi][rg * 4 + 1], acc[nj][mi][rg * 4 + 2], acc[nj][mi][rg * 4 + 3]};
+        } else {
+          uint16_t o[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          T tv = Elem<T>::from_f32(acc[nj][mi][rg * 4 + r]);
-          __builtin_memcpy(&o[r], &tv, 2);
+          for (int r = 0; r < 4; ++r) {
+            T tv = Elem<T>::from_f32(acc[nj][mi][rg * 4 + r]);
+            __builtin_memcpy(&o[r], &tv, 2);
+          }
+          uint2 ov;
+          ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
+          ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
+          *reinterpret_cast<uint2 *>(De + (size_t)i * Nb + j) = ov;
         }
-        uint2 ov;
-        ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
-        ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
-        *reinterpret_cast<uint2 *>(De + (size_t)i * Nb + j) = ov;
       }
   }
 }
 
-// db[e][n] = sum of B[r][n] over rows(e): one thread per (expert, column), the rows in order (fp32, rounded once)
-template <typename T>
-__global__ __launch_bounds__(256) void packed_bgrad_kernel(const T *__restrict__ B, int ldb, T *__restrict__ D, int N,
+// db[e][n] = sum of B[r][n] over rows(e): one thread per (expert, column), the rows in order (fp32, rounded once; OT = float: not at all)
+template <typename T, typename OT>
+__global__ __launch_bounds__(256) void packed_bgrad_kernel(const T *__restrict__ B, int ldb, OT *__restrict__ D, int N,
                                                            const int32_t *__restrict__ off) {
   const int e = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const int r0 = off[e], r1 = off[e + 1];
   float s = 0.f;
   for (int r = r0; r < r1; ++r) s += Elem<T>::to_f32(B[(size_t)r * ldb + n]);
-  D[(size_t)e * N + n] = Elem<T>::from_f32(s);
+  if constexpr (sizeof(OT) == 4) D[(size_t)e * N + n] = s;
+  else D[(size_t)e * N + n] = Elem<T>::from_f32(s);
 }
 
-static int wgrad_notsup(const char *why) {
-  tutel_set_error("tutel_amd_expert_wgrad_packed: not covered: %s", why);
+// the two entry points of each gradient share their checks and launches: `what` names the caller in errors, out_f32 picks the output form
+static int wgrad_notsup(const char *what, const char *why) {
+  tutel_set_error("%s: not covered: %s", what, why);
   return TUTEL_AMD_ENOTSUP;
+}
+
+static int wgrad_packed(const char *what, bool out_f32, const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                        const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype, const int32_t *offsets,
+                        tutel_stream_t stream) {
+  TUTEL_REQUIRE(E >= 1 && rows_bound >= 0 && Na >= 1 && Nb >= 1 && lda >= Na && ldb >= Nb && gather >= 0 && gather <= 2 &&
+                    (gather == 0 || (rows_map != nullptr && T >= 1)),
+                "%s: bad sizes E=%d rows=%d Na=%d Nb=%d lda=%d ldb=%d gather=%d T=%d", what, E, rows_bound, Na, Nb, lda, ldb, gather, T);
+  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup(what, "16-bit operands only");
+  if (Na % 8 != 0 || Nb % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0)
+    return wgrad_notsup(what, "N_a, N_b and the leading dimensions must be multiples of 8");
+  const long long tiles = (long long)E * ((Na + WG_T - 1) / WG_T) * ((Nb + WG_T - 1) / WG_T);
+  if (tiles >= 0x7fffffffLL) return wgrad_notsup(what, "more than 2^31 output tiles");
+  TUTEL_REQUIRE(A && B && D && offsets && (gather == 0 || zero_row), "%s: null pointer", what);
+  auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
+  TUTEL_REQUIRE(al16(A) && al16(B) && al16(zero_row) && ((uintptr_t)D & (out_f32 ? 15 : 7)) == 0,
+                "%s: A, B and the zero row must be 16-byte aligned, D %d-byte", what, out_f32 ? 16 : 8);
+  hipStream_t st = (hipStream_t)stream;
+  StageScope stage(TUTEL_STAGE_OTHER, st);
+  const int tna = (Na + WG_T - 1) / WG_T, tnb = (Nb + WG_T - 1) / WG_T;
+  const int32_t *map = gather != 0 ? rows_map : nullptr;
+#define WG_GO(TT, OT)                                                                                                                      \
+  hipLaunchKernelGGL((packed_wgrad_kernel<TT, OT>), dim3((unsigned)tiles), dim3(WG_THREADS), 0, st, (const uint16_t *)A, lda, (const uint16_t *)B, \
+                     ldb, map, gather == 2 ? 1 : 0, T > 0 ? T : 1, (const uint16_t *)zero_row, (OT *)D, Na, Nb, tna, tnb, offsets)
+  if (out_f32) {
+    if (dtype == TUTEL_BF16) WG_GO(bf16_t, float);
+    else WG_GO(f16_t, float);
+  } else {
+    if (dtype == TUTEL_BF16) WG_GO(bf16_t, uint16_t);
+    else WG_GO(f16_t, uint16_t);
+  }
+#undef WG_GO
+  TUTEL_CHECK_LAUNCH(what);
+  return 0;
 }
 
 extern "C" int tutel_amd_expert_wgrad_packed(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
                                              const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype,
                                              const int32_t *offsets, tutel_stream_t stream) {
-  TUTEL_REQUIRE(E >= 1 && rows_bound >= 0 && Na >= 1 && Nb >= 1 && lda >= Na && ldb >= Nb && gather >= 0 && gather <= 2 &&
-                    (gather == 0 || (rows_map != nullptr && T >= 1)),
-                "tutel_amd_expert_wgrad_packed: bad sizes E=%d rows=%d Na=%d Nb=%d lda=%d ldb=%d gather=%d T=%d", E, rows_bound, Na, Nb, lda,
-                ldb, gather, T);
-  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup("16-bit operands only");
-  if (Na % 8 != 0 || Nb % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0) return wgrad_notsup("N_a, N_b and the leading dimensions must be multiples of 8");
-  const long long tiles = (long long)E * ((Na + WG_T - 1) / WG_T) * ((Nb + WG_T - 1) / WG_T);
-  if (tiles >= 0x7fffffffLL) return wgrad_notsup("more than 2^31 output tiles");
-  TUTEL_REQUIRE(A && B && D && offsets && (gather == 0 || zero_row), "tutel_amd_expert_wgrad_packed: null pointer");
-  auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-  TUTEL_REQUIRE(al16(A) && al16(B) && al16(zero_row) && ((uintptr_t)D & 7) == 0,
-                "tutel_amd_expert_wgrad_packed: A, B and the zero row must be 16-byte aligned, D 8-byte");
+  return wgrad_packed("tutel_amd_expert_wgrad_packed", false, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb, dtype,
+                      offsets, stream);
+}
+
+extern "C" int tutel_amd_expert_wgrad_packed_f32(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                                                 const void *zero_row, float *D, int E, int rows_bound, int Na, int Nb, int dtype,
+                                                 const int32_t *offsets, tutel_stream_t stream) {
+  return wgrad_packed("tutel_amd_expert_wgrad_packed_f32", true, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb, dtype,
+                      offsets, stream);
+}
+
+static int bgrad_packed(const char *what, bool out_f32, const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
+                        tutel_stream_t stream) {
+  TUTEL_REQUIRE(E >= 1 && N >= 1 && ldb >= N, "%s: bad sizes E=%d N=%d ldb=%d", what, E, N, ldb);
+  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup(what, "16-bit operands only");
+  TUTEL_REQUIRE(E <= 65535, "%s: E=%d above the grid's 65535", what, E);
+  TUTEL_REQUIRE(B && D && offsets, "%s: null pointer", what);
+  TUTEL_REQUIRE(!out_f32 || ((uintptr_t)D & 15) == 0, "%s: D must be 16-byte aligned", what);
   hipStream_t st = (hipStream_t)stream;
   StageScope stage(TUTEL_STAGE_OTHER, st);
-  const int tna = (Na + WG_T - 1) / WG_T, tnb = (Nb + WG_T - 1) / WG_T;
-  const int32_t *map = gather != 0 ? rows_map : nullptr;
-#define WG_GO(TT)                                                                                                                     \
-  hipLaunchKernelGGL(packed_wgrad_kernel<TT>, dim3((unsigned)tiles), dim3(WG_THREADS), 0, st, (const uint16_t *)A, lda, (const uint16_t *)B, \
-                     ldb, map, gather == 2 ? 1 : 0, T > 0 ? T : 1, (const uint16_t *)zero_row, (uint16_t *)D, Na, Nb, tna, tnb, offsets)
-  if (dtype == TUTEL_BF16) WG_GO(bf16_t);
-  else WG_GO(f16_t);
-#undef WG_GO
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_wgrad_packed");
+  const dim3 grid((unsigned)((N + 255) / 256), (unsigned)E);
+#define BG_GO(TT, OT) hipLaunchKernelGGL((packed_bgrad_kernel<TT, OT>), grid, dim3(256), 0, st, (const TT *)B, ldb, (OT *)D, N, offsets)
+  if (out_f32) {
+    if (dtype == TUTEL_BF16) BG_GO(bf16_t, float);
+    else BG_GO(f16_t, float);
+  } else {
+    if (dtype == TUTEL_BF16) BG_GO(bf16_t, bf16_t);
+    else BG_GO(f16_t, f16_t);
+  }
+#undef BG_GO
+  TUTEL_CHECK_LAUNCH(what);
   return 0;
 }
 
 extern "C" int tutel_amd_expert_bgrad_packed(const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
                                              tutel_stream_t stream) {
-  TUTEL_REQUIRE(E >= 1 && N >= 1 && ldb >= N, "tutel_amd_expert_bgrad_packed: bad sizes E=%d N=%d ldb=%d", E, N, ldb);
-  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) {
-    tutel_set_error("tutel_amd_expert_bgrad_packed: not covered: 16-bit operands only");
-    return TUTEL_AMD_ENOTSUP;
-  }
-  TUTEL_REQUIRE(E <= 65535, "tutel_amd_expert_bgrad_packed: E=%d above the grid's 65535", E);
-  TUTEL_REQUIRE(B && D && offsets, "tutel_amd_expert_bgrad_packed: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  StageScope stage(TUTEL_STAGE_OTHER, st);
-  const dim3 grid((unsigned)((N + 255) / 256), (unsigned)E);
-  if (dtype == TUTEL_BF16)
-    hipLaunchKernelGGL(packed_bgrad_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)B, ldb, (bf16_t *)D, N, offsets);
-  else
-    hipLaunchKernelGGL(packed_bgrad_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t *)B, ldb, (f16_t *)D, N, offsets);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_bgrad_packed");
-  return 0;
+  return bgrad_packed("tutel_amd_expert_bgrad_packed", false, B, ldb, D, E, N, dtype, offsets, stream);
+}
+
+extern "C" int tutel_amd_expert_bgrad_packed_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
+                                                 tutel_stream_t stream) {
+  return bgrad_packed("tutel_amd_expert_bgrad_packed_f32", true, B, ldb, D, E, N, dtype, offsets, stream);
 }
 
 // the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed_ex (expert_gemm.hip).  N is any multiple of 8

@@ -18,7 +18,7 @@ host bound, the capacity kept on the device), and only when asked for:
 Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes.  Both expert types
 take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM).
 
-GraphedForward is forward-only.  A dropless TRAINING step of `ffn` experts (ReLU, bf16 / fp16) on the packed layout
+GraphedForward is forward-only.  A dropless TRAINING step of `ffn` experts (ReLU; bf16 / fp16 parameters, or fp32 masters under autocast) on the packed layout
 (`layer.dropless_packed = True`, impls/packed_train.py) needs no host synchronisation in its forward or backward either, so
 forward + backward are captured with plain torch.cuda.graph.  Warm up on a side stream BEFORE any eager step on the default
 stream (the layer keeps `l_aux`, whose autograd graph would hold gradient-accumulation nodes of the default stream):
@@ -31,7 +31,12 @@ stream (the layer keeps `l_aux`, whose autograd graph would hold gradient-accumu
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         step()
-    static_x.copy_(x); g.replay()                  # the parameters' .grad hold this batch's gradients"""
+    static_x.copy_(x); g.replay()                  # the parameters' .grad hold this batch's gradients
+
+The same recipe captures the step of fp32 master weights under autocast (examples/helloworld_amp.py): put `with
+torch.autocast("cuda", dtype=...)` around the forward and the loss INSIDE step().  The packed step casts its 16-bit compute copies
+from the masters inside the captured forward, on every replay, and its weight / bias gradients are fp32 -- so an optimizer step
+on the masters between replays (outside the graph, or captured after the backward) is seen by the next replay."""
 import torch
 
 

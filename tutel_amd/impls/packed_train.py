@@ -17,6 +17,11 @@ from the device offsets -- so the whole step, loss.backward() included, can be c
                 dhid = (dY @ W2^T) * [hid > 0]                        (k-major, gated epilogue)
                 dW1  = dhid^T x[slot], db1 = sum dhid
                 dx   = sum_j (dhid @ W1)[off[e] + loc]                (n-major GEMM, then the packed decode without gates)
+
+Under torch.autocast over fp32 master weights (examples/helloworld_amp.py) the same launches run on 16-bit compute copies that
+the forward casts from the masters on EVERY call -- no cache: a captured graph re-casts on every replay, after the optimizer
+has changed the masters -- and the weight / bias gradients leave their fp32 accumulators unrounded (out_dtype=torch.float32):
+a loss-scaled fp16 sum past 65504 stays finite, and no 16-bit gradient is cast back up.
 """
 import torch
 
@@ -66,8 +71,12 @@ def unsupported(layer, gate, T, E, k, M, dtype, cf, alignment, reserve_dims=1, o
         return "the packed training step needs unsharded local experts (sharded_count = 1, adaptive_r = 1, reserve_dims = 1)"
     w1 = ex.batched_fc1_w
     if torch.is_autocast_enabled() and w1.dtype == torch.float32:
-        return "the packed training step does not cover autocast over fp32 master weights"
-    if w1.dtype not in (torch.bfloat16, torch.float16) or dtype != w1.dtype:
+        # fp32 master weights under (CUDA) autocast: 16-bit compute copies cast per call, fp32 gradients (_PackedFFNTrain)
+        if any(p.dtype != torch.float32 for p in ex.parameters()):
+            return "the packed training step under autocast needs every expert parameter in fp32 (master weights)"
+        if dtype != torch.get_autocast_dtype("cuda") or dtype not in (torch.bfloat16, torch.float16):
+            return "the packed training step under autocast needs tokens in the autocast dtype, bf16 / fp16"
+    elif w1.dtype not in (torch.bfloat16, torch.float16) or dtype != w1.dtype:
         return "the packed training step needs bf16 / fp16 experts and tokens in their dtype"
     if ex.fused_activation() != "relu":
         return "the packed training step needs the ReLU activation"
@@ -81,10 +90,16 @@ def unsupported(layer, gate, T, E, k, M, dtype, cf, alignment, reserve_dims=1, o
 
 
 class _PackedFFNTrain(torch.autograd.Function):
-    """y from (x, gates) over one packed layout; see the module docstring for the launches"""
+    """y from (x, gates) over one packed layout; see the module docstring for the launches.  w1 / b1 / w2 / b2 are the parameters
+    themselves: in x's dtype, or fp32 masters, cast to x's dtype here on every call (never cached: see the module docstring)"""
 
     @staticmethod
     def forward(ctx, x, gates2d, w1, b1, w2, b2, lay, idx, loc, zero_row):
+        ctx.master_dtype = w1.dtype
+        if w1.dtype != x.dtype:
+            w1, w2 = w1.to(x.dtype), w2.to(x.dtype)
+            b1 = b1.to(x.dtype) if b1 is not None else None
+            b2 = b2.to(x.dtype) if b2 is not None else None
         hid = ops.expert_gemm_packed(x, w1, b1, True, lay, act="relu", gather=True, zero_row=zero_row)
         yp = ops.expert_gemm_packed(hid, w2, b2, False, lay)
         y = ops.fast_decode_packed(yp, idx, loc, gates2d, lay)
@@ -95,8 +110,8 @@ class _PackedFFNTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        x, gates2d, w1, w2, hid, yp = ctx.saved_tensors
-        lay, idx, loc = ctx.lay, ctx.idx, ctx.loc
+        x, gates2d, w1, w2, hid, yp = ctx.saved_tensors   # w1, w2: the compute copies
+        lay, idx, loc, gdt = ctx.lay, ctx.idx, ctx.loc, ctx.master_dtype
         gy = gy.contiguous()
         need_x, need_g, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:6]
         gx = gg = gw1 = gb1 = gw2 = gb2 = None
@@ -104,15 +119,15 @@ class _PackedFFNTrain(torch.autograd.Function):
             gg = ops.gate_grad_packed(gy, yp, idx, loc, lay).to(gates2d.dtype)
         dyp = ops.fast_encode(gy, lay.slot_map, gates2d.detach(), lay.rows_bound)
         if need_w2:
-            gw2 = ops.expert_wgrad_packed(hid, dyp, lay)
+            gw2 = ops.expert_wgrad_packed(hid, dyp, lay, out_dtype=gdt)
         if need_b2 and ctx.has_bias[1]:
-            gb2 = ops.expert_bgrad_packed(dyp, lay)
+            gb2 = ops.expert_bgrad_packed(dyp, lay, out_dtype=gdt)
         if need_x or need_w1 or (need_b1 and ctx.has_bias[0]):
             dhid = ops.expert_gemm_packed(dyp, w2, None, True, lay, mul=(hid > 0).to(hid.dtype))
             if need_w1:
-                gw1 = ops.expert_wgrad_packed(dhid, x, lay, gather="b", zero_row=ctx.zero_row)
+                gw1 = ops.expert_wgrad_packed(dhid, x, lay, gather="b", zero_row=ctx.zero_row, out_dtype=gdt)
             if need_b1 and ctx.has_bias[0]:
-                gb1 = ops.expert_bgrad_packed(dhid, lay)
+                gb1 = ops.expert_bgrad_packed(dhid, lay, out_dtype=gdt)
             if need_x:
                 gx = ops.fast_decode_packed(ops.expert_gemm_packed(dhid, w1, None, False, lay), idx, loc, None, lay)
         return gx, gg, gw1, gb1, gw2, gb2, None, None, None, None

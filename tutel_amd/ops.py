@@ -463,31 +463,44 @@ def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, ze
     return out
 
 
-def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None):
+def _grad_out_dtype(out_dtype, operand_dtype):
+    """out_dtype of the packed gradients: None -> the operands' dtype (the 16-bit entry points), torch.float32 -> the *_f32 ones"""
+    if out_dtype is None or out_dtype == operand_dtype:
+        return operand_dtype, ""
+    if out_dtype == torch.float32:
+        return torch.float32, "_f32"
+    raise _lib.TutelAmdError(f"tutel_amd: the packed gradients come in the operands' dtype or torch.float32, not {out_dtype}")
+
+
+def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None, out_dtype=None):
     """Weight gradient over the packed rows: D[e] = A[rows(e)]^T @ B[rows(e)] -> [E, N_a, N_b], fp32 sums in a fixed order.
     a [rows_bound, N_a], b [rows_bound, N_b]; gather="a" or "b": that operand is the token array [T, *] read through
-    layout.slot_map (zero_row, >= 8 zeros, for pad rows)."""
+    layout.slot_map (zero_row, >= 8 zeros, for pad rows).  out_dtype: None (the operands' dtype, rounded once) or torch.float32
+    (the same sums left unrounded: fp32 master weights under autocast)."""
     _dev(a, b)
     assert a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype
     assert gather in (None, "a", "b")
+    dt, sfx = _grad_out_dtype(out_dtype, a.dtype)
     a, b = _a16(a), _a16(b)
     Na, Nb = a.shape[1], b.shape[1]
     g = {None: 0, "a": 1, "b": 2}[gather]
     T = (a if gather == "a" else b).shape[0] if gather else 0
-    out = torch.empty([layout.E, Na, Nb], dtype=a.dtype, device=a.device)
-    _lib.check(_lib.lib().tutel_amd_expert_wgrad_packed(
+    out = torch.empty([layout.E, Na, Nb], dtype=dt, device=a.device)
+    what = "tutel_amd_expert_wgrad_packed" + sfx
+    _lib.check(getattr(_lib.lib(), what)(
         _ptr(a), Na, _ptr(b), Nb, _ptr(layout.slot_map) if g else None, g, T, _ptr(zero_row) if g else None,
-        _ptr(out), layout.E, layout.rows_bound, Na, Nb, _code(a), _ptr(layout.offsets), _stream()), "tutel_amd_expert_wgrad_packed")
+        _ptr(out), layout.E, layout.rows_bound, Na, Nb, _code(a), _ptr(layout.offsets), _stream()), what)
     return out
 
 
-def expert_bgrad_packed(b, layout):
-    """Bias gradient over the packed rows: D[e] = sum of b[rows(e)] -> [E, N]."""
+def expert_bgrad_packed(b, layout, out_dtype=None):
+    """Bias gradient over the packed rows: D[e] = sum of b[rows(e)] -> [E, N] (out_dtype as expert_wgrad_packed's)."""
     _dev(b)
     assert b.dim() == 2 and b.is_contiguous()
-    out = torch.empty([layout.E, b.shape[1]], dtype=b.dtype, device=b.device)
-    _lib.check(_lib.lib().tutel_amd_expert_bgrad_packed(_ptr(b), b.shape[1], _ptr(out), layout.E, b.shape[1], _code(b), _ptr(layout.offsets),
-                                                        _stream()), "tutel_amd_expert_bgrad_packed")
+    dt, sfx = _grad_out_dtype(out_dtype, b.dtype)
+    out = torch.empty([layout.E, b.shape[1]], dtype=dt, device=b.device)
+    what = "tutel_amd_expert_bgrad_packed" + sfx
+    _lib.check(getattr(_lib.lib(), what)(_ptr(b), b.shape[1], _ptr(out), layout.E, b.shape[1], _code(b), _ptr(layout.offsets), _stream()), what)
     return out
 
 
