@@ -291,7 +291,8 @@ def expert_gemm(a, w, bias, w_kmajor, act="none", E_loc=None, R=None, a_layout=N
         R = a.shape[1]
         a_layout = (R * K, 0, R, K)
     assert R is not None
-    if out is None:
+    default_out = out is None
+    if default_out:
         out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
         d_layout = (R * N, 0, R, N)
     assert d_layout is not None
@@ -299,7 +300,12 @@ def expert_gemm(a, w, bias, w_kmajor, act="none", E_loc=None, R=None, a_layout=N
         assert bias.is_contiguous() and bias.shape[-1] == N and bias.dtype == a.dtype
     assert w.dtype == a.dtype
     if mul is not None:
-        assert mul.dtype == a.dtype and mul.is_contiguous()
+        assert mul.dtype == a.dtype
+        if default_out:
+            assert mul.is_contiguous() and mul.numel() == E_loc * R * N
+        else:
+            # the kernel addresses G through d_layout exactly as it addresses `out` (G may be `out` itself): same extent, same strides
+            assert mul.shape == out.shape and mul.stride() == out.stride(), "mul must have the layout of out"
         _lib.check(_lib.lib().tutel_amd_expert_gemm_glu(
             _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
             _ptr(w), int(bool(w_kmajor)), w.stride(0), w.stride(1),
