@@ -565,6 +565,19 @@ int tutel_amd_expert_wgrad_packed_f32(const void *A, int lda, const void *B, int
                                       const int32_t *offsets, tutel_stream_t stream);
 int tutel_amd_expert_bgrad_packed_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
                                       tutel_stream_t stream);
+/* ---- gradient accumulation into an fp32 main_grad (micro-batches) ----
+ * tutel_amd_expert_wgrad_packed_acc_f32 / tutel_amd_expert_bgrad_packed_acc_f32: D += G, where G is what the *_f32 entry point
+ * above writes for the same operands, bit for bit: the epilogue reads the fp32 values of D it owns, adds its accumulators (one
+ * IEEE fp32 add per element, nothing fused into it) and stores them back, instead of a separate gradient tensor that a later
+ * kernel adds.  One workgroup (weights) / thread (biases) owns each output, so there are no atomics and the result is the same
+ * bits run after run; k calls accumulate in call order, ((D + G1) + G2) + ...  An expert without rows (offsets[e] ==
+ * offsets[e+1]) leaves its part of D untouched: it is neither read nor written.  Arguments, alignment (D 16-byte aligned),
+ * refusals and argument errors as the *_f32 siblings', all reported before anything is enqueued. */
+int tutel_amd_expert_wgrad_packed_acc_f32(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                                          const void *zero_row, float *D, int E, int rows_bound, int Na, int Nb, int dtype,
+                                          const int32_t *offsets, tutel_stream_t stream);
+int tutel_amd_expert_bgrad_packed_acc_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
+                                          tutel_stream_t stream);
 /* tutel_amd_gate_grad_packed: ggate[j*T + t] = <x[t], buf[offsets[e] + loc]> (fp32) for choice j of token t routed to expert e,
  * 0 for an entry dropped by the row limit (loc >= row_limit; pass INT_MAX for none): tutel_amd_gate_grad on the packed rows. */
 int tutel_amd_gate_grad_packed(const void *x, const void *buf, int dtype, const int32_t *idx, const int32_t *loc, int T, int M,

@@ -96,6 +96,8 @@ SIGNATURES.update({
     "tutel_amd_expert_bgrad_packed": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "tutel_amd_expert_wgrad_packed_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "tutel_amd_expert_bgrad_packed_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "tutel_amd_expert_wgrad_packed_acc_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
+    "tutel_amd_expert_bgrad_packed_acc_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "tutel_amd_gate_grad_packed": (_i, [_vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp]),
     "tutel_amd_fast_decode_packed": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp]),
     "tutel_amd_ep_load_rccl": (_i, [ctypes.c_char_p]),

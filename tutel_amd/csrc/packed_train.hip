@@ -17,6 +17,10 @@
 // One workgroup owns one output tile and walks its expert's rows in order: fp32 sums in a fixed order, no atomics, the same bits
 // run after run.  An expert without rows stores zeros; nothing at or past off[E] is read.  One operand may be gathered through
 // the packed slot map (pad rows -> the zero row), as the forward fc1 gathers its rows, so no packed copy of x exists.
+// ACC (the *_acc_f32 entry points, OT = float only: gradient accumulation into an fp32 main_grad over micro-batches): the epilogue
+// reads the 16 bytes of D it owns, adds the four accumulators (one fp32 add each; -ffp-contract=off, and nothing to fuse with)
+// and stores them back -- D += G with G the *_f32 form's bits.  The tile has one owner, so the read-modify-write needs no atomic.
+// An expert without rows returns before the epilogue: its part of D is neither read nor written.
 #include <climits>
 
 #include "common.h"
@@ -28,8 +32,8 @@
 #define WG_LD (WG_BK + 8)
 #define WG_THREADS 256
 
-// OT: the output element, T's 16 bits (D as uint16_t) or float
-template <typename T, typename OT>
+// OT: the output element, T's 16 bits (D as uint16_t) or float; ACC: D += the sums instead of D = them
+template <typename T, typename OT, bool ACC = false>
 __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint16_t *__restrict__ A, int lda, const uint16_t *__restrict__ B, int ldb,
                                                                     const int32_t *__restrict__ rows_map, int gather_b, int t_mod,
                                                                     const uint16_t *__restrict__ zero_row, OT *__restrict__ D, int Na,
@@ -42,6 +46,10 @@ __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint1
   const int e = bid / (tna * tnb), ta = (bid / tnb) % tna, tb = bid % tnb;
   const int i0 = ta * WG_T, j0 = tb * WG_T;
   const int r_begin = __builtin_amdgcn_readfirstlane(off[e]), r_end = __builtin_amdgcn_readfirstlane(off[e + 1]);
+  if constexpr (ACC) {
+    static_assert(sizeof(OT) == 4, "the accumulating form is fp32 only");
+    if (r_begin >= r_end) return;  // no rows (uniform over the workgroup): D keeps its bits, untouched
+  }
 
   // loader: threads 0..127 the A tile, 128..255 the B tile; thread -> (8-row block rb, 8-column chunk cb)
   const bool is_a = tid < 128;
@@ -126,7 +134,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint1
       for (int rg = 0; rg < 4; ++rg) {
         const int j = j0 + wb * 64 + nj * 32 + rg * 8 + kg * 4;
         if (j >= Nb) continue;
-        if constexpr (sizeof(OT) == 4) {  // fp32: the accumulators as they are, 16 bytes (N_b % 8 == 0 and D 16-byte aligned)
+        if constexpr (ACC) {  // fp32 read-modify-write of the 16 bytes this lane owns
+          float4 *dp = reinterpret_cast<float4 *>(De + (size_t)i * Nb + j);
+          float4 d = *dp;
+          d.x += acc[nj][mi][rg * 4];
+          d.y += acc[nj][mi][rg * 4 + 1];
+          d.z += acc[nj][mi][rg * 4 + 2];
+          d.w += acc[nj][mi][rg * 4 + 3];
+          *dp = d;
+        } else if constexpr (sizeof(OT) == 4) {  // fp32: the accumulators as they are, 16 bytes (N_b % 8 == 0 and D 16-byte aligned)
           *reinterpret_cast<float4 *>(De + (size_t)i * Nb + j) =
               float4{acc[nj][mi][rg * 4], acc[nj][mi][rg * 4 + 1], acc[nj][mi][rg * 4 + 2], acc[nj][mi][rg * 4 + 3]};
         } else {
@@ -146,7 +162,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void packed_wgrad_kernel(const uint1
 }
 
 // db[e][n] = sum of B[r][n] over rows(e): one thread per (expert, column), the rows in order (fp32, rounded once; OT = float: not at all)
-template <typename T, typename OT>
+// ACC (OT = float): D[e][n] += the sum; an expert without rows leaves D untouched
+template <typename T, typename OT, bool ACC = false>
 __global__ __launch_bounds__(256) void packed_bgrad_kernel(const T *__restrict__ B, int ldb, OT *__restrict__ D, int N,
                                                            const int32_t *__restrict__ off) {
   const int e = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
@@ -154,17 +171,22 @@ __global__ __launch_bounds__(256) void packed_bgrad_kernel(const T *__restrict__
   const int r0 = off[e], r1 = off[e + 1];
   float s = 0.f;
   for (int r = r0; r < r1; ++r) s += Elem<T>::to_f32(B[(size_t)r * ldb + n]);
-  if constexpr (sizeof(OT) == 4) D[(size_t)e * N + n] = s;
+  if constexpr (ACC) {
+    static_assert(sizeof(OT) == 4, "the accumulating form is fp32 only");
+    if (r0 >= r1) return;
+    D[(size_t)e * N + n] += s;
+  } else if constexpr (sizeof(OT) == 4) D[(size_t)e * N + n] = s;
   else D[(size_t)e * N + n] = Elem<T>::from_f32(s);
 }
 
-// the two entry points of each gradient share their checks and launches: `what` names the caller in errors, out_f32 picks the output form
+// the three entry points of each gradient share their checks and launches: `what` names the caller in errors, out_f32 picks the
+// output form, acc (with out_f32) the accumulating epilogue
 static int wgrad_notsup(const char *what, const char *why) {
   tutel_set_error("%s: not covered: %s", what, why);
   return TUTEL_AMD_ENOTSUP;
 }
 
-static int wgrad_packed(const char *what, bool out_f32, const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+static int wgrad_packed(const char *what, bool out_f32, bool acc, const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
                         const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype, const int32_t *offsets,
                         tutel_stream_t stream) {
   TUTEL_REQUIRE(E >= 1 && rows_bound >= 0 && Na >= 1 && Nb >= 1 && lda >= Na && ldb >= Nb && gather >= 0 && gather <= 2 &&
@@ -183,10 +205,13 @@ static int wgrad_packed(const char *what, bool out_f32, const void *A, int lda, 
   StageScope stage(TUTEL_STAGE_OTHER, st);
   const int tna = (Na + WG_T - 1) / WG_T, tnb = (Nb + WG_T - 1) / WG_T;
   const int32_t *map = gather != 0 ? rows_map : nullptr;
-#define WG_GO(TT, OT)                                                                                                                      \
-  hipLaunchKernelGGL((packed_wgrad_kernel<TT, OT>), dim3((unsigned)tiles), dim3(WG_THREADS), 0, st, (const uint16_t *)A, lda, (const uint16_t *)B, \
+#define WG_GO(TT, OT, ...)                                                                                                                 \
+  hipLaunchKernelGGL((packed_wgrad_kernel<TT, OT, ##__VA_ARGS__>), dim3((unsigned)tiles), dim3(WG_THREADS), 0, st, (const uint16_t *)A, lda, (const uint16_t *)B, \
                      ldb, map, gather == 2 ? 1 : 0, T > 0 ? T : 1, (const uint16_t *)zero_row, (OT *)D, Na, Nb, tna, tnb, offsets)
-  if (out_f32) {
+  if (acc) {
+    if (dtype == TUTEL_BF16) WG_GO(bf16_t, float, true);
+    else WG_GO(f16_t, float, true);
+  } else if (out_f32) {
     if (dtype == TUTEL_BF16) WG_GO(bf16_t, float);
     else WG_GO(f16_t, float);
   } else {
@@ -201,18 +226,25 @@ static int wgrad_packed(const char *what, bool out_f32, const void *A, int lda, 
 extern "C" int tutel_amd_expert_wgrad_packed(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
                                              const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype,
                                              const int32_t *offsets, tutel_stream_t stream) {
-  return wgrad_packed("tutel_amd_expert_wgrad_packed", false, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb, dtype,
+  return wgrad_packed("tutel_amd_expert_wgrad_packed", false, false, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb, dtype,
                       offsets, stream);
 }
 
 extern "C" int tutel_amd_expert_wgrad_packed_f32(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
                                                  const void *zero_row, float *D, int E, int rows_bound, int Na, int Nb, int dtype,
                                                  const int32_t *offsets, tutel_stream_t stream) {
-  return wgrad_packed("tutel_amd_expert_wgrad_packed_f32", true, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb, dtype,
-                      offsets, stream);
+  return wgrad_packed("tutel_amd_expert_wgrad_packed_f32", true, false, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na, Nb,
+                      dtype, offsets, stream);
 }
 
-static int bgrad_packed(const char *what, bool out_f32, const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
+extern "C" int tutel_amd_expert_wgrad_packed_acc_f32(const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
+                                                     const void *zero_row, float *D, int E, int rows_bound, int Na, int Nb, int dtype,
+                                                     const int32_t *offsets, tutel_stream_t stream) {
+  return wgrad_packed("tutel_amd_expert_wgrad_packed_acc_f32", true, true, A, lda, B, ldb, rows_map, gather, T, zero_row, D, E, rows_bound, Na,
+                      Nb, dtype, offsets, stream);
+}
+
+static int bgrad_packed(const char *what, bool out_f32, bool acc, const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
                         tutel_stream_t stream) {
   TUTEL_REQUIRE(E >= 1 && N >= 1 && ldb >= N, "%s: bad sizes E=%d N=%d ldb=%d", what, E, N, ldb);
   if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup(what, "16-bit operands only");
@@ -222,8 +254,11 @@ static int bgrad_packed(const char *what, bool out_f32, const void *B, int ldb, 
   hipStream_t st = (hipStream_t)stream;
   StageScope stage(TUTEL_STAGE_OTHER, st);
   const dim3 grid((unsigned)((N + 255) / 256), (unsigned)E);
-#define BG_GO(TT, OT) hipLaunchKernelGGL((packed_bgrad_kernel<TT, OT>), grid, dim3(256), 0, st, (const TT *)B, ldb, (OT *)D, N, offsets)
-  if (out_f32) {
+#define BG_GO(TT, OT, ...) hipLaunchKernelGGL((packed_bgrad_kernel<TT, OT, ##__VA_ARGS__>), grid, dim3(256), 0, st, (const TT *)B, ldb, (OT *)D, N, offsets)
+  if (acc) {
+    if (dtype == TUTEL_BF16) BG_GO(bf16_t, float, true);
+    else BG_GO(f16_t, float, true);
+  } else if (out_f32) {
     if (dtype == TUTEL_BF16) BG_GO(bf16_t, float);
     else BG_GO(f16_t, float);
   } else {
@@ -237,12 +272,17 @@ static int bgrad_packed(const char *what, bool out_f32, const void *B, int ldb, 
 
 extern "C" int tutel_amd_expert_bgrad_packed(const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
                                              tutel_stream_t stream) {
-  return bgrad_packed("tutel_amd_expert_bgrad_packed", false, B, ldb, D, E, N, dtype, offsets, stream);
+  return bgrad_packed("tutel_amd_expert_bgrad_packed", false, false, B, ldb, D, E, N, dtype, offsets, stream);
 }
 
 extern "C" int tutel_amd_expert_bgrad_packed_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
                                                  tutel_stream_t stream) {
-  return bgrad_packed("tutel_amd_expert_bgrad_packed_f32", true, B, ldb, D, E, N, dtype, offsets, stream);
+  return bgrad_packed("tutel_amd_expert_bgrad_packed_f32", true, false, B, ldb, D, E, N, dtype, offsets, stream);
+}
+
+extern "C" int tutel_amd_expert_bgrad_packed_acc_f32(const void *B, int ldb, float *D, int E, int N, int dtype, const int32_t *offsets,
+                                                     tutel_stream_t stream) {
+  return bgrad_packed("tutel_amd_expert_bgrad_packed_acc_f32", true, true, B, ldb, D, E, N, dtype, offsets, stream);
 }
 
 // the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed_ex (expert_gemm.hip).  N is any multiple of 8

@@ -36,7 +36,21 @@ stream (the layer keeps `l_aux`, whose autograd graph would hold gradient-accumu
 The same recipe captures the step of fp32 master weights under autocast (examples/helloworld_amp.py): put `with
 torch.autocast("cuda", dtype=...)` around the forward and the loss INSIDE step().  The packed step casts its 16-bit compute copies
 from the masters inside the captured forward, on every replay, and its weight / bias gradients are fp32 -- so an optimizer step
-on the masters between replays (outside the graph, or captured after the backward) is seen by the next replay."""
+on the masters between replays (outside the graph, or captured after the backward) is seen by the next replay.
+
+Gradient accumulation over micro-batches (`layer.dropless_packed_main_grad = True` after `packed_train.attach_main_grads(layer)`):
+capture ONE micro-step -- step() above, forward + loss.backward(), with the switch on -- and replay it once per micro-batch; the
+gradient kernels add into the expert parameters' fp32 `main_grad` on every replay.  Then run the optimizer on `main_grad`, eagerly:
+
+    packed_train.zero_main_grads(layer)            # a plain memset: outside the graph, or captured in a graph of its own
+    for x in micro_batches:
+        static_x.copy_(x); g.replay()              # main_grad += this batch's dW1, db1, dW2, db2 (the expert .grad stay None)
+    optimizer_step_on_main_grad()                  # eager; then zero_main_grads again
+
+The `main_grad` tensors are allocated once and their addresses never change, so the captured kernels keep accumulating into
+them: nothing else is needed -- no re-capture, no copies.  (Do not re-assign `p.main_grad` after the capture; zero it in place.
+The warm-up steps and the capture itself accumulate too: zero before the first replay.)  The router's weight and x keep their
+ordinary gradients, which hold the LAST replay's values as before."""
 import torch
 
 

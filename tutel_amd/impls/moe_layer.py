@@ -100,6 +100,9 @@ class MOELayer(torch.nn.Module):
         # a HIP graph; same bits as the padded layout.  The capacity then stays on the device: self.dropless_capacity (int32 [1])
         self.dropless_packed = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED", "0")) != 0
         self.dropless_capacity = None
+        # gradient accumulation over micro-batches: the packed training step adds the expert gradients into p.main_grad (fp32) inside
+        # the gradient kernels and returns no autograd gradient for them (impls/packed_train.py).  A forward that cannot do so raises
+        self.dropless_packed_main_grad = int(os.environ.get("TUTEL_AMD_PACKED_MAIN_GRAD", "0")) != 0
 
         experts = dict(experts)
         n_local = experts.pop("count_per_node", 1) if "count_per_node" in experts else experts.pop("num_experts_per_device", 1)
@@ -448,13 +451,23 @@ class MOELayer(torch.nn.Module):
                 return finish(*res)
 
         # dropless training on the packed layout (impls/packed_train.py): forward + backward without a host synchronisation
-        if cf <= 0 and self.dropless_packed and packed_train.autograd_live(self, x):
+        main_grad = self.dropless_packed_main_grad
+        if ((cf <= 0 and self.dropless_packed) or main_grad) and packed_train.autograd_live(self, x):
             why = packed_train.unsupported(self, gate, x.shape[0], logits.shape[-1], min(top_k, logits.shape[-1]), x.shape[1], x.dtype, cf,
                                            alignment, reserve_dims=len(reserve_shape), on_device=x.is_cuda and logits.dim() == 2)
+            if main_grad:
+                # never the padded step with this switch on: its gradients would go to .grad, the packed step's to main_grad
+                if not self.dropless_packed:
+                    why = "dropless_packed is off"
+                why = why or packed_train.main_grad_problem(self)
+                if why is not None:
+                    self._dropless_packed_ran = why
+                    raise RuntimeError("dropless_packed_main_grad: the expert gradients cannot be accumulated into main_grad: " + why)
             self._dropless_packed_ran = True if why is None else why
             if why is None:
                 with torch.autocast("cuda", enabled=False):
-                    y, l_aux = packed_train.forward(self, gate, x, logits, min(top_k, logits.shape[-1]), cf, alignment)
+                    y, l_aux = packed_train.forward(self, gate, x, logits, min(top_k, logits.shape[-1]), cf, alignment,
+                                                    main_grad=main_grad)
                 self.megablocks_size = megablocks_size
                 return finish(y, l_aux)
 

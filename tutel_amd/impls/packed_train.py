@@ -22,6 +22,14 @@ Under torch.autocast over fp32 master weights (examples/helloworld_amp.py) the s
 the forward casts from the masters on EVERY call -- no cache: a captured graph re-casts on every replay, after the optimizer
 has changed the masters -- and the weight / bias gradients leave their fp32 accumulators unrounded (out_dtype=torch.float32):
 a loss-scaled fp16 sum past 65504 stays finite, and no 16-bit gradient is cast back up.
+
+Gradient accumulation over micro-batches (layer.dropless_packed_main_grad, the Megatron-LM "gradient accumulation fusion"
+convention): the weight / bias gradient kernels add their fp32 accumulators into p.main_grad of the expert parameter in their
+epilogue (ops.expert_wgrad_packed(..., accumulate_into=p.main_grad)) instead of writing a gradient that AccumulateGrad reads back
+and adds to p.grad.  The parameter's autograd gradient is then None (p.grad stays None) and p.grad_added_to_main_grad = True; the
+optimizer reads main_grad.  For 16-bit parameters the sum over micro-batches stays in fp32 instead of being rounded per micro-batch.
+The router weight and x keep their ordinary gradients.  MOELayer.forward raises instead of running the padded step when the switch
+is on and the packed step is refused or a main_grad is missing (main_grad_problem): gradients never split between .grad and main_grad.
 """
 import torch
 
@@ -89,13 +97,51 @@ def unsupported(layer, gate, T, E, k, M, dtype, cf, alignment, reserve_dims=1, o
     return why if plan is None else None
 
 
+def main_grad_problem(layer):
+    """why this layer's expert gradients cannot be accumulated into main_grad (None: they can): every expert parameter that requires
+    grad needs a contiguous fp32 main_grad of its shape on its device; host arithmetic only."""
+    for name, p in layer.experts.named_parameters():
+        if not p.requires_grad:
+            continue
+        mg = getattr(p, "main_grad", None)
+        if not isinstance(mg, torch.Tensor):
+            return f"expert parameter {name} has no main_grad (packed_train.attach_main_grads)"
+        if mg.dtype != torch.float32:
+            return f"main_grad of expert parameter {name} is {mg.dtype}, not torch.float32"
+        if mg.shape != p.shape:
+            return f"main_grad of expert parameter {name} has shape {tuple(mg.shape)}, the parameter {tuple(p.shape)}"
+        if not mg.is_contiguous():
+            return f"main_grad of expert parameter {name} is not contiguous"
+        if mg.device != p.device:
+            return f"main_grad of expert parameter {name} is on {mg.device}, the parameter on {p.device}"
+    return None
+
+
+def attach_main_grads(layer):
+    """a zeroed fp32 main_grad of the parameter's shape, on its device, for every expert parameter that requires grad"""
+    for p in layer.experts.parameters():
+        if p.requires_grad:
+            p.main_grad = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+            p.grad_added_to_main_grad = False
+
+
+def zero_main_grads(layer):
+    """zero the expert parameters' main_grads in place (their addresses stay: a captured graph keeps accumulating into them)"""
+    for p in layer.experts.parameters():
+        if isinstance(getattr(p, "main_grad", None), torch.Tensor):
+            p.main_grad.zero_()
+            p.grad_added_to_main_grad = False
+
+
 class _PackedFFNTrain(torch.autograd.Function):
     """y from (x, gates) over one packed layout; see the module docstring for the launches.  w1 / b1 / w2 / b2 are the parameters
-    themselves: in x's dtype, or fp32 masters, cast to x's dtype here on every call (never cached: see the module docstring)"""
+    themselves: in x's dtype, or fp32 masters, cast to x's dtype here on every call (never cached: see the module docstring).
+    main: None, or the parameters (w1, b1, w2, b2) whose gradients the backward adds into their main_grad instead of returning"""
 
     @staticmethod
-    def forward(ctx, x, gates2d, w1, b1, w2, b2, lay, idx, loc, zero_row):
+    def forward(ctx, x, gates2d, w1, b1, w2, b2, lay, idx, loc, zero_row, main=None):
         ctx.master_dtype = w1.dtype
+        ctx.main = main
         if w1.dtype != x.dtype:
             w1, w2 = w1.to(x.dtype), w2.to(x.dtype)
             b1 = b1.to(x.dtype) if b1 is not None else None
@@ -115,27 +161,38 @@ class _PackedFFNTrain(torch.autograd.Function):
         gy = gy.contiguous()
         need_x, need_g, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:6]
         gx = gg = gw1 = gb1 = gw2 = gb2 = None
+
+        def out(i):
+            """where gradient i of (w1, b1, w2, b2) goes: a fresh tensor in the masters' dtype, or added into the parameter's main_grad"""
+            if ctx.main is None:
+                return {"out_dtype": gdt}
+            ctx.main[i].grad_added_to_main_grad = True
+            return {"accumulate_into": ctx.main[i].main_grad}
+
+        def grad(g):
+            return g if ctx.main is None else None   # accumulated in place: autograd gets no gradient for that parameter
+
         if need_g:
             gg = ops.gate_grad_packed(gy, yp, idx, loc, lay).to(gates2d.dtype)
         dyp = ops.fast_encode(gy, lay.slot_map, gates2d.detach(), lay.rows_bound)
         if need_w2:
-            gw2 = ops.expert_wgrad_packed(hid, dyp, lay, out_dtype=gdt)
+            gw2 = grad(ops.expert_wgrad_packed(hid, dyp, lay, **out(2)))
         if need_b2 and ctx.has_bias[1]:
-            gb2 = ops.expert_bgrad_packed(dyp, lay, out_dtype=gdt)
+            gb2 = grad(ops.expert_bgrad_packed(dyp, lay, **out(3)))
         if need_x or need_w1 or (need_b1 and ctx.has_bias[0]):
             dhid = ops.expert_gemm_packed(dyp, w2, None, True, lay, mul=(hid > 0).to(hid.dtype))
             if need_w1:
-                gw1 = ops.expert_wgrad_packed(dhid, x, lay, gather="b", zero_row=ctx.zero_row, out_dtype=gdt)
+                gw1 = grad(ops.expert_wgrad_packed(dhid, x, lay, gather="b", zero_row=ctx.zero_row, **out(0)))
             if need_b1 and ctx.has_bias[0]:
-                gb1 = ops.expert_bgrad_packed(dhid, lay, out_dtype=gdt)
+                gb1 = grad(ops.expert_bgrad_packed(dhid, lay, **out(1)))
             if need_x:
                 gx = ops.fast_decode_packed(ops.expert_gemm_packed(dhid, w1, None, False, lay), idx, loc, None, lay)
-        return gx, gg, gw1, gb1, gw2, gb2, None, None, None, None
+        return gx, gg, gw1, gb1, gw2, gb2, None, None, None, None, None
 
 
-
-def forward(layer, gate, x, logits, k, cf, alignment):
+def forward(layer, gate, x, logits, k, cf, alignment, main_grad=False):
     """One dropless training forward of `layer` on the packed layout: x [T, M], logits [T, E] (with autograd) -> (y [T, M_out], l_aux).
+    main_grad: the backward accumulates the expert gradients into the parameters' main_grad (main_grad_problem(layer) is None).
     Sets dispatch_count, dropless_capacity (device int32 [1]), dropless_offsets and protected_shape as the packed forward does."""
     ex = layer.experts
     T, E = logits.shape
@@ -162,8 +219,8 @@ def forward(layer, gate, x, logits, k, cf, alignment):
     lay = ops.packed_layout(cnt, idx2d, loc2d, limit, alignment, plan["rows_bound"], plan["tiles_bound"], plan["row_limit"])
     zero_row = torch.zeros([max(M, 8)], dtype=x.dtype, device=x.device)
     xc = x if x.is_contiguous() else x.contiguous()
-    y = _PackedFFNTrain.apply(xc, gates2d, ex.batched_fc1_w, ex.batched_fc1_bias, ex.batched_fc2_w, ex.batched_fc2_bias, lay, idx2d,
-                              loc2d, zero_row)
+    params = (ex.batched_fc1_w, ex.batched_fc1_bias, ex.batched_fc2_w, ex.batched_fc2_bias)
+    y = _PackedFFNTrain.apply(xc, gates2d, *params, lay, idx2d, loc2d, zero_row, params if main_grad else None)
     layer.dispatch_count = cnt
     layer.dropless_capacity = lay.capacity
     layer.dropless_offsets = lay.offsets

@@ -478,20 +478,41 @@ def _grad_out_dtype(out_dtype, operand_dtype):
     raise _lib.TutelAmdError(f"tutel_amd: the packed gradients come in the operands' dtype or torch.float32, not {out_dtype}")
 
 
-def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None, out_dtype=None):
+def _grad_acc_target(acc, numel, out_dtype, device, what):
+    """accumulate_into of the packed gradients: a contiguous fp32 tensor of `numel` elements on `device`, checked before any launch"""
+    if out_dtype is not None and out_dtype != torch.float32:
+        raise _lib.TutelAmdError(f"tutel_amd: {what}: accumulate_into is an fp32 sum, it does not go with out_dtype={out_dtype}")
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32:
+        raise _lib.TutelAmdError(f"tutel_amd: {what}: accumulate_into must be a torch.float32 tensor, not "
+                                 f"{acc.dtype if isinstance(acc, torch.Tensor) else type(acc).__name__}")
+    if acc.numel() != numel:
+        raise _lib.TutelAmdError(f"tutel_amd: {what}: accumulate_into has {acc.numel()} elements, the gradient {numel}")
+    if not acc.is_contiguous():
+        raise _lib.TutelAmdError(f"tutel_amd: {what}: accumulate_into must be contiguous")
+    if acc.device != device:
+        raise _lib.TutelAmdError(f"tutel_amd: {what}: accumulate_into is on {acc.device}, the operands on {device}")
+    return acc
+
+
+def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None, out_dtype=None, accumulate_into=None):
     """Weight gradient over the packed rows: D[e] = A[rows(e)]^T @ B[rows(e)] -> [E, N_a, N_b], fp32 sums in a fixed order.
     a [rows_bound, N_a], b [rows_bound, N_b]; gather="a" or "b": that operand is the token array [T, *] read through
     layout.slot_map (zero_row, >= 8 zeros, for pad rows).  out_dtype: None (the operands' dtype, rounded once) or torch.float32
-    (the same sums left unrounded: fp32 master weights under autocast)."""
+    (the same sums left unrounded: fp32 master weights under autocast).  accumulate_into: a contiguous fp32 tensor of E * N_a * N_b
+    elements on the operands' device (a main_grad): D += the fp32 sums in the kernel's epilogue, in place, and D is returned; an
+    expert without rows leaves its part untouched.  Not with a 16-bit out_dtype."""
+    if accumulate_into is not None:
+        assert a.dim() == 2 and b.dim() == 2
+        _grad_acc_target(accumulate_into, layout.E * a.shape[1] * b.shape[1], out_dtype, a.device, "expert_wgrad_packed")
     _dev(a, b)
     assert a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype
     assert gather in (None, "a", "b")
-    dt, sfx = _grad_out_dtype(out_dtype, a.dtype)
+    dt, sfx = _grad_out_dtype(out_dtype, a.dtype) if accumulate_into is None else (torch.float32, "_acc_f32")
     a, b = _a16(a), _a16(b)
     Na, Nb = a.shape[1], b.shape[1]
     g = {None: 0, "a": 1, "b": 2}[gather]
     T = (a if gather == "a" else b).shape[0] if gather else 0
-    out = torch.empty([layout.E, Na, Nb], dtype=dt, device=a.device)
+    out = torch.empty([layout.E, Na, Nb], dtype=dt, device=a.device) if accumulate_into is None else accumulate_into
     what = "tutel_amd_expert_wgrad_packed" + sfx
     _lib.check(getattr(_lib.lib(), what)(
         _ptr(a), Na, _ptr(b), Nb, _ptr(layout.slot_map) if g else None, g, T, _ptr(zero_row) if g else None,
@@ -499,12 +520,16 @@ def expert_wgrad_packed(a, b, layout, gather=None, zero_row=None, out_dtype=None
     return out
 
 
-def expert_bgrad_packed(b, layout, out_dtype=None):
-    """Bias gradient over the packed rows: D[e] = sum of b[rows(e)] -> [E, N] (out_dtype as expert_wgrad_packed's)."""
+def expert_bgrad_packed(b, layout, out_dtype=None, accumulate_into=None):
+    """Bias gradient over the packed rows: D[e] = sum of b[rows(e)] -> [E, N] (out_dtype and accumulate_into, here E * N fp32
+    elements, as expert_wgrad_packed's)."""
+    if accumulate_into is not None:
+        assert b.dim() == 2
+        _grad_acc_target(accumulate_into, layout.E * b.shape[1], out_dtype, b.device, "expert_bgrad_packed")
     _dev(b)
     assert b.dim() == 2 and b.is_contiguous()
-    dt, sfx = _grad_out_dtype(out_dtype, b.dtype)
-    out = torch.empty([layout.E, b.shape[1]], dtype=dt, device=b.device)
+    dt, sfx = _grad_out_dtype(out_dtype, b.dtype) if accumulate_into is None else (torch.float32, "_acc_f32")
+    out = torch.empty([layout.E, b.shape[1]], dtype=dt, device=b.device) if accumulate_into is None else accumulate_into
     what = "tutel_amd_expert_bgrad_packed" + sfx
     _lib.check(getattr(_lib.lib(), what)(_ptr(b), b.shape[1], _ptr(out), layout.E, b.shape[1], _code(b), _ptr(layout.offsets), _stream()), what)
     return out
