@@ -88,26 +88,21 @@ int tutel_decode_finish_launch(const void *buf, int dtype, const int32_t *idx, c
 // Packed dropless layout (dropless.hip).  Rows of the packed expert GEMMs per M-tile: a function of the shape alone (see
 // tutel_amd_packed_plan); the expert GEMM side (expert_gemm.hip) supports exactly this height.
 #define PK_TILE_ROWS 256
-// expert_gemm.hip: grouped GEMM over the packed layout, k-major weights.  Rows are global packed rows: A row r at A + r*lda
-// (a_rows != NULL: token a_rows[r] % T of A, -1 = zero_row), D row r at D + r*ldd.  Tile table tiles[2*i] = expert,
-// tiles[2*i+1] = first row; *ntiles live entries (device); off[E+1]: the experts' row ranges; cap: the device capacity (the
-// K-tile rotation follows it, so the bits are those of the padded launch).  Grid: tiles_bound x N-tiles.
-int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int64_t w_stride_e,
-                             int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
-                             int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
-                             hipStream_t st);
-// expert_gemm.hip: the same with the weight layout (w_kmajor 0: W[e] is [K][N], the register-staged kernel's transposing read) and an
-// optional gating operand `mul` with D's layout (D = act(A @ W + bias) * mul, the padded `mul=` form)
-int tutel_expert_gemm_packed_ex(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
-                                int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
-                                int rows_bound, int N, int K, int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles,
-                                const int32_t *cap, int tiles_bound, hipStream_t st);
+// The device tables of one packed launch: tiles[2*i] = expert, tiles[2*i+1] = first row of M-tile i; *ntiles live entries; off[E+1]:
+// the experts' row ranges; cap: the device capacity (the K-tile rotation follows it, so the bits are those of the padded launch).
+// tiles_bound (host) sizes the grid: tiles_bound x N-tiles.
+struct PackedTable { const int32_t *off, *tiles, *ntiles, *cap; int tiles_bound; };
+// expert_gemm.hip: grouped GEMM over the packed layout.  Rows are global packed rows: A row r at A + r*lda (a_rows != NULL: token
+// a_rows[r] % T of A, -1 = zero_row), D row r at D + r*ldd.  w_kmajor 0: W[e] is [K][N] (the register-staged kernel's transposing
+// read; act none or relu, no mul).  mul (optional): gating operand with D's layout, D = act(A @ W + bias) * mul.
+int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
+                             int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
+                             int rows_bound, int N, int K, int dtype, int act, const PackedTable &t, hipStream_t st);
 // expert_gemm.hip: the fused gate/up GEMM of a SwiGLU expert over the packed layout, D = round(act(A @ W_gate^T)) * (A @ W_up^T)
 // (tutel_amd_expert_gemm_gate_up's kernel); arguments as tutel_expert_gemm_packed, W_up with W_gate's strides, no bias
 int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,
                                      const void *W_up, int64_t w_stride_e, int ldw, void *D, int ldd, int E, int rows_bound, int N, int K,
-                                     int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap,
-                                     int tiles_bound, hipStream_t st);
+                                     int dtype, int act, const PackedTable &t, hipStream_t st);
 // dispatch.hip: fast_decode over the packed layout: row off[e] + loc, entries with loc >= row_limit dropped
 int tutel_decode_packed_launch(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype, int T,
                                int M, int k, int row_limit, const int32_t *off, void *out, hipStream_t st);

@@ -285,15 +285,16 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
                        m->alignment, pl.rows_bound, pl.tiles_bound, pk->offsets, tiles, ntiles, pk->capacity, slot);
     TUTEL_CHECK_LAUNCH("tutel_amd_moe_forward_packed (layout)");
   }
+  const PackedTable pt{pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound};
   if (w_up != nullptr)
     rc = tutel_expert_gemm_gate_up_packed(a.x, M, slot, T, a.zero_row, a.w1, w_up, (int64_t)H * M, M, hid, H, E, pl.rows_bound, H, M, a.dtype,
-                                          a.act, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
+                                          a.act, pt, st);
   else
-    rc = tutel_expert_gemm_packed(a.x, M, slot, T, a.zero_row, a.w1, (int64_t)H * M, M, a.b1, H, hid, H, E, pl.rows_bound, H, M, a.dtype,
-                                  a.act, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
+    rc = tutel_expert_gemm_packed(a.x, M, slot, T, a.zero_row, a.w1, 1, (int64_t)H * M, M, a.b1, H, nullptr, hid, H, E, pl.rows_bound, H, M,
+                                  a.dtype, a.act, pt, st);
   if (rc) return rc;
-  rc = tutel_expert_gemm_packed(hid, H, nullptr, 0, nullptr, a.w2, (int64_t)Mo * H, H, a.b2, Mo, outb, Mo, E, pl.rows_bound, Mo, H, a.dtype,
-                                TUTEL_ACT_NONE, pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound, st);
+  rc = tutel_expert_gemm_packed(hid, H, nullptr, 0, nullptr, a.w2, 1, (int64_t)Mo * H, H, a.b2, Mo, nullptr, outb, Mo, E, pl.rows_bound, Mo, H,
+                                a.dtype, TUTEL_ACT_NONE, pt, st);
   if (rc) return rc;
   return tutel_decode_packed_launch(outb, a.dtype, a.idx, a.loc, a.gates, m->logits_dtype, T, Mo, k, L, pk->offsets, a.y, st);
 }

@@ -262,11 +262,7 @@ static int ffn_cus() {
 }
 
 template <typename T, bool FL> static int ffn_launch_cfg(const FfnArgs &a, int grid, hipStream_t st) {
-  auto kern = expert_ffn_kernel<T, FL>;
-  if (!tutel_lds_optin((const void *)kern, ffn_lds_bytes<FL>())) return -1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(FFN_THREADS), ffn_lds_bytes<FL>(), st, a);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_ffn");
-  return 0;
+  return launch_lds(expert_ffn_kernel<T, FL>, grid, FFN_THREADS, ffn_lds_bytes<FL>(), st, a, "tutel_amd_expert_ffn");
 }
 
 // Does this pair of GEMMs take the persistent kernel?  The conditions under which launch_gemm (expert_gemm.hip) picks the 128 x 256
@@ -296,13 +292,22 @@ int tutel_expert_ffn(const void *X, int64_t x_stride_e, int ldx, const int32_t *
   if (mode <= 0) return TUTEL_AMD_ENOTSUP;
   if (E_loc <= 0 || R <= 0) return TUTEL_AMD_ENOTSUP;
   FfnArgs a;
-  const int rpw = R > 0 ? R : 1;
-  int rc = tutel_gemm_args(X, slot_map ? 0 : x_stride_e, 0, rpw, ldx, W1, 1, w1_stride_e, ldw1, b1, b1_stride_e, hid, hid_stride_e, 0, rpw, ldh,
-                           E_loc, R, H, M, dtype, act, nullptr, 1, slot_map, slot_map ? T : 0, slot_map ? zero_row : nullptr, nullptr, nullptr, 0,
-                           nullptr, idx8, n, loc, &a.g[0]);
+  GemmProblem fc1, fc2;  // X [R, M] -> hid [R, H] -> D [R, M_out], one rank of R rows each
+  fc1.A = X; fc1.a_stride_e = slot_map ? 0 : x_stride_e; fc1.lda = ldx;
+  fc1.W = W1; fc1.w_stride_e = w1_stride_e; fc1.ldw = ldw1; fc1.bias = b1; fc1.bias_stride_e = b1_stride_e;
+  fc1.D = hid; fc1.d_stride_e = hid_stride_e; fc1.ldd = ldh;
+  fc1.E_loc = E_loc; fc1.N = H; fc1.K = M; fc1.dtype = dtype;
+  gemm_one_rank(fc1, R);
+  gemm_gather(fc1, slot_map, T, slot_map ? zero_row : nullptr);
+  fc1.fl_idx8 = idx8; fc1.fl_n = n; fc1.fl_loc = loc;
+  int rc = tutel_gemm_args(fc1, &a.g[0]);
   if (rc != 0) return rc < 0 ? rc : TUTEL_AMD_ENOTSUP;
-  rc = tutel_gemm_args(hid, hid_stride_e, 0, rpw, ldh, W2, 1, w2_stride_e, ldw2, b2, b2_stride_e, D, d_stride_e, 0, rpw, ldd, E_loc, R, M_out, H,
-                       dtype, TUTEL_ACT_NONE, nullptr, 1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, &a.g[1]);
+  fc2.A = hid; fc2.a_stride_e = hid_stride_e; fc2.lda = ldh;
+  fc2.W = W2; fc2.w_stride_e = w2_stride_e; fc2.ldw = ldw2; fc2.bias = b2; fc2.bias_stride_e = b2_stride_e;
+  fc2.D = D; fc2.d_stride_e = d_stride_e; fc2.ldd = ldd;
+  fc2.E_loc = E_loc; fc2.N = M_out; fc2.K = H; fc2.dtype = dtype;
+  gemm_one_rank(fc2, R);
+  rc = tutel_gemm_args(fc2, &a.g[1]);
   if (rc != 0) return rc < 0 ? rc : TUTEL_AMD_ENOTSUP;
   const bool fl = idx8 != nullptr;
   if (!ffn_covers(a.g[0], a.g[1])) return TUTEL_AMD_ENOTSUP;

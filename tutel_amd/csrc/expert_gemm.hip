@@ -32,6 +32,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
 
@@ -39,7 +40,7 @@
 
 // Register-staged 128 x 128 kernel: K-tile depth 64, double-buffered LDS (one barrier per K-tile), 2 blocks per CU.
 // NT = non-temporal weight loads, ROT = K-tile rotation when the problem asks for it.
-// PACKED (its own instantiation): the packed dropless layout's tile table drives the grid (tutel_expert_gemm_packed_ex, n-major
+// PACKED (its own instantiation): the packed dropless layout's tile table drives the grid (tutel_expert_gemm_packed, n-major
 // weights): M-tile 2i + h of the launch is rows [pk_tiles[2i+1] + 128 h, +128) of expert pk_tiles[2i]; rows past the expert's
 // last row off[e+1] read that last row instead (never stored), so no row past off[E] is read.
 template <typename T, bool W_KMAJOR, int ACT, bool NT, bool ROT, bool PACKED = false>
@@ -59,18 +60,12 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
-  // ---- XCD-aware work order: consecutive work items (same expert, neighbouring tiles) go to
-  // the same XCD (hardware places block b on XCD b % 8; speed only, never correctness).
   int nb = gridDim.x;
   if (PACKED) {
     nb = min(nb, __builtin_amdgcn_readfirstlane(*p.pk_ntiles) * 2 * p.ntn);
     if ((int)blockIdx.x >= nb) return;
   }
-  int w;
-  {
-    const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int w = xcd_work_item(nb);
   int nt, e, m0, row_limit;
   bool rot_on = p.rot_on;
   if (PACKED) {
@@ -85,12 +80,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_kernel(GemmArgs p) 
     nt = (w / p.ntm) % p.ntn;
     e = w / (p.ntm * p.ntn);
     m0 = mt * GM_BM;
-    row_limit = p.R;
-    if (p.row_counts != nullptr) {
-      int c = p.row_counts[e];
-      c = (c + p.row_align - 1) / p.row_align * p.row_align;
-      row_limit = min(row_limit, c);
-    }
+    row_limit = padded_row_limit(p, e);
   }
   const int n0 = nt * GM_BN;
   if (m0 >= row_limit) return;
@@ -265,23 +255,13 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_glds_kernel(GemmArg
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
 
-  const int nb = gridDim.x;
-  int w;
-  {
-    const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int w = xcd_work_item(gridDim.x);
   const int mt = w % p.ntm;
   const int nt = (w / p.ntm) % p.ntn;
   const int e = w / (p.ntm * p.ntn);
   const int m0 = mt * GM_BM, n0 = nt * GM_BN;
 
-  int row_limit = p.R;
-  if (p.row_counts != nullptr) {
-    int c = p.row_counts[e];
-    c = (c + p.row_align - 1) / p.row_align * p.row_align;
-    row_limit = min(row_limit, c);
-  }
+  const int row_limit = padded_row_limit(p, e);
   if (m0 >= row_limit) return;
 
   const uint16_t *Ae = reinterpret_cast<const uint16_t *>(p.A) + (size_t)e * p.a_stride_e;
@@ -417,12 +397,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void expert_gemm_glds_kernel(GemmArg
 template <typename T, bool W_KMAJOR, int ACT, int NI, int NS, bool BUF = false, int BM = GB_BM, bool FL = false>
 __global__ __launch_bounds__(BM * 2, 2) void expert_gemm_big_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nb = gridDim.x;
-  int w;
-  {
-    const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int w = xcd_work_item(gridDim.x);
   gemm_big_tile<T, W_KMAJOR, ACT, NI, NS, BUF, BM, FL>(p, w / (p.ntm * p.ntn), w % p.ntm, (w / p.ntm) % p.ntn, smem);
 }
 
@@ -495,11 +470,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
     nb = min(nb, __builtin_amdgcn_readfirstlane(*p.pk_ntiles) * p.ntn);
     if ((int)blockIdx.x >= nb) return;
   }
-  int w;
-  {
-    const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  int w = xcd_work_item(nb);
   const int half = SPLITK ? (w & 1) : 0;  // which half of K this workgroup multiplies (and which 128-column group it finishes)
   if (SPLITK) w >>= 1;
   const int tile_id = w;
@@ -517,12 +488,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
     nt = (w / p.ntm) % p.ntn;
     e = w / (p.ntm * p.ntn);
     m0 = mt * GB_BM;
-    row_limit = p.R;
-    if (p.row_counts != nullptr) {
-      int c = p.row_counts[e];
-      c = (c + p.row_align - 1) / p.row_align * p.row_align;
-      row_limit = min(row_limit, c);
-    }
+    row_limit = padded_row_limit(p, e);
   }
   const int n0 = nt * (GATE_UP ? 128 : 256);
   if (m0 >= row_limit) return;
@@ -812,15 +778,14 @@ bool tutel_lds_optin(const void *kern, size_t lds) {
   return true;
 }
 
+// LDS of every ping-pong launch, 136 KB: the epilogue staging (8 waves x 64 rows x 272 B) > the two K-tile buffers (128 KB)
+static constexpr size_t PP_LDS_BYTES = (size_t)8 * 64 * EP_PITCH;
+static_assert(PP_LDS_BYTES >= (size_t)2 * PP_BUF * 2, "LDS request must cover the K-tile buffers");
+
 template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false>
 static int launch_pp_cfg(const GemmArgs &b, hipStream_t st) {
-  const size_t lds = (size_t)8 * 64 * EP_PITCH;  // 136 KB: the epilogue staging (8 waves x 64 rows x 272 B) > the two K-tile buffers (128 KB)
-  static_assert((size_t)8 * 64 * EP_PITCH >= (size_t)2 * PP_BUF * 2, "LDS request must cover the K-tile buffers");
-  auto kern = expert_gemm_pp_kernel<T, ACT, W_ONCE, RAGGED, EARLY_BIAS>;
-  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3(b.E_loc * b.ntm * b.ntn), dim3(GB_THREADS), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm");
-  return 0;
+  return launch_lds(expert_gemm_pp_kernel<T, ACT, W_ONCE, RAGGED, EARLY_BIAS>, b.E_loc * b.ntm * b.ntn, GB_THREADS, PP_LDS_BYTES, st, b,
+                    "tutel_amd_expert_gemm");
 }
 
 // ---- split-K launches: workspace per (device, stream) -------------------------------------------------------------------------
@@ -887,12 +852,8 @@ static int launch_pp_splitk(const GemmArgs &a, hipStream_t st) {
   if (a.row_counts != nullptr || a.R % GB_BM != 0 || (nk & 1) || nk < 8 || (tiles & 3) || a.rot_on) return 1;
   if ((a.ldd & 7) || (a.d_stride_e & 7) || (a.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(a.D) & 15)) return 1;
   if (!splitk_workspace(st, tiles, &b.sk_ws, &b.sk_flags)) return 1;
-  const size_t lds = (size_t)8 * 64 * EP_PITCH;
-  auto kern = expert_gemm_pp_kernel<T, ACT, false, false, false, true>;
-  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(2 * tiles)), dim3(GB_THREADS), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm");
-  return 0;
+  return launch_lds(expert_gemm_pp_kernel<T, ACT, false, false, false, true>, (unsigned)(2 * tiles), GB_THREADS, PP_LDS_BYTES, st, b,
+                    "tutel_amd_expert_gemm");
 }
 
 template <typename T, int ACT>
@@ -920,13 +881,9 @@ static int launch_pp_packed(const GemmArgs &a, int tiles_bound, hipStream_t st) 
   b.ntn = (a.N + 255) / 256;
   const long long grid = (long long)tiles_bound * b.ntn;
   TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_expert_gemm_packed: grid too large");
-  const size_t lds = (size_t)8 * 64 * EP_PITCH;
   auto kern = (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, true, true, false, false, true>
                                                  : expert_gemm_pp_kernel<T, ACT, false, true, false, false, true>;
-  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GB_THREADS), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_expert_gemm_packed");
-  return 0;
+  return launch_lds(kern, (unsigned)grid, GB_THREADS, PP_LDS_BYTES, st, b, "tutel_expert_gemm_packed");
 }
 
 // fused gate/up GEMM (GATE_UP ping-pong kernel): 256 x 128 output tiles, ntn = ceil(N / 128).  Padded: grid E_loc x M-tiles x N-tiles;
@@ -940,13 +897,9 @@ static int launch_gate_up(const GemmArgs &a, int tiles_bound, hipStream_t st) {
   b.ntn = (a.N + 127) / 128;
   const long long grid = PACKED ? (long long)tiles_bound * b.ntn : (long long)a.E_loc * b.ntm * b.ntn;
   TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_gate_up: grid too large");
-  const size_t lds = (size_t)8 * 64 * EP_PITCH;
   auto kern = PACKED && (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, PACKED, true, false, false, PACKED, true>
                                                           : expert_gemm_pp_kernel<T, ACT, false, true, false, false, PACKED, true>;
-  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GB_THREADS), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_gate_up");
-  return 0;
+  return launch_lds(kern, (unsigned)grid, GB_THREADS, PP_LDS_BYTES, st, b, "tutel_amd_expert_gemm_gate_up");
 }
 
 template <typename T, bool KM, int ACT, int NI, int NS = 2, bool BUF = false, int BM = GB_BM, bool FL = false>
@@ -956,19 +909,12 @@ static int launch_big(const GemmArgs &a, hipStream_t st) {
   b.ntn = (a.N + NI * 64 - 1) / (NI * 64);
   const size_t lds_k = (size_t)NS * (BM / 128 + NI / 2) * GL_STAGE * 2 + (FL ? 16384 : 0), lds_e = BUF ? (size_t)(BM / 32) * 64 * (NI * 64 + 16) : 0;
   const size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  auto kern = expert_gemm_big_kernel<T, KM, ACT, NI, NS, BUF, BM, FL>;
-  if (!tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3(a.E_loc * b.ntm * b.ntn), dim3(BM * 2), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm");
-  return 0;
+  return launch_lds(expert_gemm_big_kernel<T, KM, ACT, NI, NS, BUF, BM, FL>, a.E_loc * b.ntm * b.ntn, BM * 2, lds, st, b, "tutel_amd_expert_gemm");
 }
 
 template <typename T, bool KM, int ACT>
 static int launch_glds(const GemmArgs &a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((expert_gemm_glds_kernel<T, KM, ACT, true, true>), dim3(grid), dim3(GM_THREADS),
-                     (size_t)4 * GL_STAGE * 2, st, a);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm");
-  return 0;
+  return launch_lds(expert_gemm_glds_kernel<T, KM, ACT, true, true>, grid, GM_THREADS, (size_t)4 * GL_STAGE * 2, st, a, "tutel_amd_expert_gemm");
 }
 
 // -------------------------------------------------------------------------------------------
@@ -1000,12 +946,7 @@ static constexpr size_t gemm_lds_bytes(bool kmajor) {
 
 template <typename T, bool KM, int ACT>
 static int launch_cfg(const GemmArgs &a, int grid, hipStream_t st) {
-  const size_t lds = gemm_lds_bytes(KM);
-  auto kern = expert_gemm_kernel<T, KM, ACT, true, true>;
-  if (lds > 65536 && !tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(GM_THREADS), lds, st, a);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm");
-  return 0;
+  return launch_lds(expert_gemm_kernel<T, KM, ACT, true, true>, grid, GM_THREADS, gemm_lds_bytes(KM), st, a, "tutel_amd_expert_gemm");
 }
 
 // Kernel choice per weight layout, from on-hardware A/B at the headline shape and at R = 1024
@@ -1086,57 +1027,50 @@ static int launch_gemm(const GemmArgs &a, int grid, hipStream_t st) {
   return launch_cfg<T, KM, ACT>(a, grid, st);
 }
 
-template <typename T, bool KM>
-static int launch_gemm_act(const GemmArgs &a, int act, int grid, hipStream_t st) {
-  switch (act) {
-    case TUTEL_ACT_NONE: return launch_gemm<T, KM, TUTEL_ACT_NONE>(a, grid, st);
-    case TUTEL_ACT_RELU: return launch_gemm<T, KM, TUTEL_ACT_RELU>(a, grid, st);
-    case TUTEL_ACT_GELU: return launch_gemm<T, KM, TUTEL_ACT_GELU>(a, grid, st);
-    case TUTEL_ACT_SILU: return launch_gemm<T, KM, TUTEL_ACT_SILU>(a, grid, st);
-    default: tutel_set_error("tutel_amd_expert_gemm: unknown activation %d", act); return -1;
-  }
+// dtype x activation -> f(ElemTag<element type>, std::integral_constant<int, ACT>) for the activations listed in ACTS, the only ones
+// a site instantiates kernels for; any other activation answers other() -- each site's own error
+template <typename T> struct ElemTag { using type = T; };
+template <int... ACTS, typename F, typename Other>
+static int dispatch_dtype_act(int dtype, int act, F &&f, Other &&other) {
+  int rc = 0;
+  const bool hit = ((act == ACTS && ((rc = dtype == TUTEL_BF16 ? f(ElemTag<bf16_t>{}, std::integral_constant<int, ACTS>{})
+                                                                : f(ElemTag<f16_t>{}, std::integral_constant<int, ACTS>{})), true)) || ...);
+  return hit ? rc : other();
 }
 
 // Argument checks + the GemmArgs block of one grouped GEMM (shared with expert_ffn.hip, which runs two of them in one launch).
 // 0: *out is filled; 1: nothing to do (E_loc == 0 or R == 0); < 0: error (tutel_amd_last_error).
-int tutel_gemm_args(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W, int w_kmajor,
-                    int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e, int64_t d_stride_w,
-                    int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act, const int32_t *row_counts, int row_align,
-                    const int32_t *a_rows, int a_rows_mod, const void *a_zero, const void *mul, const uint64_t *d_peer, int64_t d_peer_off,
-                    const PeerCanary *d_can, const uint8_t *fl_idx8, int fl_n, int32_t *fl_loc, GemmArgs *out) {
-  (void)w_kmajor; (void)act;
-  TUTEL_REQUIRE(dtype == TUTEL_BF16 || dtype == TUTEL_F16, "tutel_amd_expert_gemm: dtype must be bf16 or fp16 (got %d)", dtype);
-  TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "tutel_amd_expert_gemm: bad sizes E_loc=%d R=%d N=%d K=%d", E_loc, R, N, K);
-  TUTEL_REQUIRE(K % 64 == 0, "tutel_amd_expert_gemm: K=%d must be a multiple of 64", K);
-  TUTEL_REQUIRE(N % 8 == 0, "tutel_amd_expert_gemm: N=%d must be a multiple of 8", N);
-  if (E_loc == 0 || R == 0) return 1;
-  TUTEL_REQUIRE(A && W && (D || d_peer), "tutel_amd_expert_gemm: null pointer");
-  TUTEL_REQUIRE(d_peer == nullptr || (mul == nullptr && d_peer_off % 16 == 0), "tutel_amd_expert_gemm: peer stores exclude the gated form");
-  TUTEL_REQUIRE(a_rows_per_w >= 1 && d_rows_per_w >= 1, "tutel_amd_expert_gemm: rows_per_w must be >= 1");
-  TUTEL_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldd % 4 == 0 && a_stride_e % 8 == 0 && a_stride_w % 8 == 0 &&
-                    w_stride_e % 8 == 0 && d_stride_e % 4 == 0 && d_stride_w % 4 == 0 && bias_stride_e % 4 == 0,
+int tutel_gemm_args(const GemmProblem &g, GemmArgs *out) {
+  TUTEL_REQUIRE(g.dtype == TUTEL_BF16 || g.dtype == TUTEL_F16, "tutel_amd_expert_gemm: dtype must be bf16 or fp16 (got %d)", g.dtype);
+  TUTEL_REQUIRE(g.E_loc >= 0 && g.R >= 0 && g.N >= 1 && g.K >= 1, "tutel_amd_expert_gemm: bad sizes E_loc=%d R=%d N=%d K=%d", g.E_loc, g.R, g.N, g.K);
+  TUTEL_REQUIRE(g.K % 64 == 0, "tutel_amd_expert_gemm: K=%d must be a multiple of 64", g.K);
+  TUTEL_REQUIRE(g.N % 8 == 0, "tutel_amd_expert_gemm: N=%d must be a multiple of 8", g.N);
+  if (g.E_loc == 0 || g.R == 0) return 1;
+  TUTEL_REQUIRE(g.A && g.W && (g.D || g.d_peer), "tutel_amd_expert_gemm: null pointer");
+  TUTEL_REQUIRE(g.d_peer == nullptr || (g.mul == nullptr && g.d_peer_off % 16 == 0), "tutel_amd_expert_gemm: peer stores exclude the gated form");
+  TUTEL_REQUIRE(g.a_rows_per_w >= 1 && g.d_rows_per_w >= 1, "tutel_amd_expert_gemm: rows_per_w must be >= 1");
+  TUTEL_REQUIRE(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldd % 4 == 0 && g.a_stride_e % 8 == 0 && g.a_stride_w % 8 == 0 &&
+                    g.w_stride_e % 8 == 0 && g.d_stride_e % 4 == 0 && g.d_stride_w % 4 == 0 && g.bias_stride_e % 4 == 0,
                 "tutel_amd_expert_gemm: leading dimensions / strides must keep rows 16-byte aligned");
-  TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)D % 8) == 0 && ((uintptr_t)bias % 8) == 0,
+  TUTEL_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && ((uintptr_t)g.D % 8) == 0 && ((uintptr_t)g.bias % 8) == 0,
                 "tutel_amd_expert_gemm: pointers must be 16-byte aligned");
-  TUTEL_REQUIRE(row_counts == nullptr || row_align >= 1, "tutel_amd_expert_gemm: row_align must be >= 1");
+  TUTEL_REQUIRE(g.row_counts == nullptr || g.row_align >= 1, "tutel_amd_expert_gemm: row_align must be >= 1");
 
   GemmArgs &a = *out;
-  a.A = A; a.a_stride_e = a_stride_e; a.a_stride_w = a_stride_w; a.a_rpw = a_rows_per_w; a.lda = lda;
-  a.W = W; a.w_stride_e = w_stride_e; a.ldw = ldw;
-  a.bias = bias; a.bias_stride_e = bias_stride_e;
-  a.D = D; a.d_stride_e = d_stride_e; a.d_stride_w = d_stride_w; a.d_rpw = d_rows_per_w; a.ldd = ldd;
-  a.E_loc = E_loc; a.R = R; a.N = N; a.K = K;
-  a.row_counts = row_counts; a.row_align = row_align < 1 ? 1 : row_align;
-  a.a_rows = a_rows; a.a_rows_mod = a_rows_mod; a.a_zero = a_zero;
+  a.A = g.A; a.a_stride_e = g.a_stride_e; a.a_stride_w = g.a_stride_w; a.a_rpw = g.a_rows_per_w; a.lda = g.lda;
+  a.W = g.W; a.w_stride_e = g.w_stride_e; a.ldw = g.ldw; a.bias = g.bias; a.bias_stride_e = g.bias_stride_e;
+  a.D = g.D; a.d_stride_e = g.d_stride_e; a.d_stride_w = g.d_stride_w; a.d_rpw = g.d_rows_per_w; a.ldd = g.ldd;
+  a.E_loc = g.E_loc; a.R = g.R; a.N = g.N; a.K = g.K; a.row_counts = g.row_counts; a.row_align = g.row_align < 1 ? 1 : g.row_align;
+  a.a_rows = g.a_rows; a.a_rows_mod = g.a_rows_mod; a.a_zero = g.a_zero;
   a.a_span_bytes = 0;
   bool fits32 = true;  // the ping-pong kernel addresses rows with 32-bit byte offsets from the operand bases
   {
-    const long long span = a_rows != nullptr ? (long long)a_rows_mod * lda * 2
-                                             : ((long long)((R - 1) / a_rows_per_w) * a_stride_w + (long long)a_rows_per_w * lda) * 2;
+    const long long span = g.a_rows != nullptr ? (long long)g.a_rows_mod * g.lda * 2
+                                               : ((long long)((g.R - 1) / g.a_rows_per_w) * g.a_stride_w + (long long)g.a_rows_per_w * g.lda) * 2;
     fits32 = span < 0x7ffff000LL;
     a.a_span_bytes = (int)span;
   }
-  fits32 = fits32 && ((long long)N * ldw + K) * 2 < 0xffffff00LL;
+  fits32 = fits32 && ((long long)g.N * g.ldw + g.K) * 2 < 0xffffff00LL;
   a.fits32 = fits32;
   // K-tile rotation (each block starts its K loop at a different tile) is a property of the PROBLEM, not of the kernel
   // that runs it, so every kernel produces the same bits for a given problem:
@@ -1146,74 +1080,66 @@ int tutel_gemm_args(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a
   //   R >= 256 (full 256-row tiles, operands re-read through L2): OFF -- blocks that share a token tile then walk it
   //     together and the later ones hit in L2 (ping-pong kernel 65.7 -> 62.6 us at 8 x 1024 x 2048 x 2048, 242 -> 224 at
   //     4096^2, 85 -> 79 at 32 x 256 rows).
-  a.rot_on = R < GB_BM;
-  a.sgather = tutel_get_option(TUTEL_OPT_GEMM_GATHER) != 0 && (long long)E_loc * R * 4 < 0x7fffffffLL;
+  a.rot_on = g.R < GB_BM;
+  a.sgather = tutel_get_option(TUTEL_OPT_GEMM_GATHER) != 0 && (long long)g.E_loc * g.R * 4 < 0x7fffffffLL;
   {  // store policy of the LDS epilogue; the descriptor form needs every byte offset inside an expert's output below 2^31
     const int ds = tutel_get_option(TUTEL_OPT_GEMM_STORE);
-    const long long span = ((long long)((R - 1) / d_rows_per_w) * (d_stride_w < 0 ? -d_stride_w : d_stride_w) + (long long)(d_rows_per_w < R ? d_rows_per_w : R) * ldd + N) * 2;
+    const long long span = ((long long)((g.R - 1) / g.d_rows_per_w) * (g.d_stride_w < 0 ? -g.d_stride_w : g.d_stride_w) +
+                            (long long)(g.d_rows_per_w < g.R ? g.d_rows_per_w : g.R) * g.ldd + g.N) * 2;
     a.d_store = (ds == 0 || span >= 0x7fffffffLL) ? 0 : (ds == 2 ? 2 : 1);   // automatic: write-through
-    if (d_peer != nullptr) {  // peer rows: write-through only (a non-temporal hint means nothing to a peer's memory), one source rank per store instruction
-      const long long pspan = ((long long)E_loc * d_stride_e + (long long)d_rows_per_w * ldd + N) * 2;
-      a.d_store = (ds != 0 && d_rows_per_w % 8 == 0 && pspan < 0x7fffffffLL) ? 1 : 0;
+    if (g.d_peer != nullptr) {  // peer rows: write-through only (a non-temporal hint means nothing to a peer's memory), one source rank per store instruction
+      const long long pspan = ((long long)g.E_loc * g.d_stride_e + (long long)g.d_rows_per_w * g.ldd + g.N) * 2;
+      a.d_store = (ds != 0 && g.d_rows_per_w % 8 == 0 && pspan < 0x7fffffffLL) ? 1 : 0;
     }
   }
-  a.mul = mul;
-  a.fl_idx8 = fl_idx8; a.fl_n = fl_n; a.fl_loc = fl_loc;
-  a.d_peer = d_peer; a.d_peer_off = d_peer_off;
-  a.d_can = d_can != nullptr ? *d_can : PeerCanary{nullptr, 0, 0, 0};
-  TUTEL_REQUIRE(((uintptr_t)mul % 8) == 0, "tutel_amd_expert_gemm_glu: gating operand must be 8-byte aligned");
-  TUTEL_REQUIRE(a_rows == nullptr || (a_rows_mod >= 1 && a_zero != nullptr && ((uintptr_t)a_zero % 16) == 0),
+  a.mul = g.mul;
+  a.fl_idx8 = g.fl_idx8; a.fl_n = g.fl_n; a.fl_loc = g.fl_loc;
+  a.d_peer = g.d_peer; a.d_peer_off = g.d_peer_off;
+  a.d_can = g.d_can != nullptr ? *g.d_can : PeerCanary{nullptr, 0, 0, 0};
+  TUTEL_REQUIRE(((uintptr_t)g.mul % 8) == 0, "tutel_amd_expert_gemm_glu: gating operand must be 8-byte aligned");
+  TUTEL_REQUIRE(g.a_rows == nullptr || (g.a_rows_mod >= 1 && g.a_zero != nullptr && ((uintptr_t)g.a_zero % 16) == 0),
                 "tutel_amd_expert_gemm_gather: need a_rows_mod >= 1 and a 16-byte aligned zero row");
-  a.ntm = (R + GM_BM - 1) / GM_BM;
-  a.ntn = (N + GM_BN - 1) / GM_BN;
+  a.ntm = (g.R + GM_BM - 1) / GM_BM;
+  a.ntn = (g.N + GM_BN - 1) / GM_BN;
   a.pk_off = a.pk_tiles = a.pk_ntiles = a.pk_cap = nullptr;
   a.w_up = nullptr;
   return 0;
 }
 
-static int expert_gemm_impl(const void *A, int64_t a_stride_e, int64_t a_stride_w,
-                                     int a_rows_per_w, int lda, const void *W, int w_kmajor,
-                                     int64_t w_stride_e, int ldw, const void *bias,
-                                     int64_t bias_stride_e, void *D, int64_t d_stride_e,
-                                     int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc,
-                                     int R, int N, int K, int dtype, int act,
-                                     const int32_t *row_counts, int row_align,
-                                     const int32_t *a_rows, int a_rows_mod, const void *a_zero,
-                                     const void *mul, tutel_stream_t stream, const uint64_t *d_peer = nullptr,
-                                     int64_t d_peer_off = 0, const PeerCanary *d_can = nullptr, const uint8_t *fl_idx8 = nullptr,
-                                     int fl_n = 0, int32_t *fl_loc = nullptr) {
+static int expert_gemm_impl(const GemmProblem &g, int w_kmajor, int act, tutel_stream_t stream) {
   GemmArgs a;
-  const int brc = tutel_gemm_args(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, D, d_stride_e,
-                                  d_stride_w, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, row_counts, row_align, a_rows, a_rows_mod, a_zero, mul,
-                                  d_peer, d_peer_off, d_can, fl_idx8, fl_n, fl_loc, &a);
+  const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
-  long long grid_ll = (long long)E_loc * a.ntm * a.ntn;
+  long long grid_ll = (long long)g.E_loc * a.ntm * a.ntn;
   TUTEL_REQUIRE(grid_ll < 0x7fffffffLL, "tutel_amd_expert_gemm: grid too large");
   const int grid = (int)grid_ll;
   hipStream_t st = (hipStream_t)stream;
+  auto go = [&]() -> int {
+    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+        g.dtype, act,
+        [&](auto t, auto ac) {
+          using T = typename decltype(t)::type;
+          return w_kmajor ? launch_gemm<T, true, decltype(ac)::value>(a, grid, st) : launch_gemm<T, false, decltype(ac)::value>(a, grid, st);
+        },
+        [&] { tutel_set_error("tutel_amd_expert_gemm: unknown activation %d", act); return -1; });
+  };
+  if (g.fl_idx8 != nullptr && g.fl_loc == nullptr) return go();  // eligibility query of the fused-location path: nothing is launched, nothing timed
   // per-stage timing: the launch with a fused activation is fc1, the one without is fc2 (callers that know better --
   // the native pipeline -- set a hint)
-  auto go = [&]() -> int {
-    if (dtype == TUTEL_BF16)
-      return w_kmajor ? launch_gemm_act<bf16_t, true>(a, act, grid, st) : launch_gemm_act<bf16_t, false>(a, act, grid, st);
-    return w_kmajor ? launch_gemm_act<f16_t, true>(a, act, grid, st) : launch_gemm_act<f16_t, false>(a, act, grid, st);
-  };
-  if (fl_idx8 != nullptr && fl_loc == nullptr) return go();  // eligibility query of the fused-location path: nothing is launched, nothing timed
   StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
   return go();
 }
 
-extern "C" int tutel_amd_expert_gemm(const void *A, int64_t a_stride_e, int64_t a_stride_w,
-                                     int a_rows_per_w, int lda, const void *W, int w_kmajor,
-                                     int64_t w_stride_e, int ldw, const void *bias,
-                                     int64_t bias_stride_e, void *D, int64_t d_stride_e,
-                                     int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc,
-                                     int R, int N, int K, int dtype, int act,
-                                     const int32_t *row_counts, int row_align,
-                                     tutel_stream_t stream) {
-  return expert_gemm_impl(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_kmajor, w_stride_e, ldw, bias,
-                          bias_stride_e, D, d_stride_e, d_stride_w, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act,
-                          row_counts, row_align, nullptr, 0, nullptr, nullptr, stream);
+extern "C" int tutel_amd_expert_gemm(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W, int w_kmajor,
+                                     int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e,
+                                     int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
+                                     const int32_t *row_counts, int row_align, tutel_stream_t stream) {
+  GemmProblem g;
+  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
+  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  return expert_gemm_impl(g, w_kmajor, act, stream);
 }
 
 int tutel_expert_gemm_peer(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
@@ -1221,9 +1147,13 @@ int tutel_expert_gemm_peer(const void *A, int64_t a_stride_e, int64_t a_stride_w
                            const uint64_t *d_peer, int64_t d_peer_off, int64_t d_stride_e, int d_rows_per_w, int ldd, int E_loc,
                            int R, int N, int K, int dtype, int act, const PeerCanary &can, hipStream_t st) {
   TUTEL_REQUIRE(d_peer != nullptr, "tutel_expert_gemm_peer: null peer table");
-  return expert_gemm_impl(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, nullptr,
-                          d_stride_e, 0, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, nullptr, 1, nullptr, 0, nullptr, nullptr,
-                          (tutel_stream_t)st, d_peer, d_peer_off, &can);
+  GemmProblem g;
+  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.d_stride_e = d_stride_e; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
+  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype;
+  g.d_peer = d_peer; g.d_peer_off = d_peer_off; g.d_can = &can;
+  return expert_gemm_impl(g, w_kmajor, act, (tutel_stream_t)st);
 }
 
 // tutel_amd_expert_gemm_gather with the locations computed INSIDE the launch (see the FL comment at expert_gemm_big_kernel): the
@@ -1234,46 +1164,61 @@ int tutel_expert_gemm_gather_fl(const void *X, int ldx, int32_t *slot_map, int T
                                 int N, int K, int dtype, int act, const uint8_t *idx8, int n, int32_t *loc, hipStream_t st) {
   TUTEL_REQUIRE(slot_map != nullptr && idx8 != nullptr && T >= 1 && ((uintptr_t)idx8 & 15) == 0, "tutel_expert_gemm_gather_fl: bad arguments");
   if (tutel_get_option(TUTEL_OPT_FUSED_LOCATION) == 0) return TUTEL_AMD_ENOTSUP;
-  return expert_gemm_impl(X, 0, 0, R > 0 ? R : 1, ldx, W, 1, w_stride_e, ldw, bias, bias_stride_e, D, d_stride_e, 0, R > 0 ? R : 1, ldd, E_loc,
-                          R, N, K, dtype, act, nullptr, 1, slot_map, T, zero_row, nullptr, (tutel_stream_t)st, nullptr, 0, nullptr, idx8, n, loc);
+  GemmProblem g;
+  g.A = X; g.lda = ldx;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.d_stride_e = d_stride_e; g.ldd = ldd;
+  g.E_loc = E_loc; g.N = N; g.K = K; g.dtype = dtype;
+  gemm_one_rank(g, R);
+  gemm_gather(g, slot_map, T, zero_row);
+  g.fl_idx8 = idx8; g.fl_n = n; g.fl_loc = loc;
+  return expert_gemm_impl(g, 1, act, (tutel_stream_t)st);
 }
 
-extern "C" int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w,
-                                         int a_rows_per_w, int lda, const void *W, int w_kmajor,
-                                         int64_t w_stride_e, int ldw, const void *bias,
-                                         int64_t bias_stride_e, const void *G, void *D, int64_t d_stride_e,
-                                         int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc,
-                                         int R, int N, int K, int dtype, int act,
-                                         const int32_t *row_counts, int row_align,
-                                         tutel_stream_t stream) {
+extern "C" int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
+                                         int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *G, void *D,
+                                         int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype,
+                                         int act, const int32_t *row_counts, int row_align, tutel_stream_t stream) {
   TUTEL_REQUIRE(G != nullptr || E_loc == 0 || R == 0, "tutel_amd_expert_gemm_glu: null gating operand");
-  return expert_gemm_impl(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_kmajor, w_stride_e, ldw, bias,
-                          bias_stride_e, D, d_stride_e, d_stride_w, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act,
-                          row_counts, row_align, nullptr, 0, nullptr, G, stream);
+  GemmProblem g;
+  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
+  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  g.mul = G;
+  return expert_gemm_impl(g, w_kmajor, act, stream);
 }
 
-extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_t *slot_map, int T,
-                                            const void *zero_row, const void *W, int w_kmajor,
-                                            int64_t w_stride_e, int ldw, const void *bias,
-                                            int64_t bias_stride_e, void *D, int64_t d_stride_e, int ldd,
-                                            int E_loc, int R, int N, int K, int dtype, int act,
-                                            const int32_t *row_counts, int row_align,
+extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_t *slot_map, int T, const void *zero_row, const void *W, int w_kmajor,
+                                            int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e,
+                                            int ldd, int E_loc, int R, int N, int K, int dtype, int act, const int32_t *row_counts, int row_align,
                                             tutel_stream_t stream) {
   TUTEL_REQUIRE(slot_map != nullptr && T >= 1, "tutel_amd_expert_gemm_gather: need a slot map and T >= 1");
-  return expert_gemm_impl(X, 0, 0, R > 0 ? R : 1, ldx, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, D,
-                          d_stride_e, 0, R > 0 ? R : 1, ldd, E_loc, R, N, K, dtype, act, row_counts, row_align,
-                          slot_map, T, zero_row, nullptr, stream);
+  GemmProblem g;
+  g.A = X; g.lda = ldx;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.d_stride_e = d_stride_e; g.ldd = ldd;
+  g.E_loc = E_loc; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  gemm_one_rank(g, R);
+  gemm_gather(g, slot_map, T, zero_row);
+  return expert_gemm_impl(g, w_kmajor, act, stream);
 }
 
-// internal (common.h): the grouped GEMM over the packed dropless layout (dropless.hip).  Rows are global packed rows of ONE array per
-// operand (stride between experts 0, one "rank" of rows_bound rows), so the kernel's row addressing, the out-of-range zero rows and
-// the row limit work unchanged; what changes per block is where its tile, expert and row limit come from (the device tile table).
-int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int64_t w_stride_e,
-                             int ldw, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
-                             int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap, int tiles_bound,
-                             hipStream_t st) {
-  return tutel_expert_gemm_packed_ex(A, lda, a_rows, T, zero_row, W, 1, w_stride_e, ldw, bias, bias_stride_e, nullptr, D, ldd, E, rows_bound, N,
-                                     K, dtype, act, off, tiles, ntiles, cap, tiles_bound, st);
+// ---- the packed dropless layout (dropless.hip) ---------------------------------------------------------------------------------------
+// Rows are global packed rows of ONE array per operand (stride between experts 0, one "rank" of rows_bound rows), so the kernel's row
+// addressing, the out-of-range zero rows and the row limit work unchanged; what changes per block is where its tile, expert and row
+// limit come from (the device tile table).  What the plain and the gate/up entry points share: the table's checks, and the problem's
+// row layout + the GemmArgs block with the table in it (W, bias, mul, D, the sizes and the dtype are the caller's to fill in g).
+static int packed_table_check(const char *what, const PackedTable &t, int rows_bound, const int32_t *a_rows, int T) {
+  TUTEL_REQUIRE(t.off && t.tiles && t.ntiles && t.cap && t.tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1), "%s: bad arguments", what);
+  return 0;
+}
+static int packed_gemm_args(GemmProblem &g, int rows_bound, const int32_t *a_rows, int T, const void *zero_row, const PackedTable &t, GemmArgs *a) {
+  gemm_one_rank(g, rows_bound);
+  gemm_gather(g, a_rows, T, zero_row);
+  const int brc = tutel_gemm_args(g, a);
+  if (brc == 0) { a->pk_off = t.off; a->pk_tiles = t.tiles; a->pk_ntiles = t.ntiles; a->pk_cap = t.cap; }
+  return brc;
 }
 
 // n-major weights over the packed layout: the register-staged 128 x 128 kernel (its transposing LDS read takes W [K][N] as stored),
@@ -1285,46 +1230,36 @@ static int launch_packed_nmajor(const GemmArgs &a, int tiles_bound, hipStream_t 
   b.ntn = (a.N + GM_BN - 1) / GM_BN;
   const long long grid = (long long)tiles_bound * 2 * b.ntn;
   TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_packed: grid too large");
-  const size_t lds = gemm_lds_bytes(false);
-  auto kern = expert_gemm_kernel<T, false, ACT, true, true, true>;
-  if (lds > 65536 && !tutel_lds_optin((const void *)kern, lds)) return -1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GM_THREADS), lds, st, b);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_packed");
-  return 0;
+  return launch_lds(expert_gemm_kernel<T, false, ACT, true, true, true>, (unsigned)grid, GM_THREADS, gemm_lds_bytes(false), st, b,
+                    "tutel_amd_expert_gemm_packed");
 }
 
-int tutel_expert_gemm_packed_ex(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
-                                int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
-                                int rows_bound, int N, int K, int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles,
-                                const int32_t *cap, int tiles_bound, hipStream_t st) {
-  TUTEL_REQUIRE(off && tiles && ntiles && cap && tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1),
-                "tutel_expert_gemm_packed: bad arguments");
+// internal (common.h): the grouped GEMM over the packed layout
+int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
+                             int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
+                             int rows_bound, int N, int K, int dtype, int act, const PackedTable &t, hipStream_t st) {
+  if (packed_table_check("tutel_expert_gemm_packed", t, rows_bound, a_rows, T) != 0) return -1;
+  GemmProblem g;
+  g.A = A; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.ldd = ldd;
+  g.E_loc = E; g.N = N; g.K = K; g.dtype = dtype;
+  g.mul = mul;
   GemmArgs a;
-  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, D, 0, 0, rows_bound, ldd, E,
-                                  rows_bound, N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, mul, nullptr, 0, nullptr,
-                                  nullptr, 0, nullptr, &a);
+  const int brc = packed_gemm_args(g, rows_bound, a_rows, T, zero_row, t, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   if (!a.fits32) {
     tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
     return TUTEL_AMD_ENOTSUP;
   }
-  a.pk_off = off; a.pk_tiles = tiles; a.pk_ntiles = ntiles; a.pk_cap = cap;
   StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
-  const bool bf = dtype == TUTEL_BF16;
-  if (!w_kmajor) {
-    switch (act) {
-      case TUTEL_ACT_NONE: return bf ? launch_packed_nmajor<bf16_t, TUTEL_ACT_NONE>(a, tiles_bound, st) : launch_packed_nmajor<f16_t, TUTEL_ACT_NONE>(a, tiles_bound, st);
-      case TUTEL_ACT_RELU: return bf ? launch_packed_nmajor<bf16_t, TUTEL_ACT_RELU>(a, tiles_bound, st) : launch_packed_nmajor<f16_t, TUTEL_ACT_RELU>(a, tiles_bound, st);
-      default: tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP;
-    }
-  }
-  switch (act) {
-    case TUTEL_ACT_NONE: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_NONE>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_NONE>(a, tiles_bound, st);
-    case TUTEL_ACT_RELU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_RELU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_RELU>(a, tiles_bound, st);
-    case TUTEL_ACT_GELU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_GELU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_GELU>(a, tiles_bound, st);
-    case TUTEL_ACT_SILU: return bf ? launch_pp_packed<bf16_t, TUTEL_ACT_SILU>(a, tiles_bound, st) : launch_pp_packed<f16_t, TUTEL_ACT_SILU>(a, tiles_bound, st);
-    default: tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1;
-  }
+  if (!w_kmajor)
+    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(
+        dtype, act, [&](auto e, auto ac) { return launch_packed_nmajor<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
+        [&] { tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP; });
+  return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+      dtype, act, [&](auto e, auto ac) { return launch_pp_packed<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
+      [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
 }
 
 // ---- fused gate/up GEMM of a SwiGLU expert (GATE_UP ping-pong kernel) -------------------------------------------------------------
@@ -1335,24 +1270,24 @@ static int gate_up_notsup(const char *why) {
 
 template <bool PACKED>
 static int gate_up_act(const GemmArgs &a, int dtype, int act, int tiles_bound, hipStream_t st) {
-  const bool bf = dtype == TUTEL_BF16;
-  switch (act) {
-    case TUTEL_ACT_RELU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_RELU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_RELU, PACKED>(a, tiles_bound, st);
-    case TUTEL_ACT_GELU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_GELU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_GELU, PACKED>(a, tiles_bound, st);
-    case TUTEL_ACT_SILU: return bf ? launch_gate_up<bf16_t, TUTEL_ACT_SILU, PACKED>(a, tiles_bound, st) : launch_gate_up<f16_t, TUTEL_ACT_SILU, PACKED>(a, tiles_bound, st);
-    default: return gate_up_notsup("the gate activation must be relu, gelu or silu");
-  }
+  return dispatch_dtype_act<TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+      dtype, act, [&](auto e, auto ac) { return launch_gate_up<typename decltype(e)::type, decltype(ac)::value, PACKED>(a, tiles_bound, st); },
+      [] { return gate_up_notsup("the gate activation must be relu, gelu or silu"); });
 }
+static bool gate_up_act_ok(int act) { return act == TUTEL_ACT_RELU || act == TUTEL_ACT_GELU || act == TUTEL_ACT_SILU; }
 
 extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
                                              const void *W_gate, const void *W_up, int64_t w_stride_e, int ldw, void *D, int64_t d_stride_e,
                                              int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
                                              const int32_t *row_counts, int row_align, tutel_stream_t stream) {
-  if (act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  if (!gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  GemmProblem g;
+  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
+  g.W = W_gate; g.w_stride_e = w_stride_e; g.ldw = ldw;
+  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
+  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
   GemmArgs a;
-  const int brc = tutel_gemm_args(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W_gate, 1, w_stride_e, ldw, nullptr, 0, D, d_stride_e, d_stride_w,
-                                  d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, row_counts, row_align, nullptr, 0, nullptr, nullptr, nullptr, 0,
-                                  nullptr, nullptr, 0, nullptr, &a);
+  const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_amd_expert_gemm_gate_up: W_up must be a 16-byte aligned pointer");
   if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
@@ -1366,21 +1301,21 @@ extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, 
 // internal (common.h): the same over the packed dropless layout, arguments as tutel_expert_gemm_packed plus W_up
 int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,
                                      const void *W_up, int64_t w_stride_e, int ldw, void *D, int ldd, int E, int rows_bound, int N, int K,
-                                     int dtype, int act, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, const int32_t *cap,
-                                     int tiles_bound, hipStream_t st) {
-  TUTEL_REQUIRE(off && tiles && ntiles && cap && tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1),
-                "tutel_expert_gemm_gate_up_packed: bad arguments");
-  if (act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+                                     int dtype, int act, const PackedTable &t, hipStream_t st) {
+  if (packed_table_check("tutel_expert_gemm_gate_up_packed", t, rows_bound, a_rows, T) != 0) return -1;
+  if (!gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  GemmProblem g;
+  g.A = A; g.lda = lda;
+  g.W = W_gate; g.w_stride_e = w_stride_e; g.ldw = ldw;
+  g.D = D; g.ldd = ldd;
+  g.E_loc = E; g.N = N; g.K = K; g.dtype = dtype;
   GemmArgs a;
-  const int brc = tutel_gemm_args(A, 0, 0, rows_bound, lda, W_gate, 1, w_stride_e, ldw, nullptr, 0, D, 0, 0, rows_bound, ldd, E, rows_bound,
-                                  N, K, dtype, act, nullptr, 1, a_rows, a_rows != nullptr ? T : 0, zero_row, nullptr, nullptr, 0, nullptr, nullptr,
-                                  0, nullptr, &a);
+  const int brc = packed_gemm_args(g, rows_bound, a_rows, T, zero_row, t, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
   if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
   if ((ldd & 7) || ((uintptr_t)D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
   a.w_up = W_up;
-  a.pk_off = off; a.pk_tiles = tiles; a.pk_ntiles = ntiles; a.pk_cap = cap;
   StageScope stage(TUTEL_STAGE_FC1, st);
-  return gate_up_act<true>(a, dtype, act, tiles_bound, st);
+  return gate_up_act<true>(a, dtype, act, t.tiles_bound, st);
 }

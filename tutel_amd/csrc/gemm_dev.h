@@ -10,15 +10,45 @@
 #define GEMM_PROBE(i)
 #endif
 
+// One grouped GEMM as its callers state it, D[e, r, :] = act(A[e, r, :] @ op(W[e]) + bias[e, :]) [* mul]: the operands of the C ABI
+// (include/tutel_amd.h) plus the internal forms.  Callers assign the fields they mean to a local; the rest keep these defaults.
+struct GemmProblem {
+  const void *A = nullptr; int64_t a_stride_e = 0, a_stride_w = 0; int a_rows_per_w = 0, lda = 0;
+  const void *W = nullptr; int64_t w_stride_e = 0; int ldw = 0;
+  const void *bias = nullptr; int64_t bias_stride_e = 0;
+  void *D = nullptr; int64_t d_stride_e = 0, d_stride_w = 0; int d_rows_per_w = 0, ldd = 0;
+  int E_loc = 0, R = 0, N = 0, K = 0;
+  int dtype = -1;
+  const int32_t *row_counts = nullptr; int row_align = 1;
+  const int32_t *a_rows = nullptr; int a_rows_mod = 0; const void *a_zero = nullptr;  // row r of A is token a_rows[r] % a_rows_mod (-1: a_zero)
+  const void *mul = nullptr;
+  const uint64_t *d_peer = nullptr; int64_t d_peer_off = 0; const PeerCanary *d_can = nullptr;
+  const uint8_t *fl_idx8 = nullptr; int fl_n = 0; int32_t *fl_loc = nullptr;
+};
+// A and D hold one rank of R rows per expert (no [W, E_loc, C, M] permute folded into the row addressing)
+static inline void gemm_one_rank(GemmProblem &g, int R) {
+  g.R = R;
+  g.a_rows_per_w = g.d_rows_per_w = R > 0 ? R : 1;
+}
+// A's rows come through a slot map over T token rows (fused fast_encode); slot_map == NULL: no gather
+static inline void gemm_gather(GemmProblem &g, const int32_t *slot_map, int T, const void *zero_row) {
+  g.a_rows = slot_map; g.a_rows_mod = slot_map != nullptr ? T : 0; g.a_zero = zero_row;
+}
+
 struct GemmArgs;
 // host side, expert_gemm.hip: argument checks + the GemmArgs block of one grouped GEMM (0: filled, 1: empty problem, < 0: error);
 // the > 64 KB dynamic-LDS opt-in per (kernel, device)
-int tutel_gemm_args(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W, int w_kmajor,
-                    int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e, int64_t d_stride_w,
-                    int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act, const int32_t *row_counts, int row_align,
-                    const int32_t *a_rows, int a_rows_mod, const void *a_zero, const void *mul, const uint64_t *d_peer, int64_t d_peer_off,
-                    const PeerCanary *d_can, const uint8_t *fl_idx8, int fl_n, int32_t *fl_loc, GemmArgs *out);
+int tutel_gemm_args(const GemmProblem &g, GemmArgs *out);
 bool tutel_lds_optin(const void *kern, size_t lds);
+
+// one launch with `lds` bytes of dynamic LDS: the opt-in (needed above 64 KB only), the launch, the launch check
+template <typename Kern, typename Args>
+static int launch_lds(Kern kern, unsigned grid, int threads, size_t lds, hipStream_t st, const Args &args, const char *what) {
+  if (lds > 65536 && !tutel_lds_optin((const void *)kern, lds)) return -1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, args);
+  TUTEL_CHECK_LAUNCH(what);
+  return 0;
+}
 
 #define GM_BM 128
 #define GM_BN 128
@@ -185,6 +215,24 @@ __device__ __forceinline__ void gather_rows4(const GemmArgs &p, int e, const int
     const int q0 = m[gr[0]], q1 = m[gr[1]], q2 = m[gr[2]], q3 = m[gr[3]];
     q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3;
   }
+}
+
+// XCD-aware work order: block b of nb -> work item, so that consecutive work items (same expert, neighbouring tiles) go to the same
+// XCD and share its L2 (hardware places block b on XCD b % 8; speed only, never correctness)
+__device__ __forceinline__ int xcd_work_item(int nb) {
+  const int b = blockIdx.x, q = nb >> 3, r = nb & 7, xcd = b & 7, pos = b >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+}
+
+// rows of expert e that a padded launch computes: R, or row_counts[e] rounded up to row_align when that is less
+__device__ __forceinline__ int padded_row_limit(const GemmArgs &p, int e) {
+  int row_limit = p.R;
+  if (p.row_counts != nullptr) {
+    int c = p.row_counts[e];
+    c = (c + p.row_align - 1) / p.row_align * p.row_align;
+    row_limit = min(row_limit, c);
+  }
+  return row_limit;
 }
 
 // streamed-once weight loads may bypass cache allocation (each W byte is read by exactly one CU)
@@ -414,12 +462,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
   const int m0 = mt * BM, n0 = nt * BN;
   GEMM_PROBE(0);
 
-  int row_limit = p.R;
-  if (p.row_counts != nullptr) {
-    int c = p.row_counts[e];
-    c = (c + p.row_align - 1) / p.row_align * p.row_align;
-    row_limit = min(row_limit, c);
-  }
+  const int row_limit = padded_row_limit(p, e);
   if (m0 >= row_limit) {
     tail();
     return;

@@ -285,7 +285,7 @@ extern "C" int tutel_amd_expert_bgrad_packed_acc_f32(const void *B, int ldb, flo
   return bgrad_packed("tutel_amd_expert_bgrad_packed_acc_f32", true, true, B, ldb, D, E, N, dtype, offsets, stream);
 }
 
-// the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed_ex (expert_gemm.hip).  N is any multiple of 8
+// the grouped GEMM over the packed layout, public form of tutel_expert_gemm_packed (expert_gemm.hip).  N is any multiple of 8
 // from 8 up (tutel_gemm_args refuses the rest before a launch): below the plan's 128 columns both kernels clamp every weight, bias
 // and gating-operand load of a column tile into [0, N) and store whole 8-column groups below N only (include/tutel_amd.h)
 extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W,
@@ -310,6 +310,6 @@ extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_
   TUTEL_REQUIRE(offsets && tiles && ntiles && capacity, "tutel_amd_expert_gemm_packed: null pointer");
   TUTEL_REQUIRE(((uintptr_t)D & 15) == 0 && ldd % 8 == 0 && ((uintptr_t)mul & 15) == 0,
                 "tutel_amd_expert_gemm_packed: D and mul must be 16-byte aligned, ldd a multiple of 8");
-  return tutel_expert_gemm_packed_ex(A, lda, a_rows, T, zero_row, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, mul, D, ldd, E, rows_bound,
-                                     N, K, dtype, act, offsets, tiles, ntiles, capacity, tiles_bound, (hipStream_t)stream);
+  return tutel_expert_gemm_packed(A, lda, a_rows, T, zero_row, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, mul, D, ldd, E, rows_bound, N, K,
+                                  dtype, act, PackedTable{offsets, tiles, ntiles, capacity, tiles_bound}, (hipStream_t)stream);
 }
