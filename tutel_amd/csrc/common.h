@@ -62,24 +62,42 @@ struct EncodePeer {
 int tutel_encode_launch(const void *x, int dtype, const int32_t *slot_map, const void *gates, int gate_dtype, int T, int M,
                         int n_slots, int capacity, int num_experts, int chunk_rows, int expert_slice, int ep_world, void *out,
                         const EncodePeer &peer, hipStream_t st);
-// tutel_amd_expert_gemm with the output rows of source rank w written to d_peer[w] + d_peer_off (bytes) instead of
-// D + w * d_stride_w: the second expert GEMM stores straight into the return buffers of the ranks the rows came from
-int tutel_expert_gemm_peer(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
-                           int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e,
-                           const uint64_t *d_peer, int64_t d_peer_off, int64_t d_stride_e, int d_rows_per_w, int ldd, int E_loc,
-                           int R, int N, int K, int dtype, int act, const PeerCanary &can, hipStream_t st);
-
-// expert_gemm.hip: the gather GEMM with the locations computed inside the launch (fused location); loc == NULL: eligibility query
-int tutel_expert_gemm_gather_fl(const void *X, int ldx, int32_t *slot_map, int T, const void *zero_row, const void *W, int64_t w_stride_e,
-                                int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e, int ldd, int E_loc, int R,
-                                int N, int K, int dtype, int act, const uint8_t *idx8, int n, int32_t *loc, hipStream_t st);
-// expert_ffn.hip: fc1 -> activation -> fc2 in one persistent launch.  idx8 != NULL: fused location (loc out).  query != 0: answers only.
-// TUTEL_AMD_ENOTSUP: this shape / layout takes the two-launch path (nothing was launched)
-int tutel_expert_ffn(const void *X, int64_t x_stride_e, int ldx, const int32_t *slot_map, int T, const void *zero_row, const void *W1,
-                     int64_t w1_stride_e, int ldw1, const void *b1, int64_t b1_stride_e, void *hid, int64_t hid_stride_e, int ldh,
-                     const void *W2, int64_t w2_stride_e, int ldw2, const void *b2, int64_t b2_stride_e, void *D, int64_t d_stride_e, int ldd,
-                     int E_loc, int R, int M, int H, int M_out, int dtype, int act, const uint8_t *idx8, int n, int32_t *loc, int query,
-                     hipStream_t st);
+// One grouped GEMM as its callers state it, D[e, r, :] = act(A[e, r, :] @ op(W[e]) + bias[e, :]) [* mul]: the operands of the C ABI
+// (include/tutel_amd.h) plus the internal forms.  Everyone who wants a GEMM -- the C-ABI entry points and the pipelines of ep.hip and
+// dropless.hip alike -- assigns the fields it means to a local and hands that over; the rest keep these defaults.  (The struct lives
+// here, not in gemm_dev.h, so that the pipelines can fill it without pulling in the MFMA templates.)
+struct GemmProblem {
+  const void *A = nullptr; int64_t a_stride_e = 0, a_stride_w = 0; int a_rows_per_w = 0, lda = 0;
+  const void *W = nullptr; int64_t w_stride_e = 0; int ldw = 0;
+  const void *bias = nullptr; int64_t bias_stride_e = 0;
+  void *D = nullptr; int64_t d_stride_e = 0, d_stride_w = 0; int d_rows_per_w = 0, ldd = 0;
+  int E_loc = 0, R = 0, N = 0, K = 0;
+  int dtype = -1;
+  const int32_t *row_counts = nullptr; int row_align = 1;
+  const int32_t *a_rows = nullptr; int a_rows_mod = 0; const void *a_zero = nullptr;  // row r of A is token a_rows[r] % a_rows_mod (-1: a_zero)
+  const void *mul = nullptr;
+  // peer stores (IPC transport, ep.hip): the output rows of source rank w go to d_peer[w] + d_peer_off (bytes) instead of D + w * d_stride_w
+  // -- the second expert GEMM stores straight into the return buffers of the ranks the rows came from; d_can: canaries behind the rows
+  const uint64_t *d_peer = nullptr; int64_t d_peer_off = 0; const PeerCanary *d_can = nullptr;
+  // fused location (see the FL comment at gemm_big_tile): the kernel fills a_rows [E_loc * R] and fl_loc [fl_n] itself from fl_idx8 [fl_n]
+  // (fl_n = k * T bytes, buffer padded to 16).  fl_loc == NULL: eligibility query
+  const uint8_t *fl_idx8 = nullptr; int fl_n = 0; int32_t *fl_loc = nullptr;
+};
+// A and D hold one rank of R rows per expert (no [W, E_loc, C, M] permute folded into the row addressing)
+static inline void gemm_one_rank(GemmProblem &g, int R) {
+  g.R = R;
+  g.a_rows_per_w = g.d_rows_per_w = R > 0 ? R : 1;
+}
+// A's rows come through a slot map over T token rows (fused fast_encode); slot_map == NULL: no gather
+static inline void gemm_gather(GemmProblem &g, const int32_t *slot_map, int T, const void *zero_row) {
+  g.a_rows = slot_map; g.a_rows_mod = slot_map != nullptr ? T : 0; g.a_zero = zero_row;
+}
+// expert_gemm.hip: one grouped GEMM, every form (what tutel_amd_expert_gemm and its _glu / _gather siblings run after their own checks).
+// A fused-location query (fl_idx8 set, fl_loc NULL) launches nothing: 0 = this shape takes the fused kernel, TUTEL_AMD_ENOTSUP = not
+int tutel_expert_gemm(const GemmProblem &g, int w_kmajor, int act, hipStream_t st);
+// expert_ffn.hip: fc1 -> activation -> fc2 in one persistent launch (fc2.A is fc1.D; fc1 may carry the gather and the fused-location
+// fields).  query != 0: answers only.  TUTEL_AMD_ENOTSUP: this shape / layout takes the two-launch path (nothing was launched)
+int tutel_expert_ffn(const GemmProblem &fc1, const GemmProblem &fc2, int act, int query, hipStream_t st);
 // dispatch.hip: fast_decode + the routing finish (routing_dev.h) in one launch
 struct RouteFinish;
 void tutel_route_finish_args(int T, int E, int k, void *ws, RouteFinish *out);  // routing.hip
@@ -92,17 +110,13 @@ int tutel_decode_finish_launch(const void *buf, int dtype, const int32_t *idx, c
 // the experts' row ranges; cap: the device capacity (the K-tile rotation follows it, so the bits are those of the padded launch).
 // tiles_bound (host) sizes the grid: tiles_bound x N-tiles.
 struct PackedTable { const int32_t *off, *tiles, *ntiles, *cap; int tiles_bound; };
-// expert_gemm.hip: grouped GEMM over the packed layout.  Rows are global packed rows: A row r at A + r*lda (a_rows != NULL: token
-// a_rows[r] % T of A, -1 = zero_row), D row r at D + r*ldd.  w_kmajor 0: W[e] is [K][N] (the register-staged kernel's transposing
-// read; act none or relu, no mul).  mul (optional): gating operand with D's layout, D = act(A @ W + bias) * mul.
-int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
-                             int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
-                             int rows_bound, int N, int K, int dtype, int act, const PackedTable &t, hipStream_t st);
-// expert_gemm.hip: the fused gate/up GEMM of a SwiGLU expert over the packed layout, D = round(act(A @ W_gate^T)) * (A @ W_up^T)
-// (tutel_amd_expert_gemm_gate_up's kernel); arguments as tutel_expert_gemm_packed, W_up with W_gate's strides, no bias
-int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,
-                                     const void *W_up, int64_t w_stride_e, int ldw, void *D, int ldd, int E, int rows_bound, int N, int K,
-                                     int dtype, int act, const PackedTable &t, hipStream_t st);
+// expert_gemm.hip: grouped GEMM over the packed layout.  Rows are global packed rows of one rank of g.R = rows_bound rows (gemm_one_rank,
+// gemm_gather): A row r at A + r*lda (a_rows != NULL: token a_rows[r] % T of A, -1 = zero row), D row r at D + r*ldd, no expert strides.
+// w_kmajor 0: W[e] is [K][N] (the register-staged kernel's transposing read; act none or relu, no mul).  g.mul (optional): gating
+// operand with D's layout, D = act(A @ W + bias) * mul.
+// w_up != NULL: the fused gate/up GEMM of a SwiGLU expert instead, D = round(act(A @ W^T)) * (A @ W_up^T) (tutel_amd_expert_gemm_gate_up's
+// kernel): W_up with W's strides, k-major, no bias, no mul
+int tutel_expert_gemm_packed(const GemmProblem &g, int w_kmajor, int act, const PackedTable &t, const void *w_up, hipStream_t st);
 // dispatch.hip: fast_decode over the packed layout: row off[e] + loc, entries with loc >= row_limit dropped
 int tutel_decode_packed_launch(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype, int T,
                                int M, int k, int row_limit, const int32_t *off, void *out, hipStream_t st);
@@ -111,6 +125,10 @@ int tutel_decode_packed_launch(const void *buf, int dtype, const int32_t *idx, c
 int tutel_gate_topk_launch(const void *in, const float *partials, int splits, int dtype, int T, int E, int k, int normalize_gate,
                            void *logits_out, int32_t *idx, void *gates, void *ws, int32_t *clear_map, int clear_n, uint8_t *idx8,
                            hipStream_t st);
+// ep.hip: the routing launches of the one-call forwards (ep.hip, dropless.hip), after the caller's own checks: the gate projection and
+// the top-k on its partial sums (splits > 0) or the top-k on m.logits, then the locations.  slot_map != NULL: cleared and filled for
+// m.ep.capacity rows per expert; NULL (dropless): the capacity is not known yet
+int tutel_route_launch(const tutel_amd_moe_args_t &m, int splits, int32_t *slot_map, tutel_stream_t stream);
 
 #define TUTEL_REQUIRE(cond, ...)           \
   do {                                     \

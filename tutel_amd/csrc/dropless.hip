@@ -262,39 +262,31 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
   w += pk_align((size_t)pl.rows_bound * H * 2);
   void *outb = w;
 
-  if (project) {
-    rc = tutel_amd_gate_proj(a.x, m->gate_w, a.dtype, T, M, E, m->gate_partials, m->gate_partial_bytes, stream);
-    if (rc) return rc;
-    rc = tutel_amd_gate_topk_partials(m->gate_partials, splits, a.dtype, T, E, k, m->normalize_gate, m->logits_out, nullptr,
-                                      const_cast<int32_t *>(a.idx), const_cast<void *>(a.gates), m->ws, m->ws_bytes, nullptr, 0, stream);
-  } else {
-    rc = tutel_amd_gate_topk(m->logits, m->logits_dtype, 1, T, E, k, m->normalize_gate, nullptr, const_cast<int32_t *>(a.idx),
-                             const_cast<void *>(a.gates), m->ws, m->ws_bytes, nullptr, 0, stream);
-  }
-  if (rc) return rc;
-  rc = tutel_amd_compute_location(a.idx, T, E, k, 1, m->ws, m->ws_bytes, const_cast<int32_t *>(a.loc), m->dispatch_count, m->stats, m->l_aux,
-                                  m->logits_dtype, 0, nullptr, 0, stream);
+  rc = tutel_route_launch(*m, splits, nullptr, stream);
   if (rc) return rc;
   const int L = pl.row_limit > 0 ? pl.row_limit : INT_MAX;
   {
     StageScope sc(TUTEL_STAGE_OTHER, st);
-    const long long work = (long long)k * T > pl.rows_bound ? (long long)k * T : pl.rows_bound;
-    long long grid = (work + 4 * LY_THREADS - 1) / (4 * LY_THREADS);
-    grid = grid < 1 ? 1 : (grid > 256 ? 256 : grid);
-    hipLaunchKernelGGL(packed_layout_kernel, dim3((unsigned)grid), dim3(LY_THREADS), 0, st, m->dispatch_count, a.idx, a.loc, k * T, E, L,
-                       m->alignment, pl.rows_bound, pl.tiles_bound, pk->offsets, tiles, ntiles, pk->capacity, slot);
+    launch_layout(m->dispatch_count, a.idx, a.loc, T, E, k, L, m->alignment, pl.rows_bound, pl.tiles_bound, pk->offsets, tiles, ntiles,
+                  pk->capacity, slot, st);
     TUTEL_CHECK_LAUNCH("tutel_amd_moe_forward_packed (layout)");
   }
   const PackedTable pt{pk->offsets, tiles, ntiles, pk->capacity, pl.tiles_bound};
-  if (w_up != nullptr)
-    rc = tutel_expert_gemm_gate_up_packed(a.x, M, slot, T, a.zero_row, a.w1, w_up, (int64_t)H * M, M, hid, H, E, pl.rows_bound, H, M, a.dtype,
-                                          a.act, pt, st);
-  else
-    rc = tutel_expert_gemm_packed(a.x, M, slot, T, a.zero_row, a.w1, 1, (int64_t)H * M, M, a.b1, H, nullptr, hid, H, E, pl.rows_bound, H, M,
-                                  a.dtype, a.act, pt, st);
+  GemmProblem fc1, fc2;  // x [T, M] gathered through the packed slot map -> hid [rows, H] -> outb [rows, M_out]
+  fc1.A = a.x; fc1.lda = M;
+  fc1.W = a.w1; fc1.w_stride_e = (int64_t)H * M; fc1.ldw = M; fc1.bias = a.b1; fc1.bias_stride_e = H;
+  fc1.D = hid; fc1.ldd = H;
+  fc1.E_loc = E; fc1.N = H; fc1.K = M; fc1.dtype = a.dtype;
+  gemm_one_rank(fc1, pl.rows_bound);
+  gemm_gather(fc1, slot, T, a.zero_row);
+  rc = tutel_expert_gemm_packed(fc1, 1, a.act, pt, w_up, st);
   if (rc) return rc;
-  rc = tutel_expert_gemm_packed(hid, H, nullptr, 0, nullptr, a.w2, 1, (int64_t)Mo * H, H, a.b2, Mo, nullptr, outb, Mo, E, pl.rows_bound, Mo, H,
-                                a.dtype, TUTEL_ACT_NONE, pt, st);
+  fc2.A = hid; fc2.lda = H;
+  fc2.W = a.w2; fc2.w_stride_e = (int64_t)Mo * H; fc2.ldw = H; fc2.bias = a.b2; fc2.bias_stride_e = Mo;
+  fc2.D = outb; fc2.ldd = Mo;
+  fc2.E_loc = E; fc2.N = Mo; fc2.K = H; fc2.dtype = a.dtype;
+  gemm_one_rank(fc2, pl.rows_bound);
+  rc = tutel_expert_gemm_packed(fc2, 1, TUTEL_ACT_NONE, pt, nullptr, st);
   if (rc) return rc;
   return tutel_decode_packed_launch(outb, a.dtype, a.idx, a.loc, a.gates, m->logits_dtype, T, Mo, k, L, pk->offsets, a.y, st);
 }

@@ -795,6 +795,50 @@ extern "C" int tutel_amd_ep_plan(int E, int W, int capacity, int degree, int all
   return 0;
 }
 
+// ---- the expert stage of the single-rank routes ------------------------------------------------------------------------------
+// fc1 of a single rank without a bucket array: X [T, M] gathered through the slot map (fast_encode fused) -> hid [E, C, H], with the
+// megablocks row counts where the caller gave some.  idx8 != NULL: fused location, the kernel works out the slot map and `loc` [n]
+// itself (loc == NULL: the eligibility query)
+static GemmProblem stage_fc1(const tutel_amd_ep_args_t &a, const uint8_t *idx8, int n, int32_t *loc) {
+  GemmProblem g;
+  g.A = a.x; g.lda = a.M;
+  g.W = a.w1; g.w_stride_e = (int64_t)a.H * a.M; g.ldw = a.M; g.bias = a.b1; g.bias_stride_e = a.H;
+  g.D = a.hid; g.d_stride_e = (int64_t)a.capacity * a.H; g.ldd = a.H;
+  g.E_loc = a.num_experts; g.N = a.H; g.K = a.M; g.dtype = a.dtype;
+  g.row_counts = a.row_counts; g.row_align = a.row_counts != nullptr && a.row_align >= 1 ? a.row_align : 1;
+  gemm_one_rank(g, a.capacity);
+  gemm_gather(g, a.slot_map, a.T, a.zero_row);
+  g.fl_idx8 = idx8; g.fl_n = n; g.fl_loc = loc;
+  return g;
+}
+// fc1 -> activation -> fc2 into a.send [E, C, M_out]: one persistent launch where the shape takes it (expert_ffn.hip), else the two
+// GEMM launches.  fc2's problem is looked at only after fc1 has been enqueued.  idx8 != NULL: fc1 with the fused location
+static int expert_stage(const tutel_amd_ep_args_t &a, const uint8_t *idx8, int n, hipStream_t st) {
+  const int C = a.capacity, H = a.H, Mo = a.M_out;
+  const GemmProblem fc1 = stage_fc1(a, idx8, n, idx8 != nullptr ? const_cast<int32_t *>(a.loc) : nullptr);
+  GemmProblem fc2;
+  fc2.A = a.hid; fc2.a_stride_e = (int64_t)C * H; fc2.lda = H;
+  fc2.W = a.w2; fc2.w_stride_e = (int64_t)H * Mo; fc2.ldw = a.w2_kmajor ? H : Mo; fc2.bias = a.b2; fc2.bias_stride_e = Mo;
+  fc2.D = a.send; fc2.d_stride_e = (int64_t)C * Mo; fc2.ldd = Mo;
+  fc2.E_loc = a.num_experts; fc2.N = Mo; fc2.K = H; fc2.dtype = a.dtype;
+  fc2.row_counts = fc1.row_counts; fc2.row_align = fc1.row_align;
+  gemm_one_rank(fc2, C);
+  int rc = TUTEL_AMD_ENOTSUP;
+  if (a.row_counts == nullptr && a.w2_kmajor) {
+    Range r("tutel_amd.expert_ffn");
+    rc = tutel_expert_ffn(fc1, fc2, a.act, 0, st);
+    if (rc != 0 && rc != TUTEL_AMD_ENOTSUP) return rc;
+  }
+  if (rc == TUTEL_AMD_ENOTSUP) {
+    Range r("tutel_amd.expert_fc1");
+    rc = tutel_expert_gemm(fc1, 1, a.act, st);
+    if (rc) return rc;
+    Range r2("tutel_amd.expert_fc2");
+    rc = tutel_expert_gemm(fc2, a.w2_kmajor, TUTEL_ACT_NONE, st);
+  }
+  return rc;
+}
+
 // ---- the pipeline ---------------------------------------------------------------------------------------------
 extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_args_t *a, tutel_stream_t stream) {
   TUTEL_REQUIRE(a != nullptr, "tutel_amd_ep_forward: null arguments");
@@ -814,8 +858,6 @@ extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_a
   const void *dec_gates = a->is_postscore ? a->gates : nullptr;
   TUTEL_REQUIRE(a->gates != nullptr || T == 0, "tutel_amd_ep_forward: null gates");
   TUTEL_REQUIRE(a->row_counts == nullptr || (W == 1 && c == nullptr && a->degree <= 1), "tutel_amd_ep_forward: row counts (megablocks) need a single rank");
-  const int32_t *rcnt = a->row_counts;
-  const int ralign = a->row_counts != nullptr && a->row_align >= 1 ? a->row_align : 1;
 
   if (C == 0) {  // nothing is dispatched (on any rank: the capacity is agreed): every token's output is the zero vector
     if (T > 0) HIP_CHECK(hipMemsetAsync(a->y, 0, (size_t)T * Mo * es, cur), "hipMemsetAsync");
@@ -825,30 +867,15 @@ extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_a
   // single rank, no communicator, pure-copy encode: fc1 gathers its rows from the tokens (no bucket array at all)
   if (c == nullptr && a->degree <= 1 && a->is_postscore && a->fuse_encode) {
     TUTEL_REQUIRE(a->hid && a->send && a->zero_row, "tutel_amd_ep_forward: null workspace");
-    int rc = TUTEL_AMD_ENOTSUP;
-    if (rcnt == nullptr && a->w2_kmajor) {  // fc1 -> activation -> fc2 in one persistent launch where the shape takes it (expert_ffn.hip)
-      Range r("tutel_amd.expert_ffn");
-      rc = tutel_expert_ffn(a->x, 0, M, a->slot_map, T, a->zero_row, a->w1, (int64_t)H * M, M, a->b1, H, a->hid, (int64_t)C * H, H, a->w2,
-                            (int64_t)H * Mo, H, a->b2, Mo, a->send, (int64_t)C * Mo, Mo, E_loc, C, M, H, Mo, a->dtype, a->act, nullptr, 0, nullptr, 0, cur);
-      if (rc != 0 && rc != TUTEL_AMD_ENOTSUP) return rc;
-    }
-    if (rc == TUTEL_AMD_ENOTSUP) {
-      Range r("tutel_amd.expert_fc1");
-      rc = tutel_amd_expert_gemm_gather(a->x, M, a->slot_map, T, a->zero_row, a->w1, 1, (int64_t)H * M, M, a->b1, H, a->hid,
-                                        (int64_t)C * H, H, E_loc, C, H, M, a->dtype, a->act, rcnt, ralign, cur);
-      if (rc) return rc;
-      Range r2("tutel_amd.expert_fc2");
-      rc = tutel_amd_expert_gemm(a->hid, (int64_t)C * H, 0, C, H, a->w2, a->w2_kmajor, (int64_t)H * Mo, a->w2_kmajor ? H : Mo, a->b2,
-                                 Mo, a->send, (int64_t)C * Mo, 0, C, Mo, E_loc, C, Mo, H, a->dtype, TUTEL_ACT_NONE, rcnt, ralign, cur);
-      if (rc) return rc;
-    }
+    const int rc = expert_stage(*a, nullptr, 0, cur);
+    if (rc) return rc;
     Range r("tutel_amd.fast_decode");
     return tutel_amd_fast_decode(a->send, a->dtype, a->idx, a->loc, dec_gates, a->gate_dtype, T, Mo, k, C, E, 0, 0, 1, a->y, cur);
   }
 
   const bool ipc = a->peer_seg != nullptr;
   TUTEL_REQUIRE(a->recv && a->hid && a->back && (ipc || (a->enc && a->send)), "tutel_amd_ep_forward: null workspace");
-  TUTEL_REQUIRE(rcnt == nullptr, "tutel_amd_ep_forward: row counts need the fused-encode single-rank route (is_postscore, fuse_encode)");
+  TUTEL_REQUIRE(a->row_counts == nullptr, "tutel_amd_ep_forward: row counts need the fused-encode single-rank route (is_postscore, fuse_encode)");
   const int degree = a->degree < 1 ? 1 : a->degree;
   tutel_amd_ep_plan_t pl;
   if (tutel_amd_ep_plan(E, W, C, degree, a->allow_sliced, &pl) != 0) return -1;
@@ -877,23 +904,30 @@ extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_a
     const int e0 = pl.sliced ? i * s : 0;  // first local expert of the stage
     const char *w1 = (const char *)a->w1 + (size_t)e0 * H * M * es, *w2 = (const char *)a->w2 + (size_t)e0 * H * Mo * es;
     const char *b1 = a->b1 ? (const char *)a->b1 + (size_t)e0 * H * es : nullptr, *b2 = a->b2 ? (const char *)a->b2 + (size_t)e0 * Mo * es : nullptr;
-    int r1;
+    GemmProblem fc1, fc2;
+    fc1.A = recv_i; fc1.a_stride_e = (int64_t)cc * M; fc1.a_stride_w = (int64_t)rows * M; fc1.a_rows_per_w = cc; fc1.lda = M;
+    fc1.W = w1; fc1.w_stride_e = (int64_t)H * M; fc1.ldw = M; fc1.bias = b1; fc1.bias_stride_e = H;
+    fc1.D = hid_i; fc1.d_stride_e = (int64_t)R * H; fc1.d_rows_per_w = R; fc1.ldd = H;
+    fc1.E_loc = s; fc1.R = R; fc1.N = H; fc1.K = M; fc1.dtype = a->dtype;
     {
       Range r("tutel_amd.expert_fc1");
       tutel_stage_hint(TUTEL_STAGE_FC1);
-      r1 = tutel_amd_expert_gemm(recv_i, (int64_t)cc * M, (int64_t)rows * M, cc, M, w1, 1, (int64_t)H * M, M, b1, H, hid_i,
-                                 (int64_t)R * H, 0, R, H, s, R, H, M, a->dtype, a->act, nullptr, 1, st);
+      const int r1 = tutel_expert_gemm(fc1, 1, a->act, st);
       tutel_stage_hint(-1);
       if (r1) return r1;
     }
     Range r("tutel_amd.expert_fc2");
-    if (ipc)  // rows of source rank w go straight to block <my rank> of stage i of rank w's return array
-      return tutel_expert_gemm_peer(hid_i, (int64_t)R * H, 0, R, H, w2, a->w2_kmajor, (int64_t)H * Mo, a->w2_kmajor ? H : Mo, b2, Mo, seg->tab_dev,
-                                    back_off + (long long)(((size_t)i * W + c->rank) * rows * Mo * es), (int64_t)cc * Mo, cc, Mo, s, R, Mo, H, a->dtype,
-                                    TUTEL_ACT_NONE, producer_canary(c, seg, 1, i), st);
-    char *send_i = (char *)a->send + (size_t)i * msg_out;
-    return tutel_amd_expert_gemm(hid_i, (int64_t)R * H, 0, R, H, w2, a->w2_kmajor, (int64_t)H * Mo, a->w2_kmajor ? H : Mo, b2, Mo, send_i,
-                                 (int64_t)cc * Mo, (int64_t)rows * Mo, cc, Mo, s, R, Mo, H, a->dtype, TUTEL_ACT_NONE, nullptr, 1, st);
+    fc2.A = hid_i; fc2.a_stride_e = (int64_t)R * H; fc2.a_rows_per_w = R; fc2.lda = H;
+    fc2.W = w2; fc2.w_stride_e = (int64_t)H * Mo; fc2.ldw = a->w2_kmajor ? H : Mo; fc2.bias = b2; fc2.bias_stride_e = Mo;
+    fc2.d_stride_e = (int64_t)cc * Mo; fc2.d_rows_per_w = cc; fc2.ldd = Mo;
+    fc2.E_loc = s; fc2.R = R; fc2.N = Mo; fc2.K = H; fc2.dtype = a->dtype;
+    const PeerCanary can = producer_canary(ipc ? c : nullptr, seg, 1, i);  // (fc2.d_can points at it: it must outlive the call)
+    if (ipc) {  // rows of source rank w go straight to block <my rank> of stage i of rank w's return array
+      fc2.d_peer = seg->tab_dev; fc2.d_peer_off = back_off + (long long)(((size_t)i * W + c->rank) * rows * Mo * es); fc2.d_can = &can;
+    } else {
+      fc2.D = (char *)a->send + (size_t)i * msg_out; fc2.d_stride_w = (int64_t)rows * Mo;
+    }
+    return tutel_expert_gemm(fc2, a->w2_kmajor, TUTEL_ACT_NONE, st);
   };
   // stage i's bucket rows: plain launch into `enc`, or (IPC) peer stores into the owners' receive arrays
   auto encode_stage = [&](int i, int nst) -> int {
@@ -1045,6 +1079,25 @@ extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_a
 }
 
 // ---- routing + pipeline in one call ------------------------------------------------------------------------------
+// internal (common.h): the routing launches both one-call forwards (this one and dropless.hip's packed one) make after their own checks
+int tutel_route_launch(const tutel_amd_moe_args_t &m, int splits, int32_t *slot_map, tutel_stream_t stream) {
+  const tutel_amd_ep_args_t &a = m.ep;
+  const int T = a.T, E = a.num_experts, k = a.k, clear_n = slot_map != nullptr ? E * a.capacity : 0;
+  int rc;
+  if (splits > 0) {  // the gate projection inside the call (gate_proj.hip)
+    rc = tutel_amd_gate_proj(a.x, m.gate_w, a.dtype, T, a.M, E, m.gate_partials, m.gate_partial_bytes, stream);
+    if (rc) return rc;
+    rc = tutel_amd_gate_topk_partials(m.gate_partials, splits, a.dtype, T, E, k, m.normalize_gate, m.logits_out, nullptr,
+                                      const_cast<int32_t *>(a.idx), const_cast<void *>(a.gates), m.ws, m.ws_bytes, slot_map, clear_n, stream);
+  } else {
+    rc = tutel_amd_gate_topk(m.logits, m.logits_dtype, 1, T, E, k, m.normalize_gate, nullptr, const_cast<int32_t *>(a.idx),
+                             const_cast<void *>(a.gates), m.ws, m.ws_bytes, slot_map, clear_n, stream);
+  }
+  if (rc) return rc;
+  return tutel_amd_compute_location(a.idx, T, E, k, 1, m.ws, m.ws_bytes, const_cast<int32_t *>(a.loc), m.dispatch_count, m.stats, m.l_aux,
+                                    m.logits_dtype, slot_map != nullptr ? a.capacity : 0, slot_map, slot_map != nullptr ? 1 : 0, stream);
+}
+
 extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, tutel_stream_t stream) {
   TUTEL_REQUIRE(m != nullptr, "tutel_amd_moe_forward: null arguments");
   const tutel_amd_ep_args_t &a = m->ep;
@@ -1067,7 +1120,7 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
   int32_t *smap = const_cast<int32_t *>(a.slot_map);
   int rc;
   // ---- fused location (see expert_gemm_big_kernel<.., FL>): no location launch between the top-k kernel and the first expert GEMM
-  const int Ho = a.H, Mo = a.M_out;
+  const int Mo = a.M_out;
   bool fl = !dropless && c == nullptr && a.world == 1 && a.degree <= 1 && a.is_postscore && a.fuse_encode && T > 0 && k <= 8 && E <= 128 &&
             (long long)k * T <= 15360 && m->fl_ws != nullptr && m->fl_ws_bytes >= (((size_t)k * T + 15) & ~(size_t)15) &&
             (a.dtype == TUTEL_BF16 || a.dtype == TUTEL_F16) && a.row_counts == nullptr && a.hid && a.send && a.zero_row && a.loc && a.w1 &&
@@ -1084,8 +1137,7 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
     char keep[512];
     strncpy(keep, tutel_amd_last_error(), sizeof(keep) - 1);
     keep[sizeof(keep) - 1] = 0;
-    fl = tutel_expert_gemm_gather_fl(a.x, a.M, smap, T, a.zero_row, a.w1, (int64_t)Ho * a.M, a.M, a.b1, Ho, a.hid, (int64_t)a.capacity * Ho, Ho, E,
-                                     a.capacity, Ho, a.M, a.dtype, a.act, (const uint8_t *)m->fl_ws, k * T, nullptr, (hipStream_t)stream) == 0;
+    fl = tutel_expert_gemm(stage_fc1(a, (const uint8_t *)m->fl_ws, k * T, nullptr), 1, a.act, (hipStream_t)stream) == 0;
     if (!fl) tutel_set_error("%s", keep);
   }
   if (fl) {
@@ -1100,25 +1152,8 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
                                 m->ws, nullptr, 0, idx8, st);
     if (rc) return rc;
     if (m->capacity_out != nullptr) *m->capacity_out = a.capacity;
-    rc = TUTEL_AMD_ENOTSUP;
-    if (a.w2_kmajor) {  // fc1 (gather + fused location) -> activation -> fc2 in one persistent launch where the shape takes it (expert_ffn.hip)
-      Range r("tutel_amd.expert_ffn");
-      rc = tutel_expert_ffn(a.x, 0, a.M, smap, T, a.zero_row, a.w1, (int64_t)Ho * a.M, a.M, a.b1, Ho, a.hid, (int64_t)a.capacity * Ho, Ho, a.w2,
-                            (int64_t)Ho * Mo, Ho, a.b2, Mo, a.send, (int64_t)a.capacity * Mo, Mo, E, a.capacity, a.M, Ho, Mo, a.dtype, a.act, idx8, k * T,
-                            const_cast<int32_t *>(a.loc), 0, st);
-      if (rc != 0 && rc != TUTEL_AMD_ENOTSUP) return rc;
-    }
-    if (rc == TUTEL_AMD_ENOTSUP) {
-      Range r("tutel_amd.expert_fc1");
-      rc = tutel_expert_gemm_gather_fl(a.x, a.M, smap, T, a.zero_row, a.w1, (int64_t)Ho * a.M, a.M, a.b1, Ho, a.hid, (int64_t)a.capacity * Ho, Ho,
-                                       E, a.capacity, Ho, a.M, a.dtype, a.act, idx8, k * T, const_cast<int32_t *>(a.loc), st);
-      if (rc) return rc;
-      Range r2("tutel_amd.expert_fc2");
-      rc = tutel_amd_expert_gemm(a.hid, (int64_t)a.capacity * Ho, 0, a.capacity, Ho, a.w2, a.w2_kmajor, (int64_t)Ho * Mo, a.w2_kmajor ? Ho : Mo,
-                                 a.b2, Mo, a.send, (int64_t)a.capacity * Mo, 0, a.capacity, Mo, E, a.capacity, Mo, Ho, a.dtype, TUTEL_ACT_NONE,
-                                 nullptr, 1, stream);
-      if (rc) return rc;
-    }
+    rc = expert_stage(a, idx8, k * T, st);
+    if (rc) return rc;
     Range r("tutel_amd.fast_decode");
     RouteFinish fin;
     tutel_route_finish_args(T, E, k, m->ws, &fin);
@@ -1129,19 +1164,7 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
     fin.l_aux_dtype = m->logits_dtype;
     return tutel_decode_finish_launch(a.send, a.dtype, a.idx, a.loc, a.gates, m->logits_dtype, T, Mo, k, a.capacity, E, a.y, fin, st);
   }
-  if (project && T > 0) {
-    rc = tutel_amd_gate_proj(a.x, m->gate_w, a.dtype, T, a.M, E, m->gate_partials, m->gate_partial_bytes, stream);
-    if (rc) return rc;
-    rc = tutel_amd_gate_topk_partials(m->gate_partials, splits, a.dtype, T, E, k, m->normalize_gate, m->logits_out, nullptr,
-                                      const_cast<int32_t *>(a.idx), const_cast<void *>(a.gates), m->ws, m->ws_bytes,
-                                      dropless ? nullptr : smap, dropless ? 0 : E * a.capacity, stream);
-  } else {
-    rc = tutel_amd_gate_topk(m->logits, m->logits_dtype, 1, T, E, k, m->normalize_gate, nullptr, const_cast<int32_t *>(a.idx),
-                             const_cast<void *>(a.gates), m->ws, m->ws_bytes, dropless ? nullptr : smap, dropless ? 0 : E * a.capacity, stream);
-  }
-  if (rc) return rc;
-  rc = tutel_amd_compute_location(a.idx, T, E, k, 1, m->ws, m->ws_bytes, const_cast<int32_t *>(a.loc), m->dispatch_count, m->stats,
-                                  m->l_aux, m->logits_dtype, dropless ? 0 : a.capacity, dropless ? nullptr : smap, dropless ? 0 : 1, stream);
+  rc = tutel_route_launch(*m, splits, dropless ? nullptr : smap, stream);
   if (rc) return rc;
   tutel_amd_ep_args_t e = a;
   e.gate_dtype = m->logits_dtype;

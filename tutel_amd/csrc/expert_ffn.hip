@@ -280,38 +280,22 @@ static bool ffn_covers(const GemmArgs &g1, const GemmArgs &g2) {
 static unsigned long long *g_ffn_dbg = nullptr;
 extern "C" void tutel_amd_expert_ffn_debug(void *buf) { g_ffn_dbg = (unsigned long long *)buf; }
 
-// internal (common.h): the fused FFN with every option of the two-launch path it replaces.  loc != NULL: fused location (idx8 [n]).
-// query != 0: only answers (0 / TUTEL_AMD_ENOTSUP), launches nothing.
-int tutel_expert_ffn(const void *X, int64_t x_stride_e, int ldx, const int32_t *slot_map, int T, const void *zero_row, const void *W1,
-                     int64_t w1_stride_e, int ldw1, const void *b1, int64_t b1_stride_e, void *hid, int64_t hid_stride_e, int ldh,
-                     const void *W2, int64_t w2_stride_e, int ldw2, const void *b2, int64_t b2_stride_e, void *D, int64_t d_stride_e, int ldd,
-                     int E_loc, int R, int M, int H, int M_out, int dtype, int act, const uint8_t *idx8, int n, int32_t *loc, int query,
-                     hipStream_t st) {
+// internal (common.h): the fused FFN with every option of the two-launch path it replaces, on the two problems those launches would
+// be given.  fc1.fl_idx8 != NULL: fused location.  query != 0: only answers (0 / TUTEL_AMD_ENOTSUP), launches nothing.
+int tutel_expert_ffn(const GemmProblem &fc1, const GemmProblem &fc2, int act, int query, hipStream_t st) {
   // 1 / 2 / 3 = the persistent launch; 0 and AUTOMATIC = the two launches: measured faster (see the file comment)
   const int mode = tutel_get_option(TUTEL_OPT_FFN_FUSED);
   if (mode <= 0) return TUTEL_AMD_ENOTSUP;
-  if (E_loc <= 0 || R <= 0) return TUTEL_AMD_ENOTSUP;
+  const int E_loc = fc1.E_loc, dtype = fc1.dtype;
+  if (E_loc <= 0 || fc1.R <= 0 || fc2.dtype != dtype) return TUTEL_AMD_ENOTSUP;
   FfnArgs a;
-  GemmProblem fc1, fc2;  // X [R, M] -> hid [R, H] -> D [R, M_out], one rank of R rows each
-  fc1.A = X; fc1.a_stride_e = slot_map ? 0 : x_stride_e; fc1.lda = ldx;
-  fc1.W = W1; fc1.w_stride_e = w1_stride_e; fc1.ldw = ldw1; fc1.bias = b1; fc1.bias_stride_e = b1_stride_e;
-  fc1.D = hid; fc1.d_stride_e = hid_stride_e; fc1.ldd = ldh;
-  fc1.E_loc = E_loc; fc1.N = H; fc1.K = M; fc1.dtype = dtype;
-  gemm_one_rank(fc1, R);
-  gemm_gather(fc1, slot_map, T, slot_map ? zero_row : nullptr);
-  fc1.fl_idx8 = idx8; fc1.fl_n = n; fc1.fl_loc = loc;
   int rc = tutel_gemm_args(fc1, &a.g[0]);
   if (rc != 0) return rc < 0 ? rc : TUTEL_AMD_ENOTSUP;
-  fc2.A = hid; fc2.a_stride_e = hid_stride_e; fc2.lda = ldh;
-  fc2.W = W2; fc2.w_stride_e = w2_stride_e; fc2.ldw = ldw2; fc2.bias = b2; fc2.bias_stride_e = b2_stride_e;
-  fc2.D = D; fc2.d_stride_e = d_stride_e; fc2.ldd = ldd;
-  fc2.E_loc = E_loc; fc2.N = M_out; fc2.K = H; fc2.dtype = dtype;
-  gemm_one_rank(fc2, R);
   rc = tutel_gemm_args(fc2, &a.g[1]);
   if (rc != 0) return rc < 0 ? rc : TUTEL_AMD_ENOTSUP;
-  const bool fl = idx8 != nullptr;
+  const bool fl = fc1.fl_idx8 != nullptr;
   if (!ffn_covers(a.g[0], a.g[1])) return TUTEL_AMD_ENOTSUP;
-  if (fl && !(slot_map != nullptr && n >= 1 && n <= 15360 && E_loc <= 128 && M >= 2 * GL_BK && ((uintptr_t)idx8 & 15) == 0 &&
+  if (fl && !(fc1.a_rows != nullptr && fc1.fl_n >= 1 && fc1.fl_n <= 15360 && E_loc <= 128 && fc1.K >= 2 * GL_BK && ((uintptr_t)fc1.fl_idx8 & 15) == 0 &&
               tutel_get_option(TUTEL_OPT_FUSED_LOCATION) != 0))
     return TUTEL_AMD_ENOTSUP;
   if (query) return 0;
@@ -345,7 +329,17 @@ extern "C" int tutel_amd_expert_ffn(const void *X, int64_t x_stride_e, int ldx, 
   if (E_loc == 0 || R == 0) return 0;
   TUTEL_REQUIRE(X && W1 && hid && W2 && D, "tutel_amd_expert_ffn: null pointer");
   TUTEL_REQUIRE(slot_map == nullptr || (T >= 1 && zero_row != nullptr), "tutel_amd_expert_ffn: the row gather needs T >= 1 and a zero row");
-  return tutel_expert_ffn(X, x_stride_e, ldx, slot_map, T, zero_row, W1, w1_stride_e, ldw1, b1, b1_stride_e, hid, hid_stride_e, ldh, W2,
-                          w2_stride_e, ldw2, b2, b2_stride_e, D, d_stride_e, ldd, E_loc, R, M, H, M_out, dtype, act, nullptr, 0, nullptr, 0,
-                          (hipStream_t)stream);
+  GemmProblem fc1, fc2;  // X [R, M] -> hid [R, H] -> D [R, M_out], one rank of R rows each
+  fc1.A = X; fc1.a_stride_e = slot_map ? 0 : x_stride_e; fc1.lda = ldx;
+  fc1.W = W1; fc1.w_stride_e = w1_stride_e; fc1.ldw = ldw1; fc1.bias = b1; fc1.bias_stride_e = b1_stride_e;
+  fc1.D = hid; fc1.d_stride_e = hid_stride_e; fc1.ldd = ldh;
+  fc1.E_loc = E_loc; fc1.N = H; fc1.K = M; fc1.dtype = dtype;
+  gemm_one_rank(fc1, R);
+  gemm_gather(fc1, slot_map, T, slot_map ? zero_row : nullptr);
+  fc2.A = hid; fc2.a_stride_e = hid_stride_e; fc2.lda = ldh;
+  fc2.W = W2; fc2.w_stride_e = w2_stride_e; fc2.ldw = ldw2; fc2.bias = b2; fc2.bias_stride_e = b2_stride_e;
+  fc2.D = D; fc2.d_stride_e = d_stride_e; fc2.ldd = ldd;
+  fc2.E_loc = E_loc; fc2.N = M_out; fc2.K = H; fc2.dtype = dtype;
+  gemm_one_rank(fc2, R);
+  return tutel_expert_ffn(fc1, fc2, act, 0, (hipStream_t)stream);
 }

@@ -1106,14 +1106,20 @@ int tutel_gemm_args(const GemmProblem &g, GemmArgs *out) {
   return 0;
 }
 
-static int expert_gemm_impl(const GemmProblem &g, int w_kmajor, int act, tutel_stream_t stream) {
+// internal (common.h): one grouped GEMM, every form
+int tutel_expert_gemm(const GemmProblem &g, int w_kmajor, int act, hipStream_t st) {
+  TUTEL_REQUIRE(g.d_can == nullptr || g.d_peer != nullptr, "tutel_expert_gemm_peer: null peer table");
+  if (g.fl_idx8 != nullptr || g.fl_loc != nullptr) {  // fused location: the kernel writes the slot map (g.a_rows) and g.fl_loc itself
+    TUTEL_REQUIRE(g.a_rows != nullptr && g.fl_idx8 != nullptr && g.a_rows_mod >= 1 && ((uintptr_t)g.fl_idx8 & 15) == 0,
+                  "tutel_expert_gemm_gather_fl: bad arguments");
+    if (tutel_get_option(TUTEL_OPT_FUSED_LOCATION) == 0) return TUTEL_AMD_ENOTSUP;
+  }
   GemmArgs a;
   const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   long long grid_ll = (long long)g.E_loc * a.ntm * a.ntn;
   TUTEL_REQUIRE(grid_ll < 0x7fffffffLL, "tutel_amd_expert_gemm: grid too large");
   const int grid = (int)grid_ll;
-  hipStream_t st = (hipStream_t)stream;
   auto go = [&]() -> int {
     return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
         g.dtype, act,
@@ -1139,40 +1145,7 @@ extern "C" int tutel_amd_expert_gemm(const void *A, int64_t a_stride_e, int64_t 
   g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
   g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
   g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
-  return expert_gemm_impl(g, w_kmajor, act, stream);
-}
-
-int tutel_expert_gemm_peer(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
-                           int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e,
-                           const uint64_t *d_peer, int64_t d_peer_off, int64_t d_stride_e, int d_rows_per_w, int ldd, int E_loc,
-                           int R, int N, int K, int dtype, int act, const PeerCanary &can, hipStream_t st) {
-  TUTEL_REQUIRE(d_peer != nullptr, "tutel_expert_gemm_peer: null peer table");
-  GemmProblem g;
-  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
-  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
-  g.d_stride_e = d_stride_e; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
-  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype;
-  g.d_peer = d_peer; g.d_peer_off = d_peer_off; g.d_can = &can;
-  return expert_gemm_impl(g, w_kmajor, act, (tutel_stream_t)st);
-}
-
-// tutel_amd_expert_gemm_gather with the locations computed INSIDE the launch (see the FL comment at expert_gemm_big_kernel): the
-// kernel fills slot_map [E_loc * R] and loc [n] itself from idx8 [n] (n = k * T bytes, buffer padded to 16).  loc == NULL: only
-// answers whether this shape takes the fused kernel (0) or not (TUTEL_AMD_ENOTSUP) -- nothing is launched.
-int tutel_expert_gemm_gather_fl(const void *X, int ldx, int32_t *slot_map, int T, const void *zero_row, const void *W, int64_t w_stride_e,
-                                int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e, int ldd, int E_loc, int R,
-                                int N, int K, int dtype, int act, const uint8_t *idx8, int n, int32_t *loc, hipStream_t st) {
-  TUTEL_REQUIRE(slot_map != nullptr && idx8 != nullptr && T >= 1 && ((uintptr_t)idx8 & 15) == 0, "tutel_expert_gemm_gather_fl: bad arguments");
-  if (tutel_get_option(TUTEL_OPT_FUSED_LOCATION) == 0) return TUTEL_AMD_ENOTSUP;
-  GemmProblem g;
-  g.A = X; g.lda = ldx;
-  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
-  g.D = D; g.d_stride_e = d_stride_e; g.ldd = ldd;
-  g.E_loc = E_loc; g.N = N; g.K = K; g.dtype = dtype;
-  gemm_one_rank(g, R);
-  gemm_gather(g, slot_map, T, zero_row);
-  g.fl_idx8 = idx8; g.fl_n = n; g.fl_loc = loc;
-  return expert_gemm_impl(g, 1, act, (tutel_stream_t)st);
+  return tutel_expert_gemm(g, w_kmajor, act, (hipStream_t)stream);
 }
 
 extern "C" int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
@@ -1186,7 +1159,7 @@ extern "C" int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int6
   g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
   g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
   g.mul = G;
-  return expert_gemm_impl(g, w_kmajor, act, stream);
+  return tutel_expert_gemm(g, w_kmajor, act, (hipStream_t)stream);
 }
 
 extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_t *slot_map, int T, const void *zero_row, const void *W, int w_kmajor,
@@ -1201,25 +1174,13 @@ extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_
   g.E_loc = E_loc; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
   gemm_one_rank(g, R);
   gemm_gather(g, slot_map, T, zero_row);
-  return expert_gemm_impl(g, w_kmajor, act, stream);
+  return tutel_expert_gemm(g, w_kmajor, act, (hipStream_t)stream);
 }
 
 // ---- the packed dropless layout (dropless.hip) ---------------------------------------------------------------------------------------
 // Rows are global packed rows of ONE array per operand (stride between experts 0, one "rank" of rows_bound rows), so the kernel's row
 // addressing, the out-of-range zero rows and the row limit work unchanged; what changes per block is where its tile, expert and row
-// limit come from (the device tile table).  What the plain and the gate/up entry points share: the table's checks, and the problem's
-// row layout + the GemmArgs block with the table in it (W, bias, mul, D, the sizes and the dtype are the caller's to fill in g).
-static int packed_table_check(const char *what, const PackedTable &t, int rows_bound, const int32_t *a_rows, int T) {
-  TUTEL_REQUIRE(t.off && t.tiles && t.ntiles && t.cap && t.tiles_bound >= 1 && rows_bound >= 1 && (a_rows == nullptr || T >= 1), "%s: bad arguments", what);
-  return 0;
-}
-static int packed_gemm_args(GemmProblem &g, int rows_bound, const int32_t *a_rows, int T, const void *zero_row, const PackedTable &t, GemmArgs *a) {
-  gemm_one_rank(g, rows_bound);
-  gemm_gather(g, a_rows, T, zero_row);
-  const int brc = tutel_gemm_args(g, a);
-  if (brc == 0) { a->pk_off = t.off; a->pk_tiles = t.tiles; a->pk_ntiles = t.ntiles; a->pk_cap = t.cap; }
-  return brc;
-}
+// limit come from (the device tile table).
 
 // n-major weights over the packed layout: the register-staged 128 x 128 kernel (its transposing LDS read takes W [K][N] as stored),
 // two 128-row M-tiles per entry of the 256-row tile table, grid sized by the host's tile bound
@@ -1232,34 +1193,6 @@ static int launch_packed_nmajor(const GemmArgs &a, int tiles_bound, hipStream_t 
   TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_packed: grid too large");
   return launch_lds(expert_gemm_kernel<T, false, ACT, true, true, true>, (unsigned)grid, GM_THREADS, gemm_lds_bytes(false), st, b,
                     "tutel_amd_expert_gemm_packed");
-}
-
-// internal (common.h): the grouped GEMM over the packed layout
-int tutel_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W, int w_kmajor,
-                             int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *mul, void *D, int ldd, int E,
-                             int rows_bound, int N, int K, int dtype, int act, const PackedTable &t, hipStream_t st) {
-  if (packed_table_check("tutel_expert_gemm_packed", t, rows_bound, a_rows, T) != 0) return -1;
-  GemmProblem g;
-  g.A = A; g.lda = lda;
-  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
-  g.D = D; g.ldd = ldd;
-  g.E_loc = E; g.N = N; g.K = K; g.dtype = dtype;
-  g.mul = mul;
-  GemmArgs a;
-  const int brc = packed_gemm_args(g, rows_bound, a_rows, T, zero_row, t, &a);
-  if (brc != 0) return brc < 0 ? brc : 0;
-  if (!a.fits32) {
-    tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
-    return TUTEL_AMD_ENOTSUP;
-  }
-  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
-  if (!w_kmajor)
-    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(
-        dtype, act, [&](auto e, auto ac) { return launch_packed_nmajor<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
-        [&] { tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP; });
-  return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
-      dtype, act, [&](auto e, auto ac) { return launch_pp_packed<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
-      [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
 }
 
 // ---- fused gate/up GEMM of a SwiGLU expert (GATE_UP ping-pong kernel) -------------------------------------------------------------
@@ -1298,24 +1231,33 @@ extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, 
   return gate_up_act<false>(a, dtype, act, 0, st);
 }
 
-// internal (common.h): the same over the packed dropless layout, arguments as tutel_expert_gemm_packed plus W_up
-int tutel_expert_gemm_gate_up_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *W_gate,
-                                     const void *W_up, int64_t w_stride_e, int ldw, void *D, int ldd, int E, int rows_bound, int N, int K,
-                                     int dtype, int act, const PackedTable &t, hipStream_t st) {
-  if (packed_table_check("tutel_expert_gemm_gate_up_packed", t, rows_bound, a_rows, T) != 0) return -1;
-  if (!gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
-  GemmProblem g;
-  g.A = A; g.lda = lda;
-  g.W = W_gate; g.w_stride_e = w_stride_e; g.ldw = ldw;
-  g.D = D; g.ldd = ldd;
-  g.E_loc = E; g.N = N; g.K = K; g.dtype = dtype;
+// internal (common.h): the grouped GEMM over the packed layout; w_up != NULL: the fused gate/up GEMM over it
+int tutel_expert_gemm_packed(const GemmProblem &g, int w_kmajor, int act, const PackedTable &t, const void *w_up, hipStream_t st) {
+  TUTEL_REQUIRE(t.off && t.tiles && t.ntiles && t.cap && t.tiles_bound >= 1 && g.R >= 1 && (g.a_rows == nullptr || g.a_rows_mod >= 1),
+                "%s: bad arguments", w_up != nullptr ? "tutel_expert_gemm_gate_up_packed" : "tutel_expert_gemm_packed");
+  if (w_up != nullptr && !gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
   GemmArgs a;
-  const int brc = packed_gemm_args(g, rows_bound, a_rows, T, zero_row, t, &a);
+  const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
-  TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
-  if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
-  if ((ldd & 7) || ((uintptr_t)D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
-  a.w_up = W_up;
-  StageScope stage(TUTEL_STAGE_FC1, st);
-  return gate_up_act<true>(a, dtype, act, t.tiles_bound, st);
+  a.pk_off = t.off; a.pk_tiles = t.tiles; a.pk_ntiles = t.ntiles; a.pk_cap = t.cap;
+  if (w_up != nullptr) {
+    TUTEL_REQUIRE(((uintptr_t)w_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
+    if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
+    if ((g.ldd & 7) || ((uintptr_t)g.D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
+    a.w_up = w_up;
+    StageScope stage(TUTEL_STAGE_FC1, st);
+    return gate_up_act<true>(a, g.dtype, act, t.tiles_bound, st);
+  }
+  if (!a.fits32) {
+    tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
+    return TUTEL_AMD_ENOTSUP;
+  }
+  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  if (!w_kmajor)
+    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(
+        g.dtype, act, [&](auto e, auto ac) { return launch_packed_nmajor<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
+        [&] { tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP; });
+  return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+      g.dtype, act, [&](auto e, auto ac) { return launch_pp_packed<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
+      [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
 }

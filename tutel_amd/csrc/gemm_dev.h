@@ -10,31 +10,6 @@
 #define GEMM_PROBE(i)
 #endif
 
-// One grouped GEMM as its callers state it, D[e, r, :] = act(A[e, r, :] @ op(W[e]) + bias[e, :]) [* mul]: the operands of the C ABI
-// (include/tutel_amd.h) plus the internal forms.  Callers assign the fields they mean to a local; the rest keep these defaults.
-struct GemmProblem {
-  const void *A = nullptr; int64_t a_stride_e = 0, a_stride_w = 0; int a_rows_per_w = 0, lda = 0;
-  const void *W = nullptr; int64_t w_stride_e = 0; int ldw = 0;
-  const void *bias = nullptr; int64_t bias_stride_e = 0;
-  void *D = nullptr; int64_t d_stride_e = 0, d_stride_w = 0; int d_rows_per_w = 0, ldd = 0;
-  int E_loc = 0, R = 0, N = 0, K = 0;
-  int dtype = -1;
-  const int32_t *row_counts = nullptr; int row_align = 1;
-  const int32_t *a_rows = nullptr; int a_rows_mod = 0; const void *a_zero = nullptr;  // row r of A is token a_rows[r] % a_rows_mod (-1: a_zero)
-  const void *mul = nullptr;
-  const uint64_t *d_peer = nullptr; int64_t d_peer_off = 0; const PeerCanary *d_can = nullptr;
-  const uint8_t *fl_idx8 = nullptr; int fl_n = 0; int32_t *fl_loc = nullptr;
-};
-// A and D hold one rank of R rows per expert (no [W, E_loc, C, M] permute folded into the row addressing)
-static inline void gemm_one_rank(GemmProblem &g, int R) {
-  g.R = R;
-  g.a_rows_per_w = g.d_rows_per_w = R > 0 ? R : 1;
-}
-// A's rows come through a slot map over T token rows (fused fast_encode); slot_map == NULL: no gather
-static inline void gemm_gather(GemmProblem &g, const int32_t *slot_map, int T, const void *zero_row) {
-  g.a_rows = slot_map; g.a_rows_mod = slot_map != nullptr ? T : 0; g.a_zero = zero_row;
-}
-
 struct GemmArgs;
 // host side, expert_gemm.hip: argument checks + the GemmArgs block of one grouped GEMM (0: filled, 1: empty problem, < 0: error);
 // the > 64 KB dynamic-LDS opt-in per (kernel, device)

@@ -310,6 +310,13 @@ extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_
   TUTEL_REQUIRE(offsets && tiles && ntiles && capacity, "tutel_amd_expert_gemm_packed: null pointer");
   TUTEL_REQUIRE(((uintptr_t)D & 15) == 0 && ldd % 8 == 0 && ((uintptr_t)mul & 15) == 0,
                 "tutel_amd_expert_gemm_packed: D and mul must be 16-byte aligned, ldd a multiple of 8");
-  return tutel_expert_gemm_packed(A, lda, a_rows, T, zero_row, W, w_kmajor, w_stride_e, ldw, bias, bias_stride_e, mul, D, ldd, E, rows_bound, N, K,
-                                  dtype, act, PackedTable{offsets, tiles, ntiles, capacity, tiles_bound}, (hipStream_t)stream);
+  GemmProblem g;
+  g.A = A; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.ldd = ldd;
+  g.E_loc = E; g.N = N; g.K = K; g.dtype = dtype;
+  g.mul = mul;
+  gemm_one_rank(g, rows_bound);
+  gemm_gather(g, a_rows, T, zero_row);
+  return tutel_expert_gemm_packed(g, w_kmajor, act, PackedTable{offsets, tiles, ntiles, capacity, tiles_bound}, nullptr, (hipStream_t)stream);
 }
