@@ -1,7 +1,8 @@
 """TEST-ONLY pieces shared by the fuzzers of the packed dropless kernels (tests/test_packed_fuzz_gpu.py) and their GPU-free checks
 (tests/test_packed_fuzz_cpu.py): the seeded case generators, the edge classes each fuzzer promises to draw, and the references --
 plain integer arithmetic for the layout, float64 for the GEMM / weight gradient / bias gradient, written from the layout's
-definition (csrc/dropless.hip header comment) and not from the kernels.  Nothing here needs a GPU or the library."""
+definition (csrc/dropless.hip header comment) and not from the kernels; the guard bands (moated / moat_intact) that surround every
+operand of the GEMM and gradient fuzzers.  Nothing here needs a GPU or the library."""
 import math
 import random
 
@@ -490,6 +491,277 @@ def layer_classes(d):
         if on:
             c.add(name)
     return c
+
+
+# =================================================================================================================================
+# guard bands: an operand in the middle of a larger buffer, so that a read or a store next to it shows in an assertion
+# =================================================================================================================================
+MOAT_ROWS = 64        # rows of the operand's own width on each side, at least
+MOAT_BYTES = 4096     # and never less than this on each side
+OUT_FILL = -777.0     # the band around an output (the view itself is pre-filled by the caller)
+_INT_VIEW = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def moated(t, fill=None, rows=MOAT_ROWS, device=None):
+    """a contiguous tensor of t's shape, values and dtype in the middle of a larger buffer on `device` (t's own by default): at least
+    `rows` rows of t's width and at least 4 KiB of `fill` before and after it, the band a multiple of 16 bytes so that the view is
+    aligned as a fresh allocation is.  fill: NaN for a floating tensor, SENTINEL for an integer one, unless given (an index table takes
+    an in-range index: a kernel that reads past the table must not get a wild address out of it)."""
+    if fill is None:
+        fill = float("nan") if t.dtype.is_floating_point else SENTINEL
+    es = t.element_size()
+    width = int(np.prod(t.shape[1:])) if t.dim() > 1 else 1
+    band = round_up(max(rows * width * es, MOAT_BYTES), 16) // es
+    assert (band * es) % 16 == 0
+    n = t.numel()
+    buf = torch.empty([2 * band + n], dtype=t.dtype, device=device if device is not None else t.device)
+    buf.fill_(fill)
+    view = buf[band:band + n].view(t.shape)
+    view.copy_(t)
+    view._moat = (buf, band, torch.full([1], fill, dtype=t.dtype).view(_INT_VIEW[es]).item())
+    return view
+
+
+def moat_intact(view, what="operand"):
+    """the band around a moated() view still holds its fill, bit for bit"""
+    buf, band, bits = view._moat
+    raw = buf.view(_INT_VIEW[buf.element_size()])
+    n = view.numel()
+    assert view.data_ptr() == buf.data_ptr() + band * buf.element_size() and raw.numel() == 2 * band + n, "not the view moated() returned"
+    for name, part in (("before", raw[:band]), ("after", raw[band + n:])):
+        ne = (part != bits).nonzero()
+        assert ne.numel() == 0, f"the band {name} {what} was written: {ne.numel()} elements, the first {int(ne[0])} elements into it"
+
+
+def free_token(slot, T):
+    """the largest token row that no live row of a slot map names (q % T for every q >= 0), or None"""
+    slot = np.asarray(slot, dtype=np.int64)
+    named = np.zeros([T], dtype=bool)
+    named[slot[slot >= 0] % T] = True
+    free = np.nonzero(~named)[0]
+    return int(free[-1]) if free.size else None
+
+
+# =================================================================================================================================
+# row-sampled float64 reference of the grouped GEMM (the large fixed cases: every row is compared bit for bit with a second launch,
+# float64 on the first and last row of every tile and two random rows of it)
+# =================================================================================================================================
+def tile_sample_rows(tiles, offsets, seed, per_tile=2):
+    """sorted unique rows: of every tile (e, start) its first row, its last live row (below offsets[e + 1]) and per_tile random ones"""
+    g = np.random.default_rng(seed)
+    rows = []
+    for e, start in np.asarray(tiles, dtype=np.int64).reshape(-1, 2):
+        end = min(int(start) + TILE, int(offsets[e + 1]))
+        rows += [int(start), end - 1] + [int(v) for v in g.integers(int(start), end, size=per_tile)]
+    return np.unique(np.array(rows, dtype=np.int64))
+
+
+def ref_gemm_rows(a_rows, w, bias, kmajor, act, mul, offsets, dtype, rows):
+    """ref_gemm on the packed rows `rows` only (sorted, below offsets[E]) -> (the product rounded once to dtype, the exact fp64 value
+    before the rounding, |a| |W| + |b| of the same element), each [len(rows), N]"""
+    E = w.shape[0]
+    N = w.shape[1] if kmajor else w.shape[2]
+    rows = torch.as_tensor(np.asarray(rows, dtype=np.int64))
+    exact = torch.zeros([rows.numel(), N], dtype=torch.float64)
+    mag = torch.zeros_like(exact)
+    owner = np.searchsorted(np.asarray(offsets, dtype=np.int64), rows.numpy(), side="right") - 1
+    for e in np.unique(owner):
+        sel = torch.from_numpy(np.nonzero(owner == e)[0])
+        r = rows[sel]
+        we = w[e].double()
+        we = we.t() if kmajor else we
+        A = a_rows[r].double()
+        y, m = A @ we, A.abs() @ we.abs()
+        if bias is not None:
+            y, m = y + bias[e].double(), m + bias[e].double().abs()
+        y = ACTS64[act](y)
+        if mul is not None:
+            y, m = y * mul[r].double(), m * mul[r].double().abs()
+        exact[sel], mag[sel] = y, m
+    return exact.to(dtype).double(), exact, mag
+
+
+def nmajor_bound(exact, mag, K, dtype):
+    """the bar of tests/test_packed_nmajor_gather_gpu.py: one rounding of an fp32 sum over K"""
+    u = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+    return 1.01 * u * exact.abs() + K * 2.0 ** -24 * mag + 2.0 ** -24
+
+
+# =================================================================================================================================
+# f. the forms a SwiGLU training step on the packed layout relies on (DESIGN 4.4): the n-major GEMM with gathered rows, the k-major
+# ping-pong kernel as a plain product on both sides of its weights-streamed-once switch, the weight gradient with gathered operands
+# at wide N_a, N_b -- over layouts of REAL routings (k choices per token, distinct, a share masked; slot values up to k T - 1)
+# =================================================================================================================================
+TRAIN_T = [1, 50, 1000, 4096]
+TRAIN_ALIGN = [1, 8, 128]
+NM_N = [8, 120, 128, 136, 264, 1024, 2048]
+NM_K = [64, 192, 1024, 2048]
+WG_N = [8, 136, 512, 1024, 2048]
+F64_BUDGET = 1 << 30      # multiply-adds of one float64 reference; a GEMM above it is checked on sampled rows (tile_sample_rows)
+TRAIN_PROMISED = (
+    {"nm:act=none", "nm:act=relu", "nm:bias", "nm:no_bias", "nm:bf16", "nm:f16", "nm:rot_on", "nm:rot_off", "nm:entries>=96", "nm:entries>256",
+     "nm:many_entries_empty_between", "nm:expert>256", "nm:one_row_in_new_tile", "nm:pad_rows_align8", "nm:pad_rows_align128", "nm:slot>=T",
+     "nm:N=K=2048", "nm:N=K=2048:entries>=96", "nm:masked", "nm:T=4096"}
+    | {"nm:N=%d" % n for n in NM_N} | {"nm:K=%d" % k for k in NM_K}
+    | {"pp:once_%s:%s:%s" % (s, g, m) for s in ("on", "off") for g in ("gather", "packed") for m in ("mul", "no_mul")}
+    | {"pp:once_on:expert>256", "pp:once_off:expert>256", "pp:E=128,N=512,K=64", "pp:E=256,N=256", "pp:N=K=2048:entries>=96", "pp:slot>=T", "pp:bf16",
+       "pp:f16", "pp:pad_rows", "pp:T=4096"}
+    | {"wg:gather=a", "wg:gather=b", "wg:gather=none", "wg:2048x2048", "wg:16bit:gathered", "wg:f32:gathered", "wg:acc:gathered", "wg:T=4096:slot>=T",
+       "wg:empty_between", "wg:bf16", "wg:f16", "wg:pad_rows"}
+    | {"wg:N=%d" % n for n in WG_N})
+
+
+def _routing_fields(rnd, E, t_choices=TRAIN_T + [1000, 4096]):
+    T = rnd.choice(t_choices)
+    return dict(T=T, k=min(E, rnd.choice([1, 2, 4])), align=rnd.choice(TRAIN_ALIGN), mode=rnd.choice(["random", "random", "skewed"]),
+                mask_p=0.0 if T == 1 else rnd.choice([0.1, 0.5, 0.9]), rows=None)
+
+
+def _gen_nmajor(rnd, j):
+    d = dict(act=["none", "relu"][j & 1], bias=bool((j >> 1) & 1), dtype=["bf16", "f16"][(j >> 2) & 1], gather=True, mul=False)
+    N, K = NM_N[j % len(NM_N)], NM_K[j % len(NM_K)]
+    small_n, small_k = rnd.choice([8, 120, 128, 136]), rnd.choice([64, 192])
+    E = rnd.choice([2, 3, 8, 17, 64])
+    r = _routing_fields(rnd, E)
+    live = [rnd.choice([1, 2, 7, 9]) for _ in range(100)]
+    if j == 0:      # more than 256 tile-table entries: many experts, a few rows each
+        E, N, K, r = 512, small_n, small_k, dict(T=1000, k=2, align=1, mode="random", mask_p=0.0, rows=None)
+    elif j == 1:    # at least 96 entries with an empty expert between every two live ones
+        E, N, K = 200, small_n, small_k
+        r = dict(T=1000, k=2, align=8, mode="rows", mask_p=0.0, rows=[live[e // 2] if e % 2 == 0 else 0 for e in range(E)])
+    elif j == 2:
+        E, N, K, r = 3, 2048, 2048, dict(T=50, k=2, align=1, mode="random", mask_p=0.1, rows=None)
+    elif j == 3:    # one row into a second and a third tile; an empty expert between live ones
+        E, r = 4, dict(T=1000, k=2, align=1, mode="rows", mask_p=0.0, rows=[257, 0, 300, 513])
+    elif j == 4:
+        E, r = 16, dict(T=4096, k=4, align=128, mode="random", mask_p=0.5, rows=None)
+    elif j == 5:
+        E, N, K, r = 2, 2048, 2048, dict(T=4096, k=2, align=8, mode="random", mask_p=0.9, rows=None)
+    while E * N * K > (1 << 25) and r["rows"] is None:       # the weights stay below 64 MiB: fewer experts, the same N and K
+        E = max(1, E // 2)
+    r["k"] = min(r["k"], E)
+    return dict(d, E=E, N=N, K=K, **r)
+
+
+def _gen_pp(rnd, j):
+    once, gather, mul, big = bool(j & 1), bool((j >> 1) & 1), bool((j >> 2) & 1), bool((j >> 3) & 1)
+    if once:        # E * ceil(N / 256) >= 256 at its smallest shapes
+        E, N, K = (256, 256, 64) if (j >> 1) % 3 == 0 else (128, 512, rnd.choice([64, 64, 192]))
+    else:
+        E, N, K = rnd.choice([1, 2, 3, 8, 17]), rnd.choice([8, 120, 256, 264, 512, 1024, 2048]), rnd.choice(NM_K)
+        while E * N * K > (1 << 25):
+            E = max(1, E // 2)
+    r = _routing_fields(rnd, E, [50, 1000, 4096])
+    small = [rnd.choice([0, 1, 2, 7]) for _ in range(E)]
+    at, rows = rnd.randrange(E), rnd.choice([257, 300, 513])
+    if big:
+        small[at] = rows
+        r = dict(T=1000, k=min(E, 4), align=rnd.choice(TRAIN_ALIGN), mode="rows", mask_p=0.0, rows=small)
+    return dict(act="none", bias=False, dtype=rnd.choice(["bf16", "f16"]), gather=gather, mul=mul, E=E, N=N, K=K, **r)
+
+
+def _gen_wgrad(rnd, j):
+    gather, form = ["a", "b", "none"][j % 3], ["16", "f32", "acc"][(j // 3) % 3]
+    Na, Nb = WG_N[j % len(WG_N)], WG_N[(j + j // len(WG_N)) % len(WG_N)]
+    E = rnd.choice([1, 2, 3, 8, 17, 64])
+    r = _routing_fields(rnd, E)
+    if j == 0:      # 16 x 16 output tiles per expert
+        E, Na, Nb, r = 2, 2048, 2048, dict(T=4096, k=2, align=1, mode="rows", mask_p=0.0, rows=[150, 140])
+    elif j == 1:
+        E, r = 5, dict(T=1000, k=2, align=8, mode="rows", mask_p=0.0, rows=[70, 0, 257, 0, 3])
+    elif j == 2:
+        E, r = 8, dict(T=4096, k=4, align=1, mode="random", mask_p=0.9, rows=None)
+    elif j == 3:
+        E, r = 4, dict(T=4096, k=2, align=128, mode="random", mask_p=0.9, rows=None)
+    while E * Na * Nb > (1 << 23) and r["rows"] is None:
+        E = max(1, E // 2)
+    r["k"] = min(r["k"], E)
+    while r["rows"] is None and r["k"] * r["T"] * (1 - r["mask_p"]) * Na * Nb > F64_BUDGET:     # the float64 product of all rows: mask more tokens, T stays
+        r["mask_p"] = 1 - (1 - r["mask_p"]) / 2
+    return dict(gather=gather, form=form, dtype=rnd.choice(["bf16", "f16"]), E=E, Na=Na, Nb=Nb, **r)
+
+
+def gen_train_form_cases(n_cases, seed):
+    """cases 0 and 1: K = N = 2048 over 96 tile-table entries in one launch, n-major gathered and through the k-major ping-pong kernel
+    (3 experts of 8192 rows: 8193 tokens, one of them masked, every other one choosing all three experts); then the three kinds in
+    turn, the j-th case of a kind cycling through that kind's classes"""
+    rnd = random.Random(seed)
+    out, count = [], {"nmajor": 0, "pp": 0, "wgrad": 0}
+    for case in range(n_cases):
+        if case < 2:
+            kind = ("nmajor", "pp")[case]
+            d = dict(act="none", bias=case == 0, dtype="bf16", gather=True, mul=False, E=3, N=2048, K=2048, T=8193, k=3, align=1, mode="all3", mask_p=0.0, rows=None)
+        else:
+            kind = ("nmajor", "pp", "wgrad")[(case - 2) % 3]
+            d = {"nmajor": _gen_nmajor, "pp": _gen_pp, "wgrad": _gen_wgrad}[kind](rnd, count[kind])
+            count[kind] += 1
+        out.append(dict(d, case=case, kind=kind, seed=seed * 1299709 + case))
+    return out
+
+
+def train_routing(d):
+    """the case's expert ids [k, T] int32 (numpy): the choices of a token distinct, a share of the entries masked with -1, and (T > 1)
+    one token without any live choice: the row of the token array that holds NaN and that the slot map's guard band names"""
+    g = np.random.default_rng(d["seed"])
+    T, E, k = d["T"], d["E"], d["k"]
+    if d["mode"] == "all3":
+        idx = (np.arange(T)[None, :] + np.arange(k)[:, None]) % E
+        idx[:, T // 2] = -1
+    elif d["mode"] == "rows":      # expert e gets rows[e] entries, spread over all tokens but one and over the k choices
+        rows = np.asarray(d["rows"], dtype=np.int64)
+        Tu = max(T - 1, 1)
+        n = int(rows.sum())
+        assert int(rows.max()) <= Tu and n <= k * Tu, "an expert is chosen at most once by a token"
+        perm = g.permutation(T)
+        i = np.arange(n)
+        idx = np.full([k, T], -1, dtype=np.int64)
+        idx[i // Tu, perm[i % Tu]] = np.repeat(np.arange(E), rows)
+        idx = np.take_along_axis(idx, np.argsort(g.random([k, T]), axis=0), 0)
+    else:
+        idx = make_routing(d).astype(np.int64)
+        if T > 1:
+            idx[:, int(g.integers(T))] = -1
+    return idx.astype(np.int32)
+
+
+def train_tag(d):
+    if d["kind"] == "wgrad":
+        s = "wgrad Na={Na} Nb={Nb} gather={gather} form={form}".format(**d)
+    else:
+        s = "{kind} N={N} K={K} act={act} bias={bias} mul={mul} gather={gather}".format(**d)
+    return ("train form case {case}: " + s + " {dtype} T={T} E={E} k={k} align={align} {mode} mask={mask_p}").format(s=s, **{**d, "mask_p": round(d["mask_p"], 4)})
+
+
+def train_classes(d, ref):
+    """the classes of a case and its reference layout (ref_layout of train_routing(d))"""
+    E, T, align = d["E"], d["T"], d["align"]
+    rows, kept, ntiles = ref["rows"], ref["kept"], ref["ntiles"]
+    live = np.nonzero(rows > 0)[0]
+    between = bool(live.size >= 2 and (rows[live[0]:live[-1]] == 0).any())
+    slot_hi = bool((ref["slot"] >= T).any())
+    pad = bool((rows > kept).any())
+    big = bool((rows > TILE).any())
+    masked = bool((train_routing(d) < 0).any())
+    c = set()
+    if d["kind"] == "wgrad":
+        gathered_ = d["gather"] != "none"
+        on = [("gather=" + d["gather"], True), ("2048x2048", d["Na"] == 2048 and d["Nb"] == 2048 and E <= 2 and int(ref["offsets"][-1]) <= 300),
+              ({"16": "16bit", "f32": "f32", "acc": "acc"}[d["form"]] + ":gathered", gathered_), ("T=4096:slot>=T", T == 4096 and slot_hi and gathered_),
+              ("empty_between", between), (d["dtype"], True), ("pad_rows", pad), ("N=%d" % d["Na"], True), ("N=%d" % d["Nb"], True)]
+        return {"wg:" + n for n, v in on if v}
+    N, K = d["N"], d["K"]
+    if d["kind"] == "nmajor":
+        on = [("act=" + d["act"], True), ("bias" if d["bias"] else "no_bias", True), (d["dtype"], True), ("N=%d" % N, True), ("K=%d" % K, True),
+              ("rot_on" if ref["capacity"] < 256 else "rot_off", True), ("entries>=96", ntiles >= 96), ("entries>256", ntiles > 256),
+              ("many_entries_empty_between", ntiles >= 96 and between), ("expert>256", big), ("one_row_in_new_tile", bool((rows % TILE == 1).any() and big)),
+              ("pad_rows_align8", pad and align == 8), ("pad_rows_align128", pad and align == 128), ("slot>=T", slot_hi), ("N=K=2048", N == 2048 and K == 2048),
+              ("N=K=2048:entries>=96", N == 2048 and K == 2048 and ntiles >= 96), ("masked", masked), ("T=4096", T == 4096)]
+        return {"nm:" + n for n, v in on if v}
+    once = "once_on" if E * (-(-N // 256)) >= 256 else "once_off"
+    on = [("%s:%s:%s" % (once, "gather" if d["gather"] else "packed", "mul" if d["mul"] else "no_mul"), True), (once + ":expert>256", big),
+          ("E=128,N=512,K=64", (E, N, K) == (128, 512, 64)), ("E=256,N=256", (E, N) == (256, 256)), ("N=K=2048:entries>=96", N == 2048 and K == 2048 and ntiles >= 96),
+          ("slot>=T", slot_hi and d["gather"]), (d["dtype"], True), ("pad_rows", pad), ("T=4096", T == 4096)]
+    return {"pp:" + n for n, v in on if v}
 
 
 def check_promised(what, seen, promised, n_cases, default_n):

@@ -1,8 +1,12 @@
 """The packed-kernel fuzzers (tests/test_packed_fuzz_gpu.py) without a GPU: their references (tests/_packed_fuzz.py) against brute force
 on tiny inputs -- a Python loop over entries, rows and columns -- so that a wrong reference cannot agree with a wrong kernel by
 construction; their generators alone (every promised edge class drawn at the default length and seed, no drawn case refused by
-tutel_amd_packed_plan, every reference layout within the plan's bounds); and what the public packed GEMM refuses, on the host."""
+tutel_amd_packed_plan, every reference layout within the plan's bounds); the generator of the training forms
+(tests/test_packed_train_forms_gpu.py), the guard bands (a simulated over-read gives NaN, a simulated over-write trips moat_intact, and
+neither shows without the band) and the row-sampled GEMM reference; and what the public packed GEMM refuses, on the host."""
 import ctypes
+import hashlib
+import json
 import math
 import os
 import sys
@@ -291,6 +295,193 @@ def test_layer_generator_draws_every_promised_class_inside_the_plan(L):
         assert d["experts"] in ("ffn", "swiglu") and d["act"] in ("relu", "gelu", "silu") and d["T"] in F.LAYER_T + [t // 2 ** i for t in F.LAYER_T for i in range(1, 14)]
         seen |= F.layer_classes(d)
     F.check_promised("layer", seen, F.LAYER_PROMISED, DEFAULT_CASES, DEFAULT_CASES)
+
+
+# ---- the training forms: generator, guard bands, row sampling (tests/test_packed_train_forms_gpu.py) ---------------------------------
+def _digest(cases):
+    return hashlib.sha256(json.dumps(cases, sort_keys=True).encode()).hexdigest()
+
+
+def test_the_older_generators_draw_the_cases_they_drew_before_the_training_forms():
+    """digests of the case dicts (json, sorted keys) computed on the commit before gen_train_form_cases existed"""
+    assert _digest(F.gen_gemm_cases(DEFAULT_CASES, SEEDS["gemm"])) == "89214435fbfce59e39284d6b83652b3df51ac7cb302c713d0112db612b2a3dc7"
+    assert _digest(F.gen_gemm_cases(10 * DEFAULT_CASES, SEEDS["gemm"])) == "5c6a68b5459ffdad9363b83ee7ee80d00054a863ebae0f9f383f539fb58a6a78"
+    assert _digest(F.gen_grad_cases(DEFAULT_CASES, SEEDS["grad"])) == "e438d5f66d03dbb842ab06df2426505e1e9b773500fb712ad2f1e5beff162573"
+    assert _digest(F.gen_grad_cases(10 * DEFAULT_CASES, SEEDS["grad"])) == "fc600d723c87e6f64cd7c48cb72106565a6d3b0f6caf17c32fc694a6d5181b90"
+
+
+def _train_ref(L, d):
+    idx = F.train_routing(d)
+    T, E, k = d["T"], d["E"], d["k"]
+    assert idx.shape == (k, T) and k in (1, 2, 3, 4) and k <= E and d["align"] in F.TRAIN_ALIGN
+    live = idx >= 0
+    srt = np.sort(np.where(live, idx, -1 - np.arange(k)[:, None]), axis=0)
+    assert bool((srt[1:] != srt[:-1]).all()) and int(idx.max()) < E, "a token chooses an expert twice"
+    p = _plan(L, T, E, k, 0, d["align"])
+    loc, cnt = F.ref_locations(idx, E)
+    ref = F.ref_layout(cnt, idx, loc, E, 0, d["align"], p.rows_bound)
+    assert int(ref["offsets"][-1]) <= p.rows_bound and ref["ntiles"] <= p.tiles_bound, F.train_tag(d)
+    return ref, p
+
+
+def test_train_form_generator_draws_every_promised_class_within_its_memory_bounds(L):
+    from test_packed_train_forms_gpu import DEFAULT_CASES as N_TRAIN, SEED
+    long = F.gen_train_form_cases(10 * N_TRAIN, SEED)
+    assert long[:N_TRAIN] == F.gen_train_form_cases(N_TRAIN, SEED) and long[:7] == F.gen_train_form_cases(7, SEED)     # case i does not depend on n
+    assert F.gen_gemm_cases(5, SEEDS["gemm"]) == F.gen_gemm_cases(DEFAULT_CASES, SEEDS["gemm"])[:5]
+    seen = set()
+    for d in long:
+        ref, p = _train_ref(L, d)
+        used = int(ref["offsets"][-1])
+        assert used > 0, F.train_tag(d)
+        assert d["T"] in F.TRAIN_T or d["mode"] == "all3"
+        assert d["T"] == 1 or F.free_token(ref["slot"], d["T"]) is not None, "no token left for the slot map's band to name"
+        if d["kind"] == "wgrad":
+            assert d["Na"] in F.WG_N and d["Nb"] in F.WG_N and d["E"] * d["Na"] * d["Nb"] <= (1 << 23)
+            assert used * d["Na"] * d["Nb"] <= 2 * F.F64_BUDGET, F.train_tag(d)
+        else:
+            assert d["N"] % 8 == 0 and d["K"] % 64 == 0 and d["E"] * d["N"] * d["K"] <= (1 << 25)          # weights below 64 MiB
+            assert p.rows_bound * max(d["N"], d["K"]) * 2 <= (1 << 28), F.train_tag(d)                      # no operand above 256 MiB
+            assert (d["act"], d["bias"]) == ("none", False) or d["kind"] == "nmajor"
+            rows = F.tile_sample_rows(ref["tiles"], ref["offsets"], d["seed"])
+            assert min(used, rows.size) * d["N"] * d["K"] <= 2 * F.F64_BUDGET
+        if d["case"] < N_TRAIN:
+            seen |= F.train_classes(d, ref)
+    F.check_promised("train forms", seen, F.TRAIN_PROMISED, N_TRAIN, N_TRAIN)
+
+
+def test_the_two_fixed_cases_and_their_float64_sample(L):
+    """K = N = 2048 over 96 tile-table entries from 3 experts of 8192 rows, n-major gathered and k-major; the sampled rows hold the
+    first and the last row of every tile"""
+    from test_packed_train_forms_gpu import SEED
+    for d, kind in zip(F.gen_train_form_cases(2, SEED), ("nmajor", "pp")):
+        ref, _ = _train_ref(L, d)
+        assert d["kind"] == kind and d["gather"] and (d["N"], d["K"]) == (2048, 2048) and d["act"] == "none"
+        assert ref["rows"].tolist() == [8192] * 3 and ref["ntiles"] == 96 and int(ref["slot"].max()) >= 2 * d["T"]
+        assert bool((np.diff(ref["slot"][:8192] % d["T"]) < 0).any()), "an expert's token rows are read in ascending order"
+        assert 24576 * 2048 * 2048 > F.F64_BUDGET                                 # so the runner samples
+        rows = set(F.tile_sample_rows(ref["tiles"], ref["offsets"], d["seed"]).tolist())
+        assert len(rows) >= 3 * 96
+        for t in range(96):
+            assert 256 * t in rows and 256 * t + 255 in rows
+    # a ragged layout: the last row of a tile is the expert's last row, not the tile's 256th
+    off = [0, 300, 300, 301]
+    rows = F.tile_sample_rows([(0, 0), (0, 256), (2, 300)], off, 5).tolist()
+    assert {0, 255, 256, 299, 300} <= set(rows) and max(rows) == 300
+
+
+@pytest.mark.parametrize("seed", range(200))
+def test_row_sampled_gemm_reference_equals_the_full_one(seed):
+    g = np.random.default_rng(1000 + seed)
+    E = int(g.choice([1, 2, 3, 5]))
+    cnt = g.choice([0, 1, 2, 5, 9], size=E)
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    used = int(off[-1])
+    if used == 0:
+        cnt[0], off, used = 3, off + 3, 3
+        off[0] = 0
+    N, K = int(g.choice([1, 4, 7])), int(g.choice([2, 6]))
+    kmajor, act = bool(g.integers(2)), str(g.choice(["none", "relu", "gelu", "silu"]))
+    dtype = [torch.bfloat16, torch.float16][int(g.integers(2))]
+    tg = torch.Generator().manual_seed(seed)
+    a = torch.randn([used + 2, K], generator=tg).to(dtype)
+    w = torch.randn([E, N, K] if kmajor else [E, K, N], generator=tg).to(dtype)
+    bias = torch.randn([E, N], generator=tg).to(dtype) if g.integers(2) else None
+    mul = torch.randn([used + 2, N], generator=tg).to(dtype) if g.integers(2) else None
+    full = F.ref_gemm(a, w, bias, kmajor, act, mul, off, dtype)
+    rows = np.unique(g.integers(0, used, size=int(g.integers(1, used + 2))))
+    want, exact, mag = F.ref_gemm_rows(a, w, bias, kmajor, act, mul, off, dtype, rows)
+    assert torch.equal(want, full[torch.from_numpy(rows)])
+    assert torch.equal(exact.to(dtype).double(), want) and bool((mag >= 0).all())
+    if act == "none" and mul is None:
+        assert bool((exact.abs() <= mag * (1 + 1e-12) + 1e-300).all())
+
+
+def _raw(view):
+    """the whole buffer of a moated view, and the view's first element in it"""
+    buf, band, _ = view._moat
+    return buf, band
+
+
+def _sim_gather(xv, slot_v, rows, over_row=0, over_slot=0):
+    """a gather as the kernels do it, on the moated buffers themselves: packed row r reads slot entry r + over_slot and token row
+    q % T + over_row -- addressed from the view's first element, so that an index past the view lands in the band"""
+    (xb, x0), (sb, s0) = _raw(xv), _raw(slot_v)
+    T, K = xv.shape
+    out = torch.zeros([rows, K], dtype=xv.dtype)
+    for r in range(rows):
+        q = int(sb[s0 + r + over_slot])
+        if q >= 0:
+            t = q % T + over_row
+            out[r] = xb[x0 + t * K:x0 + (t + 1) * K]
+    return out
+
+
+@pytest.mark.parametrize("dtype,shape", [(torch.bfloat16, [5, 8]), (torch.float16, [1, 2048]), (torch.float32, [3, 136, 8]), (torch.int32, [7]),
+                                         (torch.bfloat16, [3, 4]), (torch.bfloat16, [64])])
+def test_moated_view_is_aligned_contiguous_and_banded(dtype, shape):
+    n = int(np.prod(shape))
+    t = (torch.arange(n) % 100).reshape(shape).to(dtype)
+    v = F.moated(t)
+    buf, band = _raw(v)
+    es = t.element_size()
+    assert v.shape == t.shape and v.dtype == t.dtype and v.is_contiguous() and torch.equal(v, t)
+    assert v.data_ptr() % 16 == 0 and (v.data_ptr() - buf.data_ptr()) == band * es and buf.numel() == 2 * band + n
+    width = n // shape[0] if len(shape) > 1 else 1
+    assert band * es >= 4096 and band >= 64 * width and (band * es) % 16 == 0
+    assert F.moated(t, rows=200)._moat[1] >= 200 * width
+    edge = torch.cat([buf[:band], buf[band + n:]])
+    assert bool(torch.isnan(edge).all()) if dtype.is_floating_point else bool((edge == F.SENTINEL).all())
+    F.moat_intact(v)
+    assert bool((F.moated(t, fill=3)._moat[0][:band] == 3).all())
+
+
+def test_guard_bands_turn_an_overread_into_nan_and_an_overwrite_into_a_failure():
+    """the harness's own mutation test: each simulated off-by-one is caught WITH the band, and would pass unseen without it"""
+    T, K, k = 6, 8, 2
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn([T, K], generator=g).to(torch.bfloat16)
+    slot = np.array([7, 0, -1, 11, 8, 2, 10, 4, -1, -1], dtype=np.int64)     # live rows name tokens 1, 0, 5, 2, 2, 4, 4 of k T = 12 entries
+    free = F.free_token(slot, T)
+    assert free == 3
+    x[free] = float("nan")
+    used = 8
+    xv = F.moated(x)
+    sv = F.moated(torch.from_numpy(slot).int(), fill=free)
+    want = F.gathered(x, slot[:used])
+    assert not bool(torch.isnan(want).any())
+    assert torch.equal(_sim_gather(xv, sv, used), want)
+    # (1) one token row past the array: the last token's neighbour is the band
+    assert bool(torch.isnan(_sim_gather(xv, sv, used, over_row=1)[3]).all())      # row 3 names token T - 1
+    # (2) one slot-map entry past its end: the band's entry names the NaN token
+    assert bool(torch.isnan(_sim_gather(xv, sv, len(slot), over_slot=1)[-1]).all())
+    # without the bands: the same reads inside one shared buffer return somebody else's finite values, and nothing is NaN
+    pool = torch.cat([x.clone().nan_to_num_(0.5).view(-1), torch.ones([4 * K], dtype=x.dtype)])
+    bare = pool[:T * K].view(T, K)
+    bare._moat = (pool, 0, 0)
+    spool = torch.cat([torch.from_numpy(slot).int(), torch.zeros([4], dtype=torch.int32)])
+    sbare = spool[:len(slot)]
+    sbare._moat = (spool, 0, 0)
+    assert not bool(torch.isnan(_sim_gather(bare, sbare, used, over_row=1)).any())
+    assert not bool(torch.isnan(_sim_gather(bare, sbare, len(slot), over_slot=1)).any())
+    # (3) a store one row past the output (and one before it) trips moat_intact; a store inside does not
+    for dtype in (torch.bfloat16, torch.float32):
+        o = F.moated(torch.full([4, K], 3.0, dtype=dtype), fill=F.OUT_FILL)
+        buf, band = _raw(o)
+        o[3] = 1.0
+        F.moat_intact(o)
+        buf[band + 4 * K:band + 5 * K] = 1.0
+        with pytest.raises(AssertionError, match="after"):
+            F.moat_intact(o)
+        o = F.moated(torch.full([4, K], 3.0, dtype=dtype), fill=F.OUT_FILL)
+        o._moat[0][band - 1] = 1.0
+        with pytest.raises(AssertionError, match="before"):
+            F.moat_intact(o)
+    n = F.moated(torch.zeros([4], dtype=torch.float16))       # a NaN band is compared by its bits: NaN != NaN does not fool it
+    F.moat_intact(n)
+    n._moat[0][0] = 0.0
+    with pytest.raises(AssertionError):
+        F.moat_intact(n)
 
 
 # ---- the public packed GEMM on the host: what it refuses, before anything is enqueued -----------------------------------------------

@@ -8,6 +8,9 @@ packed ones.  No case is skipped: the generators draw only shapes the entry poin
   grad     ops.expert_wgrad_packed / expert_bgrad_packed vs fp64 with derived bounds
   decode   ops.fast_decode_packed (bit for bit), ops.gate_grad_packed, and the encode through the packed slot map (bit for bit)
   layer    whole dropless layers with dropless_packed (ffn ReLU / GELU / SiLU and SwiGLU experts, megablocks, negative factors, graph replays) vs the oracle
+The gemm and grad fuzzers keep every operand in a guard band (F.moated: NaN around inputs, a sentinel around `out=` / `accumulate_into=`,
+a valid entry naming a NaN token row around the slot map): a read or store next to an operand fails an assertion.  The forms a SwiGLU
+training step needs (n-major gathered, real routings, wide gradients) have their own fuzzer, tests/test_packed_train_forms_gpu.py.
 The default run takes 60 cases each, --runslow 600; `python tests/test_packed_fuzz_gpu.py [cases] [seed] [what]` runs any length and
 writes packed_<what>_fuzz_<seed>.json beside the records of tests/test_fuzz_gpu.py (the repository's ignored `*_out/` directory)."""
 import json
@@ -116,6 +119,20 @@ def _rows_layout(d):
     return lay, off
 
 
+def _moat_slot_map(lay, used, T):
+    """rebind the layout's slot map to a copy inside a guard band (F.moated) whose entries name a token row of a T-row array that no live
+    row reads -- the caller fills that row with NaN -- or token 0 where every row is read: an index a kernel may follow -> that row | None"""
+    free = F.free_token(lay.slot_map.cpu().numpy()[:used], T) if T > 0 else None
+    lay.slot_map = F.moated(lay.slot_map, fill=free if free is not None else 0)
+    return free
+
+
+def _moats_intact(*named):
+    for what, t in named:
+        if t is not None:
+            F.moat_intact(t, what)
+
+
 def _gemm_tol(dtype):
     # the bar of run_gemm_fuzz / test_ops_gpu._gemm_tol for inputs scaled by 1 / sqrt(K)
     return (2 ** -7, 2e-3) if dtype == torch.bfloat16 else (2 ** -10, 3e-4)
@@ -145,19 +162,26 @@ def run_gemm_fuzz(n_cases, seed, verbose=False):
                 mul = mul.to(dtype)
             if d["gather"]:
                 x = torch.randn([d["T"], K], generator=g).to(dtype)
+                free = _moat_slot_map(lay, used, d["T"])
+                if free is not None:
+                    x[free] = float("nan")      # the token row the slot map's band names: nothing may read it
                 a_rows = F.gathered(x, lay.slot_map.cpu()[:max(used, 1)])
-                a_dev, zero = x.cuda(), torch.zeros([max(K, 8)], dtype=dtype, device="cuda")
+                assert not bool(torch.isnan(a_rows).any())
+                a_dev, zero = F.moated(x, device="cuda"), F.moated(torch.zeros([max(K, 8)], dtype=dtype), device="cuda")
             else:
                 a_rows = torch.randn([rb, K], generator=g).to(dtype)
                 a_rows[used:] = float("nan")
-                a_dev, zero = a_rows.cuda(), None
-            wd, bd, md = w.cuda(), bias.cuda() if bias is not None else None, mul.cuda() if mul is not None else None
+                a_dev, zero = F.moated(a_rows, device="cuda"), None
+                _moat_slot_map(lay, used, 0)
+            wd, bd, md = (F.moated(t, device="cuda") if t is not None else None for t in (w, bias, mul))
 
             def run():
-                o = torch.full([rb, N], 3.0, dtype=dtype, device="cuda")
+                o = F.moated(torch.full([rb, N], 3.0, dtype=dtype, device="cuda"), fill=F.OUT_FILL)
                 ops.expert_gemm_packed(a_dev, wd, bd, kmajor, lay, act=d["act"], gather=d["gather"] or None, zero_row=zero, mul=md, out=o)
+                F.moat_intact(o, "out")
                 return o.cpu()
             got = run()
+            _moats_intact(("a", a_dev), ("w", wd), ("bias", bd), ("mul", md), ("zero_row", zero), ("slot_map", lay.slot_map))
             assert bool((got[used:] == 3.0).all()), "a row at or past offsets[E] was written"
             ref = F.ref_gemm(a_rows, w, bias, kmajor, d["act"], mul, off, dtype)
             rtol, atol = _gemm_tol(dtype)
@@ -199,18 +223,23 @@ def run_grad_fuzz(n_cases, seed, verbose=False):
             lay, off = _rows_layout(d)
             used, rb = int(off[-1]), lay.rows_bound
             slot = lay.slot_map.cpu()[:max(used, 1)]
+            free = _moat_slot_map(lay, used, d["T"])
 
             def operand(N, is_gathered):
                 if is_gathered:
                     x = torch.randn([d["T"], N], generator=g).to(dtype)
-                    return x.cuda(), F.gathered(x, slot)
+                    if free is not None:
+                        x[free] = float("nan")      # the token row the slot map's band names: nothing may read it
+                    rows = F.gathered(x, slot)
+                    assert not bool(torch.isnan(rows).any())
+                    return F.moated(x, device="cuda"), rows
                 t = torch.randn([rb, N], generator=g).to(dtype)
                 t[used:] = float("nan")
-                return t.cuda(), t
+                return F.moated(t, device="cuda"), t
             a_dev, a_rows = operand(Na, d["gather"] == "a")
             b_dev, b_rows = operand(Nb, d["gather"] == "b")
             gather = None if d["gather"] == "none" else d["gather"]
-            zero = torch.zeros([max(Na, Nb, 8)], dtype=dtype, device="cuda") if gather else None
+            zero = F.moated(torch.zeros([max(Na, Nb, 8)], dtype=dtype), device="cuda") if gather else None
             got_d = ops.expert_wgrad_packed(a_dev, b_dev, lay, gather=gather, zero_row=zero)
             got = got_d.cpu()
             ref, bnd = F.ref_wgrad(a_rows, b_rows, off)
@@ -229,6 +258,19 @@ def run_grad_fuzz(n_cases, seed, verbose=False):
                     e, j = _first_violation(viol, viol.shape)
                     raise AssertionError(f"db[{e}][{j}] = {float(db[e, j])} vs {float(dref[e, j])} over {int(n[e])} rows (sum |B| {float(mag[e, j]):.3e})")
                 assert bool((db[empty] == 0).all()), "db of an expert without rows is not exactly zero"
+            # the outputs the caller allocates: the accumulating forms, D + G bit for bit with every band intact
+            G = ops.expert_wgrad_packed(a_dev, b_dev, lay, gather=gather, zero_row=zero, out_dtype=torch.float32)
+            D = F.moated(torch.full([E, Na, Nb], 0.5, device="cuda"), fill=F.OUT_FILL)
+            ops.expert_wgrad_packed(a_dev, b_dev, lay, gather=gather, zero_row=zero, accumulate_into=D)
+            F.moat_intact(D, "dW accumulate_into")
+            assert torch.equal(D, 0.5 + G), "dW: accumulate_into is not D + G bit for bit"
+            if d["gather"] != "b":
+                g32 = ops.expert_bgrad_packed(b_dev, lay, out_dtype=torch.float32)
+                db_acc = F.moated(torch.full([E, Nb], 0.5, device="cuda"), fill=F.OUT_FILL)
+                ops.expert_bgrad_packed(b_dev, lay, accumulate_into=db_acc)
+                F.moat_intact(db_acc, "db accumulate_into")
+                assert torch.equal(db_acc, 0.5 + g32), "db: accumulate_into is not D + G bit for bit"
+            _moats_intact(("a", a_dev), ("b", b_dev), ("zero_row", zero), ("slot_map", lay.slot_map))
         except Exception as ex:  # noqa: BLE001
             _fail(bad, tag, ex, verbose)
         if verbose and (d["case"] + 1) % 100 == 0:
