@@ -1138,3 +1138,59 @@ def test_layer_input_that_starts_at_an_odd_element(oracle, dtype):
             assert xv.data_ptr() % 16 != 0
             y = layer(xv)
             assert torch.equal(y, want) and float(y.l_aux) == float(want.l_aux), off
+
+
+def test_mixed_workspace_kinds_share_one_cache(oracle):
+    """One layer run in turn with a static capacity, dropless on the padded layout and dropless on the packed layout: the three
+    forwards of impls/ep_native.py keep their workspaces in ONE least-recently-used cache per layer (`_workspace`), each kind hit
+    by its own rule.  Every output equals, bit for bit, what a fresh layer computes for that batch alone in that mode (and packed
+    equals padded); the cache never exceeds WS_MAX; it allocates exactly the (kind, bucket) pairs the sequence needs, derived here
+    from the bucket functions; and a graph captured on the packed layout keeps replaying after the cache has been dropped and
+    refilled by the other modes -- GraphedForward pins the workspaces its kernels point into."""
+    from tutel_amd.impls import ep_native as N
+    from tutel_amd.impls.graph import GraphedForward
+    M = H = 128                                    # the smallest shape the packed plan accepts
+    E, k, dtype = 8, 2, torch.bfloat16
+    x700, *weights = oracle.make_problem(700, M, H, E, dtype=dtype, seed=91)
+    xs = {700: x700.cuda(), 300: torch.randn([300, M], generator=torch.Generator().manual_seed(92)).to(dtype).cuda()}
+
+    def run(layer, mode, T):
+        layer.dropless_packed = mode == "packed"
+        with torch.no_grad():
+            y = layer(xs[T], **({"capacity_factor": 1.0} if mode == "static" else {})).clone()
+        assert mode != "packed" or layer._dropless_packed_ran is True
+        assert len(layer._ep_workspaces) <= N.WS_MAX
+        return y
+
+    want = {(mode, T): run(make_layer(M, H, E, k, 0.0, dtype, weights).eval(), mode, T) for mode in ("static", "padded", "packed")
+            for T in (700, 300)}
+    for T in (700, 300):
+        assert torch.equal(want["packed", T], want["padded", T])
+    layer = make_layer(M, H, E, k, 0.0, dtype, weights).eval()
+    have = []   # the cache as the bucket functions predict it: (kind, T_cap, C_cap), fewer than WS_MAX entries, so nothing leaves
+
+    def ask(kind, T, C=0):
+        """padded: any workspace with T_cap >= T and C_cap >= C; packed: T_cap >= T (its bytes grow with T_cap, same limit and alignment)"""
+        for h in have:
+            if h[0] == kind and h[1] >= T and h[2] >= C:
+                return h
+        have.append((kind, N._bucket_tokens(T), N._bucket_capacity(C) if kind == "padded" else 0))
+        return have[-1]
+
+    for mode, T in (("static", 700), ("padded", 300), ("packed", 700), ("packed", 300), ("static", 300), ("packed", 700)):
+        assert torch.equal(run(layer, mode, T), want[mode, T]), (mode, T)
+        if mode == "static":
+            ask("padded", T, layer._static_capacity(T, E, k, 1.0, 1))
+        elif mode == "padded":   # the first guess of _run_native_moe, then (only if the batch's load exceeds the workspace found) one grown
+            used = int(layer.protected_shape[1])
+            if used > ask("padded", T, (k * ((T + E - 1) // E) * 3 // 2 + 31) // 32 * 32)[2]:
+                ask("padded", T, (used * 5 // 4 + 31) // 32 * 32)
+        else:
+            ask("packed", T)
+    assert layer._ep_workspace_allocations == len(have) < N.WS_MAX, (layer._ep_workspace_allocations, have)
+    g = GraphedForward(layer, xs[300], dropless_packed=True)
+    assert torch.equal(g(xs[300]), want["packed", 300])
+    N.forget_workspaces(layer)   # the graph's workspace now lives by the pin alone
+    for mode, T in (("static", 700), ("padded", 300), ("packed", 700)):
+        assert torch.equal(run(layer, mode, T), want[mode, T]), (mode, T)
+    assert torch.equal(g(xs[300]), want["packed", 300])

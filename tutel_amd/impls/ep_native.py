@@ -15,6 +15,7 @@ This module owns the host side of that call:
   * the workspace of the pipeline, cached per (layer, shape, stream): buffers live as long as the
     layer, calls on one stream are ordered, so nothing is allocated per forward except the output.
 """
+import collections
 import ctypes
 import logging
 import os
@@ -46,7 +47,6 @@ IPC_TIMEOUT_MS = int(os.environ.get("TUTEL_AMD_EP_TIMEOUT_MS", "120000"))
 _FORCE_COMM = False  # test hook: run a single rank through a real 1-rank RCCL communicator (staged pipeline, both streams)
 _comms = {}      # (ranks of the group, device) -> EpComm | False (creation failed: do not retry)
 _groups = {}
-_zero_rows = {}
 
 
 class Segment:
@@ -312,13 +312,9 @@ def _create(group, device):
     t = idbuf.to(device) if on_dev else idbuf
     dist.broadcast(t, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
     idbytes = bytes(t.cpu().tolist())
-
-    def agree(v):  # all ranks continue only if every rank is fine (a rank that skipped a collective would hang the others)
-        f = torch.tensor([v], dtype=torch.int32, device=device if on_dev else "cpu")
-        dist.all_reduce(f, op=dist.ReduceOp.MIN, group=group)
-        return int(f)
     comm = None
-    ok = agree(ok)     # every rank resolved RCCL and rank 0 drew an id: only then is ncclCommInitRank (collective) entered
+    # all ranks continue only if every rank is fine (a rank that skipped a collective would hang the others)
+    ok = _agree(ok, group, device)     # every rank resolved RCCL and rank 0 drew an id: only then is ncclCommInitRank (collective) entered
     if ok:
         try:
             with torch.cuda.device(device):
@@ -328,7 +324,7 @@ def _create(group, device):
             logging.warning("tutel_amd: native expert-parallel communicator could not be created on rank %d (%s)", rank, ex)
             ok = 0
 
-    ok = agree(ok)
+    ok = _agree(ok, group, device)
     if ok:
         try:
             # self-check: block p of my send buffer carries (my rank, p); after the exchange block r must carry (r, my rank)
@@ -343,7 +339,7 @@ def _create(group, device):
         except Exception as ex:
             logging.warning("tutel_amd: native expert-parallel communicator failed its self-check on rank %d (%s)", rank, ex)
             ok = 0
-        ok = agree(ok)
+        ok = _agree(ok, group, device)
     if not ok:
         if handle:
             L.tutel_amd_ep_comm_destroy(handle)
@@ -528,6 +524,114 @@ def _bucket_capacity(C):
     return 1 << (C - 1).bit_length()
 
 
+def _workspace(layer, static_key, T, C, make, exact_capacity=False, fits=None):
+    """least-recently-used cache of at most WS_MAX workspaces per layer, of every kind (the only code that touches
+    layer._ep_workspaces and _ep_workspace_allocations); a hit is ANY workspace of the same configuration that is large enough
+    (variable token counts -- serving -- keep hitting the largest one allocated so far): T_cap >= T and the caller's size rule.
+    The padded pipelines' rule is the capacity: C_cap >= C, or with exact_capacity (the IPC transport) C_cap == bucket(C) -- the
+    capacity bucket decides WHICH peer-mapped segment the kernels store into and where `back` starts inside it, so it must be the
+    same on every rank for a given call: a function of the call's (agreed) capacity alone, never of which workspaces this rank
+    happens to have cached (its token count differs from its peers': ADVICE r4 high); only the token bucket, which no peer ever
+    sees, may be larger than needed.  The packed layout has no capacity (C = None, C_cap = 0 in its key): its rule is `fits(ws)`."""
+    cache = layer.__dict__.get("_ep_workspaces")
+    if not isinstance(cache, collections.OrderedDict):
+        cache = layer.__dict__["_ep_workspaces"] = collections.OrderedDict()
+    C_cap = _bucket_capacity(C) if C is not None else 0
+    if fits is None:
+        fits = (lambda ws: ws.C_cap == C_cap) if exact_capacity else (lambda ws: ws.C_cap >= C)
+    for key, ws in cache.items():
+        if key[0] == static_key and ws.T_cap >= T and fits(ws):
+            cache.move_to_end(key)
+            return ws
+    T_cap = _bucket_tokens(T)
+    ws = make(T_cap, C_cap)
+    cache[(static_key, T_cap, C_cap)] = ws
+    layer.__dict__["_ep_workspace_allocations"] = layer.__dict__.get("_ep_workspace_allocations", 0) + 1
+    while len(cache) > WS_MAX:
+        cache.popitem(last=False)
+    return ws
+
+
+# ---------------------------------------------------------------------------------------------
+# what the workspaces of the three forwards share: the static argument fields and the routing buffers
+# ---------------------------------------------------------------------------------------------
+def _static_args(layer, x, E, k, H, world=1, degree=1, fuse=True):
+    """an EpArgs with the fields that no call of a workspace changes"""
+    ex = layer.experts
+    a = _lib.EpArgs()
+    a.M, a.H, a.M_out, a.num_experts, a.world, a.k, a.degree = x.shape[1], H, ex.output_dim, E, world, k, degree
+    a.allow_sliced, a.dtype, a.act = 1, ops._DT[x.dtype], ops.ACT_CODES[ex.fused_activation()]
+    a.is_postscore, a.fuse_encode = int(bool(layer.is_postscore)), int(fuse)
+    return a
+
+
+def _add_routing(ws, a, logits, k, T_cap, dev, scratch_tokens=()):
+    """give `ws` the routing buffers its calls reuse -- idx / loc / gates [k, T_cap], stats, the routing scratch `ws` for the
+    largest tiling any T takes (<= 128 token tiles, csrc/routing.hip) and for `scratch_tokens` -- and the split-K partial sums
+    of the in-call gate projection (on demand: _bind_gate); returns the MoeArgs around a COPY of `a` that names them"""
+    E = logits.shape[1]
+    ws.idx = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
+    ws.loc = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
+    ws.gates = torch.empty([k, T_cap], dtype=logits.dtype, device=dev)
+    ws.stats = torch.empty([1], dtype=torch.int32, device=dev)
+    scratch = max(int(_lib.lib().tutel_amd_routing_workspace_bytes(t, E, k)) for t in (64 * 128,) + tuple(scratch_tokens))
+    ws.ws = torch.empty([max(scratch, 4)], dtype=torch.uint8, device=dev)
+    ws.gate_partials, ws.gate_partials_keep = None, []
+    m = _lib.MoeArgs()
+    m.ep = a
+    m.ep.idx, m.ep.loc, m.ep.gates = ws.idx.data_ptr(), ws.loc.data_ptr(), ws.gates.data_ptr()
+    m.logits_dtype = ops._DT[logits.dtype]
+    m.ws, m.ws_bytes, m.stats = ws.ws.data_ptr(), ws.ws.numel(), ws.stats.data_ptr()
+    return m
+
+
+# ---------------------------------------------------------------------------------------------
+# what every call binds: the expert operands, the row counts, the gate source; and the routing it may export
+# ---------------------------------------------------------------------------------------------
+def _bind_operands(a, ex, x, params):
+    """this call's tokens, expert parameters (w1, b1, w2, b2, w2_kmajor) and a fresh output -> y [T, M_out]"""
+    w1, b1, w2, b2, kmajor = params
+    y = torch.empty([x.shape[0], ex.output_dim], dtype=x.dtype, device=x.device)
+    a.T, a.x, a.y = x.shape[0], x.data_ptr(), y.data_ptr()
+    a.w1, a.w2, a.w2_kmajor = w1.data_ptr(), w2.data_ptr(), int(kmajor)
+    a.b1 = b1.data_ptr() if b1 is not None else None
+    a.b2 = b2.data_ptr() if b2 is not None else None
+    return y
+
+
+def _bind_row_counts(a, counts, align):
+    """align = megablocks_size > 0 (single rank): the GEMMs stop at each expert's row count, rounded up to it; else no counts"""
+    a.row_counts, a.row_align = (counts.data_ptr(), int(align)) if align > 0 else (None, 1)
+
+
+def _bind_gate(ws, m, layer, x, logits, gate_w, normalize_gate, export_logits):
+    """where the call's logits come from: the tensor, or -- gate_w given, `logits` then a meta tensor (shape / dtype only) -- the
+    projection inside the call (csrc/gate_proj.hip), whose partial sums live in the workspace and grow by replacement.
+    export_logits: the padded forward hands the projected logits to layer.last_logits when the layer keeps its routing"""
+    m.normalize_gate = int(bool(normalize_gate))
+    if gate_w is None:
+        m.logits, m.gate_w, m.logits_out = logits.data_ptr(), None, None
+        return
+    T, E = logits.shape
+    need = ops.gate_proj_splits(T, x.shape[1], E, x.dtype) * T * E
+    if ws.gate_partials is None or ws.gate_partials.numel() < need:
+        ws.gate_partials_keep.append(ws.gate_partials)   # a captured graph may still hold the old pointer
+        ws.gate_partials = torch.empty([need], dtype=torch.float32, device=x.device)
+    m.logits, m.gate_w, m.logits_out = None, gate_w.data_ptr(), None
+    m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
+    if export_logits:
+        keep = getattr(layer, "_keep_routing", False)
+        layer.last_logits = torch.empty([T, E], dtype=x.dtype, device=x.device) if keep else None
+        m.logits_out = ops._ptr(layer.last_logits)
+
+
+def _export_routing(layer, ws, k, T):
+    """tests (layer._keep_routing): [k, T] copies of the workspace's routing arrays (its rows are T apart)"""
+    if getattr(layer, "_keep_routing", False):
+        n = k * T
+        layer.last_routing = (ws.idx.view(-1)[:n].view(k, -1).clone(), ws.loc.view(-1)[:n].view(k, -1).clone())
+
+
 class _Workspace:
     """the buffers of one pipeline configuration + its argument struct.  Buffers are sized for a BUCKET (T_cap tokens,
     C_cap rows per expert): any call with T <= T_cap and capacity <= C_cap reuses them -- the strides the kernels use come
@@ -542,10 +646,7 @@ class _Workspace:
         E_loc = E // W
         self.T_cap, self.C_cap = int(T_cap), int(C_cap)
         fuse = comm is None and degree <= 1 and layer.is_postscore and FUSE_ENCODE
-        a = _lib.EpArgs()
-        a.M, a.H, a.M_out, a.num_experts, a.world, a.k, a.degree = M, H, Mo, E, W, k, max(degree, 1)
-        a.allow_sliced, a.dtype, a.act = 1, ops._DT[dt], ops.ACT_CODES[ex.fused_activation()]
-        a.is_postscore, a.fuse_encode = int(bool(layer.is_postscore)), int(fuse)
+        a = _static_args(layer, x, E, k, H, W, max(degree, 1), fuse)
         self.bufs = {}
 
         def buf(name, rows, cols, alias=None):
@@ -571,40 +672,12 @@ class _Workspace:
             buf("recv", E * C_cap, M, alias="enc" if comm is None else None)
             buf("back", E * C_cap, Mo, alias="send" if comm is None else None)
         else:
-            z = _zero_rows.get((dev, dt))
-            if z is None or z.numel() < M:
-                z = _zero_rows[(dev, dt)] = torch.zeros([max(M, 8192)], dtype=dt, device=dev)
-            self.bufs["zero_row"] = z
+            z = self.bufs["zero_row"] = ops.zero_row(M, dt, dev)
             a.zero_row = z.data_ptr()
         self.args, self.comm = a, comm
         if comm is not None and hasattr(comm, "register"):
             for t in self.bufs.values():
                 comm.register(t)
-
-
-def _workspace(layer, static_key, T, C, make, exact_capacity=False):
-    """least-recently-used cache of at most WS_MAX workspaces per layer; a hit is ANY workspace of the same configuration
-    that is large enough (variable token counts -- serving -- keep hitting the largest one allocated so far).
-    exact_capacity (the IPC transport): the capacity bucket decides WHICH peer-mapped segment the kernels store into and where
-    `back` starts inside it, so it must be the same on every rank for a given call -- a function of the call's (agreed) capacity
-    alone, never of which workspaces this rank happens to have cached (its token count differs from its peers': ADVICE r4 high).
-    A hit then needs C_cap == bucket(C); only the token bucket, which no peer ever sees, may be larger than needed."""
-    import collections
-    cache = layer.__dict__.get("_ep_workspaces")
-    if not isinstance(cache, collections.OrderedDict):
-        cache = layer.__dict__["_ep_workspaces"] = collections.OrderedDict()
-    C_cap = _bucket_capacity(C)
-    for key, ws in cache.items():
-        if key[0] == static_key and ws.T_cap >= T and (ws.C_cap == C_cap if exact_capacity else ws.C_cap >= C):
-            cache.move_to_end(key)
-            return ws
-    T_cap = _bucket_tokens(T)
-    ws = make(T_cap, C_cap)
-    cache[(static_key, T_cap, C_cap)] = ws
-    layer.__dict__["_ep_workspace_allocations"] = layer.__dict__.get("_ep_workspace_allocations", 0) + 1
-    while len(cache) > WS_MAX:
-        cache.popitem(last=False)
-    return ws
 
 
 def forward(layer, x, crit, degree):
@@ -615,32 +688,21 @@ def forward(layer, x, crit, degree):
     comm = communicator(layer.group, x.device) if with_comm else None
     if with_comm and comm is None:
         return None
-    if getattr(layer, "megablocks_size", 0) > 0 and with_comm:
+    mega = int(getattr(layer, "megablocks_size", 0))
+    if mega > 0 and with_comm:
         return None
     if not with_comm:
         degree = 1  # a single rank has nothing to overlap (the reference returns expert_fn(input) there, overlap.py:16-17)
     k = crit.idx2d.shape[0]
-    key = ("ep", x.shape[1], x.dtype, x.device, crit[0], k, degree, bool(layer.is_postscore), ex.fused_activation(), ops._stream(), with_comm,
-           bool(comm is not None and comm.ipc))
-    ws = _workspace(layer, key, x.shape[0], crit[4], lambda Tc, Cc: _Workspace(layer, x, crit[0], Cc, k, degree, comm, Tc),
-                    exact_capacity=bool(comm is not None and comm.ipc))
+    ipc = bool(comm is not None and comm.ipc)
+    key = ("ep", x.shape[1], x.dtype, x.device, crit[0], k, degree, bool(layer.is_postscore), ex.fused_activation(), ops._stream(), with_comm, ipc)
+    ws = _workspace(layer, key, x.shape[0], crit[4], lambda Tc, Cc: _Workspace(layer, x, crit[0], Cc, k, degree, comm, Tc), exact_capacity=ipc)
     a = ws.args
-    a.T, a.capacity = x.shape[0], crit[4]
-    w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
+    y = _bind_operands(a, ex, x, ex.fused_params(x.dtype))
+    _bind_row_counts(a, getattr(layer, "dispatch_count", None), mega)
     gates = crit.gates2d
-    y = torch.empty([x.shape[0], ex.output_dim], dtype=x.dtype, device=x.device)
-    a.w2_kmajor = int(kmajor)
-    a.x, a.slot_map, a.idx, a.loc, a.gates = x.data_ptr(), crit.slot_map.data_ptr(), crit.idx2d.data_ptr(), crit.loc2d.data_ptr(), gates.data_ptr()
-    a.gate_dtype = ops._DT[gates.dtype]
-    a.w1, a.w2 = w1.data_ptr(), w2.data_ptr()
-    a.b1 = b1.data_ptr() if b1 is not None else None
-    a.b2 = b2.data_ptr() if b2 is not None else None
-    a.y = y.data_ptr()
-    mega = int(getattr(layer, "megablocks_size", 0))
-    if mega > 0 and not with_comm:
-        a.row_counts, a.row_align = layer.dispatch_count.data_ptr(), mega
-    else:
-        a.row_counts, a.row_align = None, 1
+    a.capacity, a.gate_dtype = crit[4], ops._DT[gates.dtype]
+    a.slot_map, a.idx, a.loc, a.gates = crit.slot_map.data_ptr(), crit.idx2d.data_ptr(), crit.loc2d.data_ptr(), gates.data_ptr()
     _lib.check(_lib.lib().tutel_amd_ep_forward(comm.handle if comm is not None else None, ctypes.byref(a), ops._stream()),
                "tutel_amd_ep_forward")
     layer.protected_shape = torch.Size([layer.num_local_experts, W * crit[4], ex.output_dim])
@@ -654,28 +716,15 @@ class _MoeWorkspace(_Workspace):
     """_Workspace + the routing buffers (idx / loc / gates / slot map / per-tile histograms), all reused call after call"""
 
     def __init__(self, layer, x, logits, k, capacity, degree, comm, T_cap):
-        E, T = logits.shape[1], int(T_cap)
-        dev = x.device
+        E, T, dev = logits.shape[1], int(T_cap), x.device
         super().__init__(layer, x, E, capacity, k, degree, comm, T_cap)
-        self.idx = torch.empty([k, T], dtype=torch.int32, device=dev)
-        self.loc = torch.empty([k, T], dtype=torch.int32, device=dev)
-        self.gates = torch.empty([k, T], dtype=logits.dtype, device=dev)
+        m = self.margs = _add_routing(self, self.args, logits, k, T, dev)
         self.slot_map = torch.empty([E * capacity], dtype=torch.int32, device=dev)
-        # routing scratch for the largest tiling any T takes (<= 128 token tiles, csrc/routing.hip)
-        self.ws = torch.empty([max(int(_lib.lib().tutel_amd_routing_workspace_bytes(64 * 128, E, k)), 4)], dtype=torch.uint8, device=dev)
-        self.stats = torch.empty([1], dtype=torch.int32, device=dev)
+        m.ep.slot_map = self.slot_map.data_ptr()
         # the dropless capacity is read back into this workspace's own pinned word (no process-global slot: ADVICE r2)
         self.cap_host = torch.zeros([1], dtype=torch.int32).pin_memory()
         self.cap_c = ctypes.c_int.from_address(self.cap_host.data_ptr())
-        m = _lib.MoeArgs()
-        m.ep = self.args
-        m.ep.slot_map, m.ep.idx, m.ep.loc, m.ep.gates = (self.slot_map.data_ptr(), self.idx.data_ptr(), self.loc.data_ptr(),
-                                                          self.gates.data_ptr())
-        m.logits_dtype = ops._DT[logits.dtype]
-        m.ws, m.ws_bytes, m.stats = self.ws.data_ptr(), self.ws.numel(), self.stats.data_ptr()
         m.capacity_out = ctypes.pointer(self.cap_c)
-        self.margs = m
-        self.gate_partials, self.gate_partials_keep = None, []   # split-K partial sums of the in-call gate projection (on demand)
         # fused location (single rank; csrc/expert_gemm.hip FL kernels): the top-k kernel's byte copy of idx, k * T bytes padded to 16
         self.fl_ws = None
         if comm is None and _FUSED_LOCATION:
@@ -698,47 +747,24 @@ def forward_from_logits(layer, x, logits, k, capacity, degree, normalize_gate, w
         return None
     if not with_comm:
         degree = 1
+    T, E = x.shape[0], logits.shape[1]
     sizes = layer.__dict__.setdefault("_ep_dropless_cap", {})
-    skey = (tuple(x.shape), logits.shape[1], k)
+    skey = (tuple(x.shape), E, k)
     if dropless is not None:
         capacity = max(capacity, sizes.get(skey, 0))
+    ipc = bool(comm is not None and comm.ipc)
+    key = ("moe", x.shape[1], x.dtype, x.device, E, logits.dtype, k, degree, bool(layer.is_postscore), ex.fused_activation(), ops._stream(),
+           with_comm, ipc)
     for attempt in range(4):
-        key = ("moe", x.shape[1], x.dtype, x.device, logits.shape[1], logits.dtype, k, degree, bool(layer.is_postscore),
-               ex.fused_activation(), ops._stream(), with_comm, bool(comm is not None and comm.ipc))
-        ws = _workspace(layer, key, x.shape[0], capacity, lambda Tc, Cc: _MoeWorkspace(layer, x, logits, k, Cc, degree, comm, Tc),
-                        exact_capacity=bool(comm is not None and comm.ipc))
+        ws = _workspace(layer, key, T, capacity, lambda Tc, Cc: _MoeWorkspace(layer, x, logits, k, Cc, degree, comm, Tc), exact_capacity=ipc)
         m = ws.margs
         a = m.ep
-        a.T = x.shape[0]
-        w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
-        dev = x.device
-        y = torch.empty([x.shape[0], ex.output_dim], dtype=x.dtype, device=dev)
-        cnt = torch.empty([logits.shape[1]], dtype=torch.int32, device=dev)
-        l_aux = torch.empty([1], dtype=logits.dtype, device=dev) if want_loss else None
-        a.w2_kmajor = int(kmajor)
-        a.x, a.w1, a.w2 = x.data_ptr(), w1.data_ptr(), w2.data_ptr()
-        a.b1 = b1.data_ptr() if b1 is not None else None
-        a.b2 = b2.data_ptr() if b2 is not None else None
-        a.y = y.data_ptr()
-        if megablocks_size > 0 and not with_comm:
-            a.row_counts, a.row_align = cnt.data_ptr(), int(megablocks_size)
-        else:
-            a.row_counts, a.row_align = None, 1
-        m.normalize_gate = int(bool(normalize_gate))
-        if gate_w is None:
-            m.logits, m.gate_w, m.logits_out = logits.data_ptr(), None, None
-        else:   # `logits` is a meta tensor (shape / dtype only): the projection runs inside the call (csrc/gate_proj.hip)
-            need = ops.gate_proj_splits(x.shape[0], x.shape[1], logits.shape[1], x.dtype) * x.shape[0] * logits.shape[1]
-            if ws.gate_partials is None or ws.gate_partials.numel() < need:
-                ws.gate_partials_keep.append(ws.gate_partials)   # a captured graph may still hold the old pointer
-                ws.gate_partials = torch.empty([need], dtype=torch.float32, device=dev)
-            m.logits, m.gate_w = None, gate_w.data_ptr()
-            m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
-            layer.last_logits = torch.empty(list(logits.shape), dtype=x.dtype, device=dev) if getattr(layer, "_keep_routing", False) else None
-            m.logits_out = layer.last_logits.data_ptr() if layer.last_logits is not None else None
-        m.dispatch_count = cnt.data_ptr()
-        m.l_aux = l_aux.data_ptr() if l_aux is not None else None
-        cap_out = ws.cap_c
+        y = _bind_operands(a, ex, x, ex.fused_params(x.dtype))
+        cnt = torch.empty([E], dtype=torch.int32, device=x.device)
+        l_aux = torch.empty([1], dtype=logits.dtype, device=x.device) if want_loss else None
+        _bind_row_counts(a, cnt, 0 if with_comm else megablocks_size)
+        _bind_gate(ws, m, layer, x, logits, gate_w, normalize_gate, export_logits=True)
+        m.dispatch_count, m.l_aux = cnt.data_ptr(), (l_aux.data_ptr() if want_loss else None)
         if dropless is not None:
             a.capacity = 0
             m.capacity_limit, m.alignment, m.max_capacity = int(dropless[0]), int(dropless[1]), int(ws.C_cap)
@@ -747,14 +773,12 @@ def forward_from_logits(layer, x, logits, k, capacity, degree, normalize_gate, w
             m.capacity_limit, m.alignment, m.max_capacity = 0, 1, int(capacity)
         rc = _lib.lib().tutel_amd_moe_forward(comm.handle if comm is not None else None, ctypes.byref(m), ops._stream())
         if rc == _lib.EAGAIN and dropless is not None:   # the batch needs more rows per expert than the workspace holds: grow, redo
-            capacity = (int(cap_out.value) * 5 // 4 + 31) // 32 * 32
+            capacity = (int(ws.cap_c.value) * 5 // 4 + 31) // 32 * 32
             sizes[skey] = capacity
             continue
         _lib.check(rc, "tutel_amd_moe_forward")
-        used = int(cap_out.value) if dropless is not None else int(capacity)
-        if getattr(layer, "_keep_routing", False):   # tests: [k, T] views of the workspace's routing arrays (rows are T apart)
-            n = k * x.shape[0]
-            layer.last_routing = (ws.idx.view(-1)[:n].view(k, -1).clone(), ws.loc.view(-1)[:n].view(k, -1).clone())
+        used = int(ws.cap_c.value) if dropless is not None else int(capacity)
+        _export_routing(layer, ws, k, T)
         layer.protected_shape = torch.Size([layer.num_local_experts, W * used, ex.output_dim])
         return y, (l_aux[0] if l_aux is not None else None), cnt, used
     raise _lib.TutelAmdError("tutel_amd_moe_forward: the dropless capacity kept growing")
@@ -763,6 +787,11 @@ def forward_from_logits(layer, x, logits, k, capacity, degree, normalize_gate, w
 # ---------------------------------------------------------------------------------------------
 # dropless routing without a host synchronisation: the packed layout (tutel_amd_moe_forward_packed, csrc/dropless.hip)
 # ---------------------------------------------------------------------------------------------
+def dropless_row_limit(T, E, k, cf):
+    """rows an expert may take in a dropless forward: k * int(-cf * ceil(T / E)) for capacity_factor cf < 0, else 0 (no limit)"""
+    return k * int(-cf * ((T + E - 1) // E)) if cf < 0 else 0
+
+
 def packed_plan(T, E, k, M, H, M_out, dtype, capacity_limit, alignment):
     """tutel_amd_packed_plan as a dict (host arithmetic only, no GPU), or (None, reason) when the shape is not covered"""
     p = _lib.PackedPlan()
@@ -799,126 +828,79 @@ def _swiglu_unsupported(ex, dtype):
     return None
 
 
-def packed_unsupported(layer, T, E, k, M, dtype, capacity_limit, alignment):
-    """why this layer's dropless forward cannot take the packed layout (None: it can)"""
+def packed_cover(layer, T, E, k, M, dtype, capacity_limit, alignment):
+    """(plan, None) when this layer's dropless forward can take the packed layout -- the plan of THIS call, to hand to
+    forward_packed(plan=...) -- else (None, why not)"""
     ex = layer.experts
     if layer.world_size != 1:
-        return "the packed dropless layout runs on a single rank only"
+        return None, "the packed dropless layout runs on a single rank only"
     if not layer.is_postscore:
-        return "the packed dropless layout needs is_postscore=True (gates applied in the decode)"
+        return None, "the packed dropless layout needs is_postscore=True (gates applied in the decode)"
     if _swiglu(ex):
         why = _swiglu_unsupported(ex, dtype)
         if why is not None:
-            return why
+            return None, why
     elif not ex.w2_kmajor_now():
-        return "the packed dropless layout needs the k-major fc2 copy of inference (eval mode, no gradient)"
-    plan, why = packed_plan(T, E, k, M, _hidden_size(ex), ex.output_dim, dtype, capacity_limit, alignment)
-    return why if plan is None else None
+        return None, "the packed dropless layout needs the k-major fc2 copy of inference (eval mode, no gradient)"
+    return packed_plan(T, E, k, M, _hidden_size(ex), ex.output_dim, dtype, capacity_limit, alignment)
+
+
+def packed_unsupported(layer, T, E, k, M, dtype, capacity_limit, alignment):
+    """why this layer's dropless forward cannot take the packed layout (None: it can)"""
+    return packed_cover(layer, T, E, k, M, dtype, capacity_limit, alignment)[1]
 
 
 class _PackedWorkspace:
     """routing buffers + the packed workspace of tutel_amd_moe_forward_packed, sized by the host bound for T_cap tokens: nothing
     in it depends on the routing, so a captured forward replays for any batch of the same token count"""
 
-    def __init__(self, layer, x, logits, k, T_cap, capacity_limit, alignment):
-        ex = layer.experts
-        E, dev, dt = logits.shape[1], x.device, x.dtype
-        M, H, Mo = x.shape[1], _hidden_size(ex), ex.output_dim
+    def __init__(self, layer, x, logits, k, T_cap, capacity_limit, alignment, plan=None):
+        E, dev = logits.shape[1], x.device
+        H = _hidden_size(layer.experts)
         self.T_cap = int(T_cap)
-        plan, why = packed_plan(T_cap, E, k, M, H, Mo, dt, capacity_limit, alignment)
-        if plan is None:
-            raise _lib.TutelAmdError(why)
+        if plan is None:   # (the caller hands over its own plan when the bucket is its token count)
+            plan, why = packed_plan(T_cap, E, k, x.shape[1], H, layer.experts.output_dim, x.dtype, capacity_limit, alignment)
+            if plan is None:
+                raise _lib.TutelAmdError(why)
         self.pk_bytes = plan["ws_bytes"]
         self.packed = torch.empty([max(self.pk_bytes, 256)], dtype=torch.uint8, device=dev)
         self.offsets = torch.empty([E + 1], dtype=torch.int32, device=dev)
         self.capacity = torch.zeros([1], dtype=torch.int32, device=dev)
-        self.idx = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
-        self.loc = torch.empty([k, T_cap], dtype=torch.int32, device=dev)
-        self.gates = torch.empty([k, T_cap], dtype=logits.dtype, device=dev)
-        self.stats = torch.empty([1], dtype=torch.int32, device=dev)
-        rb = max(int(_lib.lib().tutel_amd_routing_workspace_bytes(64 * 128, E, k)),
-                 int(_lib.lib().tutel_amd_routing_workspace_bytes(T_cap, E, k)), 4)
-        self.ws = torch.empty([rb], dtype=torch.uint8, device=dev)
-        z = _zero_rows.get((dev, dt))
-        if z is None or z.numel() < M:
-            z = _zero_rows[(dev, dt)] = torch.zeros([max(M, 8192)], dtype=dt, device=dev)
-        self.zero_row = z
-        self.gate_partials, self.gate_partials_keep = None, []
-        a = _lib.EpArgs()
-        a.M, a.H, a.M_out, a.num_experts, a.world, a.k, a.degree = M, H, Mo, E, 1, k, 1
-        a.allow_sliced, a.dtype, a.act = 1, ops._DT[dt], ops.ACT_CODES[ex.fused_activation()]
-        a.is_postscore, a.fuse_encode, a.capacity = int(bool(layer.is_postscore)), 1, 0
-        a.idx, a.loc, a.gates, a.zero_row = self.idx.data_ptr(), self.loc.data_ptr(), self.gates.data_ptr(), z.data_ptr()
-        m = _lib.MoeArgs()
-        m.ep = a
-        m.logits_dtype = ops._DT[logits.dtype]
-        m.ws, m.ws_bytes, m.stats = self.ws.data_ptr(), self.ws.numel(), self.stats.data_ptr()
+        self.zero_row = ops.zero_row(x.shape[1], x.dtype, dev)
+        m = self.margs = _add_routing(self, _static_args(layer, x, E, k, H), logits, k, T_cap, dev, scratch_tokens=(T_cap,))
+        m.ep.zero_row = self.zero_row.data_ptr()
         m.capacity_limit, m.alignment = int(capacity_limit), int(alignment)
-        pk = _lib.PackedArgs()
+        pk = self.pargs = _lib.PackedArgs()
         pk.ws, pk.ws_bytes = self.packed.data_ptr(), self.packed.numel()
         pk.offsets, pk.capacity = self.offsets.data_ptr(), self.capacity.data_ptr()
-        self.margs, self.pargs = m, pk
 
 
-def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignment, gate_w=None):
+def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignment, gate_w=None, plan=None):
     """Dropless forward on the packed layout: x [T, M], logits [T, E] -> (y [T, M_out], l_aux, dispatch_count [E], capacity [1]),
     all on the device -- no read-back, no retry, capturable.  None when the layout does not cover this layer / shape (the caller
-    then takes the padded path, whose results are the same bits)."""
+    then takes the padded path, whose results are the same bits).  plan: packed_cover's, from a caller that has asked already."""
     ex = layer.experts
     T, E = logits.shape
-    if packed_unsupported(layer, T, E, k, x.shape[1], x.dtype, capacity_limit, alignment) is not None:
-        return None
-    import collections
-    # (the limit is not part of the key: it follows T, and a workspace serves every call whose bound it holds)
+    if plan is None:
+        plan = packed_cover(layer, T, E, k, x.shape[1], x.dtype, capacity_limit, alignment)[0]
+        if plan is None:
+            return None
     swiglu = _swiglu(ex)
-    key = ("packed_glu" if swiglu else "packed", x.shape[1], x.dtype, x.device, E, logits.dtype, k, bool(layer.is_postscore), ex.fused_activation(), ops._stream(),
-           int(alignment))
-    plan = packed_plan(T, E, k, x.shape[1], _hidden_size(ex), ex.output_dim, x.dtype, capacity_limit, alignment)[0]
-    need = plan["ws_bytes"]
-    cache = layer.__dict__.get("_ep_workspaces")
-    if not isinstance(cache, collections.OrderedDict):
-        cache = layer.__dict__["_ep_workspaces"] = collections.OrderedDict()
-    ws = None
-    for ck, w in cache.items():
-        if ck[0] == key and w.T_cap >= T and w.pk_bytes >= need:
-            cache.move_to_end(ck)
-            ws = w
-            break
-    if ws is None:
-        T_cap = _bucket_tokens(T)
-        ws = _PackedWorkspace(layer, x, logits, k, T_cap, capacity_limit, alignment)
-        cache[(key, T_cap, 0)] = ws
-        layer.__dict__["_ep_workspace_allocations"] = layer.__dict__.get("_ep_workspace_allocations", 0) + 1
-        while len(cache) > WS_MAX:
-            cache.popitem(last=False)
+    # (the limit is not part of the key: it follows T, and a workspace serves every call whose bound it holds)
+    key = ("packed_glu" if swiglu else "packed", x.shape[1], x.dtype, x.device, E, logits.dtype, k, bool(layer.is_postscore),
+           ex.fused_activation(), ops._stream(), int(alignment))
+    ws = _workspace(layer, key, T, None, fits=lambda w: w.pk_bytes >= plan["ws_bytes"], make=lambda Tc, Cc: _PackedWorkspace(
+        layer, x, logits, k, Tc, capacity_limit, alignment, plan if Tc == T else None))
     m, pk = ws.margs, ws.pargs
-    a = m.ep
-    a.T = T
     m.capacity_limit = int(capacity_limit)
     if swiglu:   # k-major W_fc1 (gate), W_fc2 (up), W_fc3 (down); no biases
         w1, w_up, w2 = ex.kmajor_weights()
-        b1 = b2 = None
-        kmajor = True
+        y = _bind_operands(m.ep, ex, x, (w1, None, w2, None, True))
     else:
-        w1, b1, w2, b2, kmajor = ex.fused_params(x.dtype)
-    dev = x.device
-    y = torch.empty([T, ex.output_dim], dtype=x.dtype, device=dev)
-    cnt = torch.empty([E], dtype=torch.int32, device=dev)
-    l_aux = torch.empty([1], dtype=logits.dtype, device=dev)
-    a.w2_kmajor = int(kmajor)
-    a.x, a.w1, a.w2, a.y = x.data_ptr(), w1.data_ptr(), w2.data_ptr(), y.data_ptr()
-    a.b1 = b1.data_ptr() if b1 is not None else None
-    a.b2 = b2.data_ptr() if b2 is not None else None
-    m.normalize_gate = int(bool(normalize_gate))
-    if gate_w is None:
-        m.logits, m.gate_w, m.logits_out = logits.data_ptr(), None, None
-    else:   # `logits` is a meta tensor: the projection runs inside the call, as in forward_from_logits
-        need_p = ops.gate_proj_splits(T, x.shape[1], E, x.dtype) * T * E
-        if ws.gate_partials is None or ws.gate_partials.numel() < need_p:
-            ws.gate_partials_keep.append(ws.gate_partials)   # a captured graph may still hold the old pointer
-            ws.gate_partials = torch.empty([need_p], dtype=torch.float32, device=dev)
-        m.logits, m.gate_w, m.logits_out = None, gate_w.data_ptr(), None
-        m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
+        y = _bind_operands(m.ep, ex, x, ex.fused_params(x.dtype))
+    cnt = torch.empty([E], dtype=torch.int32, device=x.device)
+    l_aux = torch.empty([1], dtype=logits.dtype, device=x.device)
+    _bind_gate(ws, m, layer, x, logits, gate_w, normalize_gate, export_logits=False)
     m.dispatch_count, m.l_aux = cnt.data_ptr(), l_aux.data_ptr()
     if swiglu:
         rc = _lib.lib().tutel_amd_moe_forward_packed_glu(None, ctypes.byref(m), ctypes.byref(pk), w_up.data_ptr(), ops._stream())
@@ -927,9 +909,7 @@ def forward_packed(layer, x, logits, k, normalize_gate, capacity_limit, alignmen
     if rc == _lib.ENOTSUP:
         return None
     _lib.check(rc, "tutel_amd_moe_forward_packed")
-    if getattr(layer, "_keep_routing", False):
-        n = k * T
-        layer.last_routing = (ws.idx.view(-1)[:n].view(k, -1).clone(), ws.loc.view(-1)[:n].view(k, -1).clone())
+    _export_routing(layer, ws, k, T)
     # protected_shape in this mode: [local experts, host bound of the packed rows of ALL experts, M_out] -- the middle entry is a
     # bound, not the capacity (that one stays on the device: layer.dropless_capacity)
     layer.protected_shape = torch.Size([layer.num_local_experts, plan["rows_bound"], ex.output_dim])

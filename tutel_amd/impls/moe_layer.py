@@ -247,7 +247,7 @@ class MOELayer(torch.nn.Module):
               original_dtype, crit=None, allow_native=True):
         W = self.world_size
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
-        # reason: ep_native.packed_unsupported, checked in _run_native_moe)
+        # reason: ep_native.packed_cover, asked in _run_native_moe)
         swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
         fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
@@ -314,12 +314,12 @@ class MOELayer(torch.nn.Module):
         T, E = logits.shape
         k = min(top_k, E)
         spe = (T + E - 1) // E
+        limit = ep_native.dropless_row_limit(T, E, k, cf)
         xc = x if x.is_contiguous() else x.contiguous()
         if cf <= 0 and self.dropless_packed:   # dropless on the packed layout: the capacity never leaves the device
-            limit = k * int(-cf * spe) if cf < 0 else 0
-            why = ep_native.packed_unsupported(self, T, E, k, xc.shape[1], xc.dtype, limit, alignment)
-            res = None if why is not None else ep_native.forward_packed(self, xc, logits.contiguous(), k, self.normalize_gate, limit,
-                                                                         alignment, gate_w=gate_w)
+            plan, why = ep_native.packed_cover(self, T, E, k, xc.shape[1], xc.dtype, limit, alignment)
+            res = None if plan is None else ep_native.forward_packed(self, xc, logits.contiguous(), k, self.normalize_gate, limit,
+                                                                     alignment, gate_w=gate_w, plan=plan)
             self._dropless_packed_ran = True if res is not None else (why or "the packed layout does not cover this shape")
             if res is not None:
                 y, l_aux, cnt, cap = res
@@ -332,8 +332,7 @@ class MOELayer(torch.nn.Module):
         if cf <= 0:   # dropless: capacity = max expert load, read back inside the native call (fast_dispatch.py:191-199)
             guess = (k * spe * 3 // 2 + 31) // 32 * 32
             res = ep_native.forward_from_logits(self, xc, logits.contiguous(), k, guess, 1, self.normalize_gate, want_loss=True,
-                                                dropless=(k * int(-cf * spe) if cf < 0 else 0, alignment), megablocks_size=megablocks_size,
-                                                gate_w=gate_w)
+                                                dropless=(limit, alignment), megablocks_size=megablocks_size, gate_w=gate_w)
         else:
             res = ep_native.forward_from_logits(self, xc, logits.contiguous(), k, self._static_capacity(T, E, k, cf, alignment), degree,
                                                 self.normalize_gate, want_loss=True, gate_w=gate_w)

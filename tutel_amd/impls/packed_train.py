@@ -92,9 +92,8 @@ def unsupported(layer, gate, T, E, k, M, dtype, cf, alignment, reserve_dims=1, o
         return "the packed training step needs a non-empty batch on the HIP device"
     if ex.output_dim % 64 != 0:
         return "the packed training step needs M_out a multiple of 64 (the backward contracts over it)"
-    limit = k * int(-cf * ((T + E - 1) // E)) if cf < 0 else 0
-    plan, why = ep_native.packed_plan(T, E, k, M, w1.size(1), ex.output_dim, dtype, limit, alignment)
-    return why if plan is None else None
+    limit = ep_native.dropless_row_limit(T, E, k, cf)
+    return ep_native.packed_plan(T, E, k, M, w1.size(1), ex.output_dim, dtype, limit, alignment)[1]
 
 
 def main_grad_problem(layer):
@@ -197,7 +196,7 @@ def forward(layer, gate, x, logits, k, cf, alignment, main_grad=False):
     ex = layer.experts
     T, E = logits.shape
     M, H, Mo = x.shape[1], ex.batched_fc1_w.size(1), ex.output_dim
-    limit = k * int(-cf * ((T + E - 1) // E)) if cf < 0 else 0
+    limit = ep_native.dropless_row_limit(T, E, k, cf)
     plan, why = ep_native.packed_plan(T, E, k, M, H, Mo, x.dtype, limit, alignment)
     if plan is None:
         raise RuntimeError(why)
@@ -217,6 +216,8 @@ def forward(layer, gate, x, logits, k, cf, alignment, main_grad=False):
         gates2d = gk if gk.dtype == logits.dtype else gk.to(logits.dtype)
         l_aux = lk[0] if lk.dtype == logits.dtype else lk[0].to(logits.dtype)
     lay = ops.packed_layout(cnt, idx2d, loc2d, limit, alignment, plan["rows_bound"], plan["tiles_bound"], plan["row_limit"])
+    # (its own tensor per call, not ops.zero_row: this step may run inside a captured graph, and the process-wide cache must not
+    # hold memory that belongs to a graph's pool)
     zero_row = torch.zeros([max(M, 8)], dtype=x.dtype, device=x.device)
     xc = x if x.is_contiguous() else x.contiguous()
     params = (ex.batched_fc1_w, ex.batched_fc1_bias, ex.batched_fc2_w, ex.batched_fc2_bias)

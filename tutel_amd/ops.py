@@ -347,6 +347,16 @@ def expert_gemm_gate_up(a, w_gate, w_up, act="silu", row_counts=None, row_align=
 _zero_rows = {}
 
 
+def zero_row(n, dtype, device):
+    """the process's cached zero row of (device, dtype), at least n elements: what a gathering GEMM reads for a slot without a token.
+    Allocated max(n, 8192) long and replaced by a longer one when too short (earlier holders keep theirs alive).  Not for a tensor
+    made inside a captured training step: a process-wide cache must not hold memory of a graph's pool (impls/packed_train.py)."""
+    z = _zero_rows.get((device, dtype))
+    if z is None or z.numel() < n:
+        z = _zero_rows[(device, dtype)] = torch.zeros([max(n, 8192)], dtype=dtype, device=device)
+    return z
+
+
 def expert_gemm_gather(x, smap, w, bias, w_kmajor, act, R, row_counts=None, row_align=1):
     """fc1 with fast_encode fused: D[e,r,:] = act(x[smap[e*R+r] % T] @ op(W[e]) + bias[e]), zero row where smap < 0."""
     _dev(x, smap, w, bias, row_counts)
@@ -354,10 +364,7 @@ def expert_gemm_gather(x, smap, w, bias, w_kmajor, act, R, row_counts=None, row_
     E_loc, N, K = (w.shape if w_kmajor else (w.shape[0], w.shape[2], w.shape[1]))
     assert x.shape[1] == K and smap.dtype == torch.int32 and smap.numel() == E_loc * R
     x = _a16(x)
-    key = (x.device, x.dtype)
-    z = _zero_rows.get(key)
-    if z is None or z.numel() < K:
-        z = _zero_rows[key] = torch.zeros([max(K, 8192)], dtype=x.dtype, device=x.device)
+    z = zero_row(K, x.dtype, x.device)
     out = torch.empty([E_loc, R, N], dtype=x.dtype, device=x.device)
     _lib.check(_lib.lib().tutel_amd_expert_gemm_gather(
         _ptr(x), x.stride(0), _ptr(smap), x.shape[0], _ptr(z), _ptr(w), int(bool(w_kmajor)), w.stride(0), w.stride(1),
@@ -384,11 +391,7 @@ def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
         xs, ldx, T, z = R * M, M, 0, None
     else:
         assert x.dim() == 2 and x.shape[1] == M and smap.dtype == torch.int32 and smap.numel() == E_loc * R
-        key = (x.device, x.dtype)
-        z = _zero_rows.get(key)
-        if z is None or z.numel() < M:
-            z = _zero_rows[key] = torch.zeros([max(M, 8192)], dtype=x.dtype, device=x.device)
-        xs, ldx, T = 0, x.stride(0), x.shape[0]
+        xs, ldx, T, z = 0, x.stride(0), x.shape[0], zero_row(M, x.dtype, x.device)
     if hid is None:
         hid = torch.empty([E_loc, R, H], dtype=x.dtype, device=x.device)
     out = torch.empty([E_loc, R, M_out], dtype=x.dtype, device=x.device)
@@ -599,7 +602,6 @@ def stage_report():
     tot, cnt = (ctypes.c_double * n)(), (ctypes.c_int * n)()
     _lib.check(_lib.lib().tutel_amd_stage_report(tot, cnt, n), "tutel_amd_stage_report")
     return {name: (float(tot[i]), int(cnt[i])) for i, name in enumerate(_lib.STAGES)}
-
 
 
 def mark():
