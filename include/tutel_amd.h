@@ -91,6 +91,20 @@ int tutel_amd_gate_topk_partials(const float *partials, int splits, int dtype, i
                                  int normalize_gate, void *logits_out, void *scores_out, int32_t *idx, void *gates,
                                  void *ws, size_t ws_bytes, int32_t *clear_map, int clear_n, tutel_stream_t stream);
 
+/* The gate projection of an FP32 linear gate over 16-bit tokens (fp32_gate=True: replaces `F.linear(x.float(), wg.float())`):
+ * partials[s][t][e] = sum_m float(x[t, m]) * wg[e, m], x [T, M] bf16 / fp16 (x_dtype), wg_f32 [E, M] fp32, on the exact-f32 matrix
+ * instruction.  Same coverage as tutel_amd_gate_proj (E <= 128, E % 4 == 0, M % 64 == 0, T >= 1), same argument checks; the split
+ * count S = tutel_amd_gate_proj_f32w_splits(T, M, E, x_dtype) is a pure function of its arguments, 1 <= S <= 64, 0 = not covered
+ * (tutel_amd_gate_proj_splits(.., TUTEL_F32) stays 0: that query names the 16-bit kernel).
+ * Ordering contract: split s owns the contiguous range m in [s * L, min(M, (s + 1) * L)) with L = 64 * ceil((M / 64) / S) (no
+ * range is empty), and partials[s][t][e] is bit for bit the sequential chain
+ *     acc = 0.f; for m ascending over the range: acc = fmaf((float)x[t][m], wg[e][m], acc);
+ * -- no atomics, nothing depends on T, E or the launch.  tutel_amd_gate_topk_partials with dtype == TUTEL_F32 consumes them: the
+ * logits are ((p[0] + p[1]) + p[2]) + ... in fp32, not rounded again; logits_out, scores_out and gates are then fp32. */
+int tutel_amd_gate_proj_f32w_splits(int T, int M, int E, int x_dtype);
+int tutel_amd_gate_proj_f32w(const void *x, const void *wg_f32, int x_dtype, int T, int M, int E, float *partials,
+                             size_t partial_bytes, tutel_stream_t stream);
+
 /* Warm the memory-side cache (256 MiB Infinity Cache) with n_chunks byte ranges of chunk_bytes each, stride_bytes apart: plain
  * loads, nothing written (sink4: 4 writable bytes or NULL; practically never written).  For a caller that has a second stream
  * idle while the routing kernels run -- they are latency chains that leave HBM idle, and the first expert GEMM's weights depend
@@ -445,10 +459,12 @@ typedef struct {
   int *capacity_out;         /* host pointer, out: the capacity used (may be NULL when ep.capacity > 0); dropless: the read-back
                               * lands here (pinned memory keeps the copy asynchronous) */
   /* the gate projection inside the call (round 5): logits == NULL and gate_w != NULL -> logits = ep.x @ gate_w^T through
-   * tutel_amd_gate_proj + tutel_amd_gate_topk_partials (ep.dtype must equal logits_dtype; the shape must be covered, see
-   * tutel_amd_gate_proj_splits -- otherwise the call fails before anything is enqueued). */
-  const void *gate_w;        /* [num_experts, M] in ep.dtype (nn.Linear weight of the gate), or NULL */
-  float *gate_partials;      /* >= splits * T * num_experts floats */
+   * tutel_amd_gate_proj + tutel_amd_gate_topk_partials.  gate_w is always in logits_dtype, and two pairs are legal: logits_dtype
+   * == ep.dtype (tutel_amd_gate_proj / _splits), or logits_dtype == TUTEL_F32 with a 16-bit ep.dtype (an fp32 gate over 16-bit
+   * tokens: tutel_amd_gate_proj_f32w / _f32w_splits; gates, l_aux and logits_out are then fp32).  The shape must be covered by
+   * that pair's split query -- otherwise the call fails before anything is enqueued). */
+  const void *gate_w;        /* [num_experts, M] in logits_dtype (nn.Linear weight of the gate), or NULL */
+  float *gate_partials;      /* >= splits * T * num_experts floats, splits from the pair's query */
   size_t gate_partial_bytes;
   void *logits_out;          /* optional out [T, num_experts], logits dtype: the projected logits (NULL to skip) */
   /* fused location (round 5; TUTEL_OPT_FUSED_LOCATION): scratch of >= round_up(k * T, 16) bytes.  With it, on one rank with

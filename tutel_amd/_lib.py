@@ -27,6 +27,8 @@ SIGNATURES = {
     "tutel_amd_gate_topk": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp]),
     "tutel_amd_gate_proj_splits": (_i, [_i, _i, _i, _i]),
     "tutel_amd_gate_proj": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tutel_amd_gate_proj_f32w_splits": (_i, [_i, _i, _i, _i]),
+    "tutel_amd_gate_proj_f32w": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "tutel_amd_gate_topk_partials": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp]),
     "tutel_amd_cache_warm": (_i, [_vp, _sz, _i, _sz, _i, _vp, _vp]),
     "tutel_amd_compute_location": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),

@@ -129,6 +129,14 @@ int tutel_gate_topk_launch(const void *in, const float *partials, int splits, in
 // the top-k on its partial sums (splits > 0) or the top-k on m.logits, then the locations.  slot_map != NULL: cleared and filled for
 // m.ep.capacity rows per expert; NULL (dropless): the capacity is not known yet
 int tutel_route_launch(const tutel_amd_moe_args_t &m, int splits, int32_t *slot_map, tutel_stream_t stream);
+// gate_proj.hip: the in-call gate projection by its (token dtype, logits dtype) pair; gate_w is always in the logits dtype.  Equal
+// dtypes: tutel_amd_gate_proj; fp32 logits over 16-bit tokens (gate_proj_mixed): tutel_amd_gate_proj_f32w
+static inline bool gate_proj_mixed(int x_dtype, int logits_dtype) {
+  return logits_dtype == TUTEL_F32 && (x_dtype == TUTEL_BF16 || x_dtype == TUTEL_F16);
+}
+int tutel_gate_proj_splits_for(int T, int M, int E, int x_dtype, int logits_dtype);
+int tutel_gate_proj_for(const void *x, const void *gate_w, int x_dtype, int logits_dtype, int T, int M, int E, float *partials,
+                        size_t partial_bytes, tutel_stream_t stream);
 
 #define TUTEL_REQUIRE(cond, ...)           \
   do {                                     \

@@ -243,8 +243,8 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
                 "tutel_amd_moe_forward_packed: x / weights / y / zero_row must be 16-byte aligned (biases 8-byte)");
   int splits = 0;
   if (project) {
-    TUTEL_REQUIRE(a.dtype == m->logits_dtype, "tutel_amd_moe_forward_packed: the in-call gate projection needs the gate in the token dtype");
-    splits = tutel_amd_gate_proj_splits(T, M, E, a.dtype);
+    TUTEL_REQUIRE(a.dtype == m->logits_dtype || gate_proj_mixed(a.dtype, m->logits_dtype), "tutel_amd_moe_forward_packed: the in-call gate projection needs the gate in the token dtype");
+    splits = tutel_gate_proj_splits_for(T, M, E, a.dtype, m->logits_dtype);
     TUTEL_REQUIRE(splits > 0, "tutel_amd_moe_forward_packed: the in-call gate projection does not cover T=%d, M=%d, E=%d (pass logits)", T, M, E);
     TUTEL_REQUIRE(m->gate_partials != nullptr && m->gate_partial_bytes >= (size_t)splits * T * E * sizeof(float),
                   "tutel_amd_moe_forward_packed: gate_partials must hold %d x %d x %d floats", splits, T, E);

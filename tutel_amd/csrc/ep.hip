@@ -1085,9 +1085,9 @@ int tutel_route_launch(const tutel_amd_moe_args_t &m, int splits, int32_t *slot_
   const int T = a.T, E = a.num_experts, k = a.k, clear_n = slot_map != nullptr ? E * a.capacity : 0;
   int rc;
   if (splits > 0) {  // the gate projection inside the call (gate_proj.hip)
-    rc = tutel_amd_gate_proj(a.x, m.gate_w, a.dtype, T, a.M, E, m.gate_partials, m.gate_partial_bytes, stream);
+    rc = tutel_gate_proj_for(a.x, m.gate_w, a.dtype, m.logits_dtype, T, a.M, E, m.gate_partials, m.gate_partial_bytes, stream);
     if (rc) return rc;
-    rc = tutel_amd_gate_topk_partials(m.gate_partials, splits, a.dtype, T, E, k, m.normalize_gate, m.logits_out, nullptr,
+    rc = tutel_amd_gate_topk_partials(m.gate_partials, splits, m.logits_dtype, T, E, k, m.normalize_gate, m.logits_out, nullptr,
                                       const_cast<int32_t *>(a.idx), const_cast<void *>(a.gates), m.ws, m.ws_bytes, slot_map, clear_n, stream);
   } else {
     rc = tutel_amd_gate_topk(m.logits, m.logits_dtype, 1, T, E, k, m.normalize_gate, nullptr, const_cast<int32_t *>(a.idx),
@@ -1106,8 +1106,8 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
   TUTEL_REQUIRE((m->logits != nullptr || project || T == 0) && m->ws != nullptr && m->dispatch_count != nullptr, "tutel_amd_moe_forward: null pointer");
   int splits = 0;
   if (project && T > 0) {
-    TUTEL_REQUIRE(a.dtype == m->logits_dtype, "tutel_amd_moe_forward: the in-call gate projection needs the gate in the token dtype (%d vs %d)", m->logits_dtype, a.dtype);
-    splits = tutel_amd_gate_proj_splits(T, a.M, E, a.dtype);
+    TUTEL_REQUIRE(a.dtype == m->logits_dtype || gate_proj_mixed(a.dtype, m->logits_dtype), "tutel_amd_moe_forward: the in-call gate projection needs the gate in the token dtype (%d vs %d)", m->logits_dtype, a.dtype);
+    splits = tutel_gate_proj_splits_for(T, a.M, E, a.dtype, m->logits_dtype);
     TUTEL_REQUIRE(splits > 0, "tutel_amd_moe_forward: the in-call gate projection does not cover T=%d, M=%d, E=%d, dtype=%d (pass logits)", T, a.M, E, a.dtype);
     TUTEL_REQUIRE(a.x != nullptr && m->gate_partials != nullptr && m->gate_partial_bytes >= (size_t)splits * T * E * sizeof(float),
                   "tutel_amd_moe_forward: gate_partials must hold %d x %d x %d floats", splits, T, E);
@@ -1144,7 +1144,7 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
     hipStream_t st = (hipStream_t)stream;
     uint8_t *idx8 = (uint8_t *)m->fl_ws;
     if (project) {
-      rc = tutel_amd_gate_proj(a.x, m->gate_w, a.dtype, T, a.M, E, m->gate_partials, m->gate_partial_bytes, stream);
+      rc = tutel_gate_proj_for(a.x, m->gate_w, a.dtype, m->logits_dtype, T, a.M, E, m->gate_partials, m->gate_partial_bytes, stream);
       if (rc) return rc;
     }
     rc = tutel_gate_topk_launch(project ? nullptr : m->logits, project ? m->gate_partials : nullptr, splits, m->logits_dtype, T, E, k,

@@ -835,7 +835,7 @@ extern "C" int tutel_amd_gate_topk_partials(const float *partials, int splits, i
                                             int normalize_gate, void *logits_out, void *scores_out, int32_t *idx,
                                             void *gates, void *ws, size_t ws_bytes, int32_t *clear_map, int clear_n,
                                             tutel_stream_t stream) {
-  TUTEL_REQUIRE(dtype == TUTEL_F16 || dtype == TUTEL_BF16, "tutel_amd_gate_topk_partials: the logits dtype must be fp16 / bf16 (got %d)", dtype);
+  TUTEL_REQUIRE(dtype_ok(dtype), "tutel_amd_gate_topk_partials: the logits dtype must be fp32 / fp16 / bf16 (got %d)", dtype);
   TUTEL_REQUIRE(T >= 0 && E >= 1 && E <= 128, "tutel_amd_gate_topk_partials: need 1 <= E <= 128 (got %d)", E);
   TUTEL_REQUIRE(k >= 1 && k <= RT_MAX_K && k <= E, "tutel_amd_gate_topk_partials: need 1 <= k <= min(E,%d) (got k=%d, E=%d)", RT_MAX_K, k, E);
   TUTEL_REQUIRE(splits >= 1 && splits <= 64, "tutel_amd_gate_topk_partials: bad split count %d", splits);
@@ -846,6 +846,8 @@ extern "C" int tutel_amd_gate_topk_partials(const float *partials, int splits, i
   if (clear_n == 0) clear_map = nullptr;
   hipStream_t st = (hipStream_t)stream;
   StageScope stage(TUTEL_STAGE_GATE_TOPK, st);
+  if (dtype == TUTEL_F32)   // the partial sums of tutel_amd_gate_proj_f32w: the fp32 sum in split order IS the logit, no rounding follows
+    return launch_gate_topk<float>(nullptr, 1, T, E, k, normalize_gate, scores_out, idx, gates, ws, clear_map, clear_n, st, partials, splits, logits_out);
   if (dtype == TUTEL_BF16)
     return launch_gate_topk<bf16_t>(nullptr, 1, T, E, k, normalize_gate, scores_out, idx, gates, ws, clear_map, clear_n, st, partials, splits, logits_out);
   return launch_gate_topk<f16_t>(nullptr, 1, T, E, k, normalize_gate, scores_out, idx, gates, ws, clear_map, clear_n, st, partials, splits, logits_out);

@@ -613,7 +613,9 @@ def _bind_gate(ws, m, layer, x, logits, gate_w, normalize_gate, export_logits):
         m.logits, m.gate_w, m.logits_out = logits.data_ptr(), None, None
         return
     T, E = logits.shape
-    need = ops.gate_proj_splits(T, x.shape[1], E, x.dtype) * T * E
+    # gate_w is in the logits dtype: x's own (the 16-bit kernel) or fp32 over 16-bit tokens (the fp32-weight kernel)
+    splits = ops.gate_proj_splits if logits.dtype == x.dtype else ops.gate_proj_f32w_splits
+    need = splits(T, x.shape[1], E, x.dtype) * T * E
     if ws.gate_partials is None or ws.gate_partials.numel() < need:
         ws.gate_partials_keep.append(ws.gate_partials)   # a captured graph may still hold the old pointer
         ws.gate_partials = torch.empty([need], dtype=torch.float32, device=x.device)
@@ -621,7 +623,7 @@ def _bind_gate(ws, m, layer, x, logits, gate_w, normalize_gate, export_logits):
     m.gate_partials, m.gate_partial_bytes = ws.gate_partials.data_ptr(), ws.gate_partials.numel() * 4
     if export_logits:
         keep = getattr(layer, "_keep_routing", False)
-        layer.last_logits = torch.empty([T, E], dtype=x.dtype, device=x.device) if keep else None
+        layer.last_logits = torch.empty([T, E], dtype=logits.dtype, device=x.device) if keep else None
         m.logits_out = ops._ptr(layer.last_logits)
 
 

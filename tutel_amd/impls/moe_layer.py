@@ -43,6 +43,9 @@ _FORCE_OVERLAP = int(os.environ.get("TUTEL_AMD_FORCE_OVERLAP", "0")) != 0
 _FUSE_ENCODE = int(os.environ.get("TUTEL_AMD_FUSE_ENCODE", "1")) != 0
 # A/B switch: the projection of a 16-bit linear gate inside the native call (csrc/gate_proj.hip) instead of F.linear
 _NATIVE_GATE = int(os.environ.get("TUTEL_AMD_NATIVE_GATE", "1")) != 0
+# opt-in: the same for an fp32 gate (fp32_gate=True) over bf16 / fp16 tokens -- fp32 weights, exact-f32 MFMA, fp32 logits -- instead of
+# x.float() + an fp32 F.linear.  Off: such a layer projects with F.linear exactly as before
+_NATIVE_GATE_FP32 = int(os.environ.get("TUTEL_AMD_NATIVE_GATE_FP32", "0")) != 0
 
 
 def _autocast_dtype(t):
@@ -293,16 +296,22 @@ class MOELayer(torch.nn.Module):
     @staticmethod
     def _native_gate_weight(gate, x):
         """wg.weight when the gate projection can run inside the native call, else None"""
-        if not (_NATIVE_GATE and x.is_cuda and type(gate) is LinearTopKGate and not gate.fp32_gate and x.dim() == 2):
+        if not (_NATIVE_GATE and x.is_cuda and type(gate) is LinearTopKGate and x.dim() == 2):
             return None
         w = gate.wg.weight
-        if w.dtype != x.dtype or x.dtype not in (torch.bfloat16, torch.float16) or not w.is_contiguous() or w.device != x.device:
+        # an fp32 gate projects natively only as fp32 weights over 16-bit tokens (a gate module cast as a whole to 16 bits widens its
+        # weight per call: that stays on F.linear), and only when asked for
+        if gate.fp32_gate and not (_NATIVE_GATE_FP32 and w.dtype == torch.float32):
+            return None
+        splits = ops.gate_proj_f32w_splits if gate.fp32_gate else ops.gate_proj_splits
+        if (not gate.fp32_gate and w.dtype != x.dtype) or x.dtype not in (torch.bfloat16, torch.float16) or not w.is_contiguous() \
+                or w.device != x.device:
             return None
         if gate._forward_hooks or gate._forward_pre_hooks or gate.wg._forward_hooks or gate.wg._forward_pre_hooks:
             return None
         if torch.is_grad_enabled() and (w.requires_grad or x.requires_grad):
             return None
-        if torch.is_autocast_enabled() or ops.gate_proj_splits(x.shape[0], x.shape[1], w.shape[0], x.dtype) == 0:
+        if torch.is_autocast_enabled() or splits(x.shape[0], x.shape[1], w.shape[0], x.dtype) == 0:
             return None
         # the split-K kernel fetches 16-byte vectors: a contiguous but offset view (a slice of a larger buffer) stays on F.linear
         # instead of raising from the forward (ADVICE r5).  Non-contiguous x is made contiguous (a fresh allocation) by the caller.
@@ -424,10 +433,10 @@ class MOELayer(torch.nn.Module):
         # A plain 16-bit linear gate on the one-call path: the projection runs INSIDE the native call (csrc/gate_proj.hip, split-K
         # MFMA + the top-k kernel adding the partial sums) instead of F.linear here.  Decided on the logits' shape / dtype alone
         # (a meta tensor stands in for them); anything else -- hooks on the gate, a gradient, fp32_gate, an uncovered shape --
-        # projects below as before.
+        # projects below as before.  (_NATIVE_GATE_FP32: an fp32 gate over 16-bit tokens too; the logits are then fp32.)
         gate_w = self._native_gate_weight(gate, x)
         if gate_w is not None:
-            spec = torch.empty([x.shape[0], gate_w.shape[0]], dtype=x.dtype, device="meta")
+            spec = torch.empty([x.shape[0], gate_w.shape[0]], dtype=gate_w.dtype, device="meta")
             if self._plan("before_routing", x, spec, *plan_args) == "native_moe":
                 res = self._run_native_moe(x, spec, top_k, cf, degree, alignment, megablocks_size, gate_w=gate_w)
                 if res is not None:

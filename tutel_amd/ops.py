@@ -115,9 +115,46 @@ def gate_proj(x, wg, partials=None):
     return partials
 
 
+def gate_proj_f32w_splits(T, M, E, dtype):
+    """split count of the fp32-weight gate projection (fp32 gate over tokens of `dtype`) for this shape; 0: not covered"""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return 0
+    return int(_lib.lib().tutel_amd_gate_proj_f32w_splits(int(T), int(M), int(E), _DT[dtype]))
+
+
+def gate_proj_f32w_ranges(T, M, E, dtype):
+    """the ordering contract of gate_proj_f32w (include/tutel_amd.h): [(m_begin, m_end)] per split -- split s accumulates
+    fmaf(float(x[t, m]), wg[e, m], acc) over its range in ascending m, from 0"""
+    S = gate_proj_f32w_splits(T, M, E, dtype)
+    if S == 0:
+        return []
+    L = 64 * -(-(M // 64) // S)
+    return [(s * L, min(M, (s + 1) * L)) for s in range(S)]
+
+
+def gate_proj_f32w(x, wg, partials=None):
+    """x [T, M] bf16 / fp16, wg [E, M] fp32 -> fp32 partial sums [S, T, E] of x.float() @ wg^T on the exact-f32 MFMA (split-K,
+    csrc/gate_proj.hip); None when the shape is not covered.  gate_topk_partials(.., torch.float32, ..) adds them in split order."""
+    _dev(x, wg)
+    assert x.dim() == 2 and wg.dim() == 2 and x.shape[1] == wg.shape[1] and wg.dtype == torch.float32
+    T, M = x.shape
+    E = wg.shape[0]
+    S = gate_proj_f32w_splits(T, M, E, x.dtype)
+    if S == 0 or T == 0:
+        return None
+    x, wg = x.contiguous(), wg.contiguous()
+    if partials is None:
+        partials = torch.empty([S, T, E], dtype=torch.float32, device=x.device)
+    assert partials.numel() >= S * T * E and partials.dtype == torch.float32
+    _lib.check(_lib.lib().tutel_amd_gate_proj_f32w(_ptr(x), _ptr(wg), _code(x), T, M, E, _ptr(partials), partials.numel() * 4, _stream()),
+               "tutel_amd_gate_proj_f32w")
+    return partials
+
+
 def gate_topk_partials(partials, dtype, k, normalize_gate=True, want_logits=False, want_scores=False, ws=None, clear=None):
-    """partials [S, T, E] fp32 (gate_proj) -> idx [k,T] i32, gates [k,T] dtype, ws, logits|None, scores|None: softmax + top-k on
-    logits = dtype(sum_s partials[s]), exactly as gate_topk(logits, apply_softmax=True)."""
+    """partials [S, T, E] fp32 (gate_proj / gate_proj_f32w) -> idx [k,T] i32, gates [k,T] dtype, ws, logits|None, scores|None:
+    softmax + top-k on logits = dtype(sum_s partials[s]), exactly as gate_topk(logits, apply_softmax=True).  dtype float32 (the
+    partial sums of gate_proj_f32w): the fp32 sum in split order is the logit."""
     _dev(partials)
     assert partials.dim() == 3 and partials.dtype == torch.float32 and partials.is_contiguous()
     S, T, E = partials.shape
@@ -129,7 +166,7 @@ def gate_topk_partials(partials, dtype, k, normalize_gate=True, want_logits=Fals
     scores = torch.empty([T, E], dtype=dtype, device=dev) if want_scores else None
     if ws is None:
         ws = routing_workspace(T, E, k, dev)
-    code = _lib.BF16 if dtype == torch.bfloat16 else _lib.F16
+    code = _DT[dtype]
     _lib.check(_lib.lib().tutel_amd_gate_topk_partials(_ptr(partials), S, code, T, E, k, int(bool(normalize_gate)), _ptr(logits),
                                                        _ptr(scores), _ptr(idx), _ptr(gates), _ptr(ws), ws.numel(), _ptr(clear),
                                                        clear.numel() if clear is not None else 0, _stream()),
@@ -138,13 +175,14 @@ def gate_topk_partials(partials, dtype, k, normalize_gate=True, want_logits=Fals
 
 
 def gate_logits(x, wg):
-    """x @ wg^T in x.dtype through the split-K kernel: the SAME logits, bit for bit, that the one-call path routes on (its top-k kernel
-    adds the same partial sums in the same order) -- so that a layer's routing does not depend on which path its planner picks.
-    None when the shape is not covered."""
-    part = gate_proj(x, wg)
+    """x @ wg^T through the split-K kernel, in wg's dtype: the SAME logits, bit for bit, that the one-call path routes on (its top-k
+    kernel adds the same partial sums in the same order) -- so that a layer's routing does not depend on which path its planner
+    picks.  wg in x's 16-bit dtype, or fp32 over 16-bit tokens (an fp32 gate: fp32 logits).  None when the shape is not covered."""
+    mixed = wg.dtype == torch.float32 and x.dtype != torch.float32
+    part = gate_proj_f32w(x, wg) if mixed else gate_proj(x, wg)
     if part is None:
         return None
-    return gate_topk_partials(part, x.dtype, 1, want_logits=True)[3]
+    return gate_topk_partials(part, wg.dtype, 1, want_logits=True)[3]
 
 
 def cache_warm(t, chunk_bytes=None, n_chunks=1, stride_bytes=0, blocks=0, offset=0):
