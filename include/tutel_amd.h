@@ -689,6 +689,35 @@ int tutel_amd_marks_report(double *delta_us, int n);
 #define TUTEL_OPT_COUNT 13
 int tutel_amd_set_option(int key, int value);
 
+/* Which kernel would a grouped GEMM run?  An introspection aid for tests and tools: the library picks every grouped GEMM's kernel in
+ * one pure function of the problem, the weight layout, the form (padded / packed / gate-up) and the GEMM_* knobs above, and this
+ * entry point shows its answer.  It ARMS the calling thread: the next tutel_amd_expert_gemm, _glu, _gather, _gate_up, _packed or
+ * tutel_amd_expert_ffn called on this thread runs all its argument checks, writes the plan to out[0] and returns the status it would
+ * have returned -- before any HIP call: nothing is allocated, timed or launched.  The arm clears itself on that call, whether the
+ * call succeeds or refuses (a call refused before it got to planning leaves family = -1).  `out` must have room for TWO plans:
+ * tutel_amd_expert_ffn fills out[0] (fc1) and out[1] (fc2) with what the two launches would run, and `covered` in both says
+ * whether the pair takes the persistent kernel instead.  Two pipelines answer as well, for the GEMMs no single-GEMM entry point
+ * can state: tutel_amd_moe_forward on its fused-location route (out[0]: the eligibility query, out[1]: the fc1 launch after a
+ * yes; TUTEL_AMD_ENOTSUP when the route is not taken) and tutel_amd_moe_forward_packed[_glu] (out[0]: fc1 or the fused
+ * gate/up GEMM over the packed layout, out[1]: fc2); armed, they launch nothing either.  corun != 0 stands in for the "a collective runs beside this GEMM" hint
+ * that only the expert-parallel pipeline sets.  tests/test_gemm_plan_cpu.py pins the plans of a table of cases. */
+#define TUTEL_GEMM_STAGED_128 0    /* register-staged 128 x 128 */
+#define TUTEL_GEMM_GLDS_128 1      /* LDS-DMA 128 x 128 */
+#define TUTEL_GEMM_RING 2          /* 128- / 256-row ring tile: ni x 64 columns, ns slots, bm rows, buf = LDS epilogue built in, fl = fused location */
+#define TUTEL_GEMM_PINGPONG 3      /* 256 x 256 ping-pong: w_once, ragged, early_bias, splitk, packed, gate_up */
+#define TUTEL_GEMM_PACKED_NMAJOR 4 /* register-staged 128 x 128 over the packed layout's tile table */
+typedef struct {
+  int status;                      /* 0 a launch; 1 a fused-location query, answered yes; TUTEL_AMD_ENOTSUP or -1: refused (tutel_amd_last_error) */
+  int family, w_kmajor;            /* TUTEL_GEMM_* (-1: none) */
+  int ni, ns, bm, buf, fl;         /* TUTEL_GEMM_RING */
+  int w_once, ragged, early_bias, splitk, packed, gate_up; /* TUTEL_GEMM_PINGPONG */
+  int ntm, ntn, grid, threads, lds_bytes;
+  int lds_epilogue;                /* the output tile leaves through LDS in 16-byte stores (output rows 16-byte aligned) */
+  int rot_on, fits32, d_store;     /* of the argument block: K-tile rotation, 32-bit operand offsets, store policy */
+  int covered;                     /* tutel_amd_expert_ffn only */
+} tutel_amd_gemm_plan_t;
+int tutel_amd_expert_gemm_plan_next(tutel_amd_gemm_plan_t *out, int corun);
+
 /* ---- self-test helpers (used by tests / smoke only) ---------------------------------------
  * Dumps the lane->element permutation of ds_read_b64_tr_b16 (the transposing LDS read the
  * [K,N]-weight GEMM relies on): out[64*4] uint16, LDS pre-filled with lds[i] = i, lane l

@@ -30,7 +30,7 @@ GLU_PROMISED = ({"form=" + f for f in FORMS} | {"kmajor+mul", "nmajor+mul", "bia
                 | {"impl=%d+mul" % v for v in GLU_IMPL} | {"tile=%d+mul" % v for v in GLU_TILE} | {"store=%d+mul" % v for v in GLU_STORE})
 
 # The fixed head of every case list: the smallest shapes that reach, WITH a gating operand, the kernel templates a random draw of
-# the forced options seldom or never reaches (csrc/expert_gemm.hip::launch_gemm):
+# the forced options seldom or never reaches (csrc/gemm_plan.hip):
 #   the 128 x 256 ring      k-major, impl = 4, tile <= 0, R <= 128, N >= 256
 #   the 256 x 128 rings     k-major, tile = 2 (two slots), tile = 3 (three slots, buffer path), tile = 3 with impl = 2 (three slots
 #                           without the buffer path -- the only drawn-or-fixed case with an impl outside GLU_IMPL)

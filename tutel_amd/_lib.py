@@ -86,7 +86,16 @@ class PackedPlan(ctypes.Structure):
     _fields_ = [("rows_bound", _i), ("tiles_bound", _i), ("tile_rows", _i), ("row_limit", _i), ("ws_bytes", _sz)]
 
 
+class GemmPlan(ctypes.Structure):
+    """tutel_amd_gemm_plan_t"""
+    _fields_ = [(n, _i) for n in ("status", "family", "w_kmajor", "ni", "ns", "bm", "buf", "fl", "w_once", "ragged", "early_bias", "splitk",
+                                  "packed", "gate_up", "ntm", "ntn", "grid", "threads", "lds_bytes", "lds_epilogue", "rot_on", "fits32",
+                                  "d_store", "covered")]
+
+
+GEMM_FAMILIES = ("STAGED_128", "GLDS_128", "RING", "PINGPONG", "PACKED_NMAJOR")     # TUTEL_GEMM_*
 SIGNATURES.update({
+    "tutel_amd_expert_gemm_plan_next": (_i, [ctypes.POINTER(GemmPlan * 2), _i]),
     "tutel_amd_moe_forward": (_i, [_vp, ctypes.POINTER(MoeArgs), _vp]),
     "tutel_amd_packed_plan": (_i, [_i] * 9 + [ctypes.POINTER(PackedPlan)]),
     "tutel_amd_moe_packed_workspace_bytes": (_sz, [_i] * 9),

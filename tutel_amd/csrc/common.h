@@ -95,6 +95,11 @@ static inline void gemm_gather(GemmProblem &g, const int32_t *slot_map, int T, c
 // expert_gemm.hip: one grouped GEMM, every form (what tutel_amd_expert_gemm and its _glu / _gather siblings run after their own checks).
 // A fused-location query (fl_idx8 set, fl_loc NULL) launches nothing: 0 = this shape takes the fused kernel, TUTEL_AMD_ENOTSUP = not
 int tutel_expert_gemm(const GemmProblem &g, int w_kmajor, int act, hipStream_t st);
+// tutel_amd_expert_gemm_plan_next (gemm_plan.hip): the first statement of a public entry point that runs grouped GEMMs takes the
+// thread's arm for the length of the call; whoever plans a GEMM inside it hands the plan over instead of launching.
+// gemm_plan_asked: is one waiting?  (slot >= 0: and the next plan handed over goes to out[slot])
+struct GemmPlanScope { GemmPlanScope(); ~GemmPlanScope(); };
+bool gemm_plan_asked(int slot = -1);
 // expert_ffn.hip: fc1 -> activation -> fc2 in one persistent launch (fc2.A is fc1.D; fc1 may carry the gather and the fused-location
 // fields).  query != 0: answers only.  TUTEL_AMD_ENOTSUP: this shape / layout takes the two-launch path (nothing was launched)
 int tutel_expert_ffn(const GemmProblem &fc1, const GemmProblem &fc2, int act, int query, hipStream_t st);

@@ -15,8 +15,8 @@
 // on the device.  Buffers and grids are sized by the host bound of tutel_amd_packed_plan, a function of (T, E, k, limit, alignment).
 //
 // Tile rule: PK_TILE_ROWS = 256 rows per M-tile, for every shape -- the 256 x 256 ping-pong kernel the padded path takes at the
-// dropless headline shape (E = 64, T = 4096, k = 2: ~160 rows per expert, launch_pp).  With 128-row tiles an expert above 128 rows
-// streams its weights twice (the launch_gemm comment records fc1 at 214 us vs 118 us); a 256-row tile of an expert with fewer rows
+// dropless headline shape (E = 64, T = 4096, k = 2: ~160 rows per expert, gemm_plan).  With 128-row tiles an expert above 128 rows
+// streams its weights twice (the gemm_plan comments record fc1 at 214 us vs 118 us); a 256-row tile of an expert with fewer rows
 // skips the MFMAs of the empty 32-row groups (the RAGGED form) and its weights are still streamed once.
 #include <climits>
 
@@ -201,6 +201,7 @@ extern "C" size_t tutel_amd_moe_packed_workspace_bytes(int T, int E, int k, int 
 // w2 (the down projection) -- no biases
 static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, const tutel_amd_packed_args_t *pk, const void *w_up,
                           tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(m != nullptr && pk != nullptr, "tutel_amd_moe_forward_packed: null arguments");
   const tutel_amd_ep_args_t &a = m->ep;
   const int T = a.T, E = a.num_experts, k = a.k, M = a.M, H = a.H, Mo = a.M_out;
@@ -262,10 +263,12 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
   w += pk_align((size_t)pl.rows_bound * H * 2);
   void *outb = w;
 
-  rc = tutel_route_launch(*m, splits, nullptr, stream);
+  // tutel_amd_expert_gemm_plan_next: only the two GEMMs answer (out[0], out[1]); nothing is launched
+  const bool ask = gemm_plan_asked(0);
+  rc = ask ? 0 : tutel_route_launch(*m, splits, nullptr, stream);
   if (rc) return rc;
   const int L = pl.row_limit > 0 ? pl.row_limit : INT_MAX;
-  {
+  if (!ask) {
     StageScope sc(TUTEL_STAGE_OTHER, st);
     launch_layout(m->dispatch_count, a.idx, a.loc, T, E, k, L, m->alignment, pl.rows_bound, pl.tiles_bound, pk->offsets, tiles, ntiles,
                   pk->capacity, slot, st);
@@ -286,8 +289,9 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
   fc2.D = outb; fc2.ldd = Mo;
   fc2.E_loc = E; fc2.N = Mo; fc2.K = H; fc2.dtype = a.dtype;
   gemm_one_rank(fc2, pl.rows_bound);
+  gemm_plan_asked(1);
   rc = tutel_expert_gemm_packed(fc2, 1, TUTEL_ACT_NONE, pt, nullptr, st);
-  if (rc) return rc;
+  if (rc || ask) return rc;
   return tutel_decode_packed_launch(outb, a.dtype, a.idx, a.loc, a.gates, m->logits_dtype, T, Mo, k, L, pk->offsets, a.y, st);
 }
 

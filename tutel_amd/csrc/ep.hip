@@ -989,7 +989,7 @@ extern "C" int tutel_amd_ep_forward(tutel_amd_ep_comm_t *c, const tutel_amd_ep_a
           if ((rc = ipc_wait(c, 0, i, 1, ks, seg)) != 0) return rc;
         }
         // two stages run side by side on the two side streams: a stage GEMM whose full grid would be one workgroup per CU takes
-        // the half-chip 256 x 256 grid instead (launch_gemm, expert_gemm.hip), so that fc1 / fc2 of stage i overlap those of stage
+        // the half-chip 256 x 256 grid instead (gemm_plan.hip), so that fc1 / fc2 of stage i overlap those of stage
         // i + 1 rather than queueing behind them block by block
         tutel_gemm_corun_hint(kss[0] != kss[1] && tutel_get_option(TUTEL_OPT_EP_STAGE_GRID) != 0);
         rc = stage_gemms(i, ks);
@@ -1099,6 +1099,7 @@ int tutel_route_launch(const tutel_amd_moe_args_t &m, int splits, int32_t *slot_
 }
 
 extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m, tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(m != nullptr, "tutel_amd_moe_forward: null arguments");
   const tutel_amd_ep_args_t &a = m->ep;
   const int T = a.T, E = a.num_experts, k = a.k;
@@ -1138,7 +1139,11 @@ extern "C" int tutel_amd_moe_forward(tutel_amd_ep_comm_t *c, const tutel_amd_moe
     strncpy(keep, tutel_amd_last_error(), sizeof(keep) - 1);
     keep[sizeof(keep) - 1] = 0;
     fl = tutel_expert_gemm(stage_fc1(a, (const uint8_t *)m->fl_ws, k * T, nullptr), 1, a.act, (hipStream_t)stream) == 0;
-    if (!fl) tutel_set_error("%s", keep);
+    if (!fl && !gemm_plan_asked()) tutel_set_error("%s", keep);
+  }
+  if (gemm_plan_asked(1)) {  // tutel_amd_expert_gemm_plan_next: out[0] holds the query's plan (or its refusal); out[1]: the fc1 launch after a yes
+    if (fl) (void)tutel_expert_gemm(stage_fc1(a, (const uint8_t *)m->fl_ws, k * T, const_cast<int32_t *>(a.loc)), 1, a.act, (hipStream_t)stream);
+    return fl ? 0 : TUTEL_AMD_ENOTSUP;
   }
   if (fl) {
     hipStream_t st = (hipStream_t)stream;

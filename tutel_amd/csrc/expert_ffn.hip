@@ -265,15 +265,15 @@ template <typename T, bool FL> static int ffn_launch_cfg(const FfnArgs &a, int g
   return launch_lds(expert_ffn_kernel<T, FL>, grid, FFN_THREADS, ffn_lds_bytes<FL>(), st, a, "tutel_amd_expert_ffn");
 }
 
-// Does this pair of GEMMs take the persistent kernel?  The conditions under which launch_gemm (expert_gemm.hip) picks the 128 x 256
-// ring tile with its LDS epilogue for BOTH, so that the fused launch runs exactly the tiles the two launches would.
-static bool ffn_covers(const GemmArgs &g1, const GemmArgs &g2) {
-  auto ring = [](const GemmArgs &g) {
-    return g.fits32 && g.N >= 256 && g.R <= GM_BM && (long long)g.E_loc * ((g.N + 255) / 256) >= 256 && g.mul == nullptr && g.d_peer == nullptr &&
-           g.row_counts == nullptr && !((g.ldd & 7) || (g.d_stride_e & 7) || (g.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(g.D) & 15));
+// Does this pair of GEMMs take the persistent kernel?  When the two launches, under automatic knobs, would BOTH run the 128 x 256 ring
+// tile with its LDS epilogue (p1, p2: their plans, gemm_plan), so that the fused launch runs exactly the tiles they would -- and
+// nothing the persistent kernel has no form for is asked: the gated form, peer stores, row counts.
+static bool ffn_covers(const GemmArgs &g1, const GemmArgs &g2, const GemmPlan &p1, const GemmPlan &p2, const GemmKnobs &k) {
+  auto ring = [](const GemmArgs &g, const GemmPlan &p) {
+    return (p.status == GEMM_PLAN_LAUNCH || p.status == GEMM_PLAN_FL_QUERY) && p.family == TUTEL_GEMM_RING && p.bm == 128 && p.lds_epilogue &&
+           g.mul == nullptr && g.d_peer == nullptr && g.row_counts == nullptr;
   };
-  return ring(g1) && ring(g2) && g1.E_loc == g2.E_loc && g1.R == g2.R && g1.d_store == 1 && tutel_get_option(TUTEL_OPT_GEMM_IMPL) < 0 &&
-         tutel_get_option(TUTEL_OPT_GEMM_TILE) < 0;
+  return ring(g1, p1) && ring(g2, p2) && g1.E_loc == g2.E_loc && g1.R == g2.R && g1.d_store == 1 && k.impl < 0 && k.tile < 0;
 }
 
 // development probe: a device array [grid][8] of per-workgroup tick sums (see FfnArgs::dbg); NULL = off
@@ -294,15 +294,21 @@ int tutel_expert_ffn(const GemmProblem &fc1, const GemmProblem &fc2, int act, in
   rc = tutel_gemm_args(fc2, &a.g[1]);
   if (rc != 0) return rc < 0 ? rc : TUTEL_AMD_ENOTSUP;
   const bool fl = fc1.fl_idx8 != nullptr;
-  if (!ffn_covers(a.g[0], a.g[1])) return TUTEL_AMD_ENOTSUP;
-  if (fl && !(fc1.a_rows != nullptr && fc1.fl_n >= 1 && fc1.fl_n <= 15360 && E_loc <= 128 && fc1.K >= 2 * GL_BK && ((uintptr_t)fc1.fl_idx8 & 15) == 0 &&
-              tutel_get_option(TUTEL_OPT_FUSED_LOCATION) != 0))
-    return TUTEL_AMD_ENOTSUP;
-  if (query) return 0;
-  for (int i = 0; i < 2; ++i) {
-    a.g[i].ntm = 1;
-    a.g[i].ntn = (a.g[i].N + 255) / 256;
+  const GemmKnobs k = gemm_knobs();
+  const GemmPlan p1 = gemm_plan(a.g[0], true, false, 0, k), p2 = gemm_plan(a.g[1], true, false, 0, k);
+  // (a fused-location fc1 that the ring kernel does not take has no plan: gemm_fl_eligible, gemm_plan.hip)
+  const bool covered = ffn_covers(a.g[0], a.g[1], p1, p2, k) &&
+                       (!fl || (((uintptr_t)fc1.fl_idx8 & 15) == 0 && tutel_get_option(TUTEL_OPT_FUSED_LOCATION) != 0));
+  if (gemm_plan_asked(0)) {  // tutel_amd_expert_gemm_plan_next: what the two launches would run, and whether this one replaces them
+    gemm_plan_report(p1, a.g[0], covered);
+    gemm_plan_asked(1);
+    gemm_plan_report(p2, a.g[1], covered);
+    return covered ? 0 : TUTEL_AMD_ENOTSUP;
   }
+  if (!covered) return TUTEL_AMD_ENOTSUP;
+  if (query) return 0;
+  a.g[0].ntm = p1.ntm; a.g[0].ntn = p1.ntn;  // the ring's tiles: one M-tile, 256 columns
+  a.g[1].ntm = p2.ntm; a.g[1].ntn = p2.ntn;
   a.ctl = ffn_ctl(st, E_loc);
   if (a.ctl == nullptr) return TUTEL_AMD_ENOTSUP;  // (first use inside a stream capture: the two-launch path is always there)
   a.xcc_queue = mode == 2 ? 0 : 1;
@@ -324,6 +330,7 @@ extern "C" int tutel_amd_expert_ffn(const void *X, int64_t x_stride_e, int ldx, 
                                     int64_t hid_stride_e, int ldh, const void *W2, int64_t w2_stride_e, int ldw2, const void *b2,
                                     int64_t b2_stride_e, void *D, int64_t d_stride_e, int ldd, int E_loc, int R, int M, int H, int M_out,
                                     int dtype, int act, tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(dtype == TUTEL_BF16 || dtype == TUTEL_F16, "tutel_amd_expert_ffn: dtype must be bf16 or fp16 (got %d)", dtype);
   TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && M >= 1 && H >= 1 && M_out >= 1, "tutel_amd_expert_ffn: bad sizes");
   if (E_loc == 0 || R == 0) return 0;

@@ -27,7 +27,7 @@
 // Three kernels share this file: the register-staged 128 x 128 kernel described above, its LDS-DMA
 // sibling (global_load_lds, no VGPR / ds_write staging), and the 256-row-tile LDS-DMA kernel for
 // more than 128 rows per expert (256 x 256, or 256 x 128 on a three-slot ring), where the bound is
-// the L2 -> CU path rather than HBM.  launch_gemm() picks; every kernel walks k in the same order
+// the L2 -> CU path rather than HBM.  gemm_plan (gemm_plan.hip) picks; every kernel walks k in the same order
 // for a given output element, so the choice never changes a bit of the result.
 #include <stdlib.h>
 
@@ -741,7 +741,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void expert_gemm_pp_kernel(GemmArgs 
     gemm_epilogue_lds<T, ACT, 2, true>(p, acc, no_bias, smem + wid * (64 * (2 * 64 + 16)), e, m0, n0, wm, wn, lane, row_limit);
   } else {
     if (!EARLY_BIAS) PP_LOAD_BIAS();
-    if ((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15)) {
+    if (!gemm_out_rows16(p)) {
       gemm_epilogue<T, ACT, 4>(p, acc, bias_r, e, m0, n0, wm, wn, l31, kg, row_limit);  // rows not 16-byte aligned
       return;
     }
@@ -776,16 +776,6 @@ bool tutel_lds_optin(const void *kern, size_t lds) {
   if (i == n && n < MAXK) { seen[n] = kern; done[n] = 0; ++n; }
   if (i < MAXK && dev >= 0) done[i] |= 1ull << dev;
   return true;
-}
-
-// LDS of every ping-pong launch, 136 KB: the epilogue staging (8 waves x 64 rows x 272 B) > the two K-tile buffers (128 KB)
-static constexpr size_t PP_LDS_BYTES = (size_t)8 * 64 * EP_PITCH;
-static_assert(PP_LDS_BYTES >= (size_t)2 * PP_BUF * 2, "LDS request must cover the K-tile buffers");
-
-template <typename T, int ACT, bool W_ONCE, bool RAGGED = false, bool EARLY_BIAS = false>
-static int launch_pp_cfg(const GemmArgs &b, hipStream_t st) {
-  return launch_lds(expert_gemm_pp_kernel<T, ACT, W_ONCE, RAGGED, EARLY_BIAS>, b.E_loc * b.ntm * b.ntn, GB_THREADS, PP_LDS_BYTES, st, b,
-                    "tutel_amd_expert_gemm");
 }
 
 // ---- split-K launches: workspace per (device, stream) -------------------------------------------------------------------------
@@ -839,84 +829,6 @@ static bool splitk_workspace(hipStream_t st, size_t tiles, float **ws, uint32_t 
   return true;
 }
 
-// 0: launched split; 1: not applicable here (the caller launches the unsplit grid); < 0: error
-template <typename T, int ACT>
-static int launch_pp_splitk(const GemmArgs &a, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = (a.R + GB_BM - 1) / GB_BM;
-  b.ntn = (a.N + 255) / 256;
-  const size_t tiles = (size_t)b.E_loc * b.ntm * b.ntn;
-  const int nk = a.K / GL_BK;
-  // whole 256-row tiles only (no ragged variant), an even number of K-tiles with at least four per half (the steady-state loop),
-  // a multiple of four tiles (so that the two workgroups of a tile are neighbours on one XCD in the work order), 16-byte rows
-  if (a.row_counts != nullptr || a.R % GB_BM != 0 || (nk & 1) || nk < 8 || (tiles & 3) || a.rot_on) return 1;
-  if ((a.ldd & 7) || (a.d_stride_e & 7) || (a.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(a.D) & 15)) return 1;
-  if (!splitk_workspace(st, tiles, &b.sk_ws, &b.sk_flags)) return 1;
-  return launch_lds(expert_gemm_pp_kernel<T, ACT, false, false, false, true>, (unsigned)(2 * tiles), GB_THREADS, PP_LDS_BYTES, st, b,
-                    "tutel_amd_expert_gemm");
-}
-
-template <typename T, int ACT>
-static int launch_pp(const GemmArgs &a, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = (a.R + GB_BM - 1) / GB_BM;
-  b.ntn = (a.N + 255) / 256;
-  // a last M-tile with >= 32 padding rows, or per-expert row counts: the variant that skips padded 32-row groups
-  const int tail_rows = b.R % GB_BM;
-  const bool ragged = b.row_counts != nullptr || (tail_rows != 0 && tail_rows <= GB_BM - 32);
-  // bias fetched before the K loop (full tiles; +0.5-1.7 % on every MFMA-bound shape, profiles/r03_pp_bias_ab.json); 0 = after it, for A/B
-  const bool early = tutel_get_option(TUTEL_OPT_GEMM_PERSIST) != 0;
-  if (b.ntm == 1 && (long long)b.E_loc * b.ntn >= 256)
-    return ragged ? launch_pp_cfg<T, ACT, true, true>(b, st) : (early ? launch_pp_cfg<T, ACT, true, false, true>(b, st) : launch_pp_cfg<T, ACT, true>(b, st));
-  return ragged ? launch_pp_cfg<T, ACT, false, true>(b, st) : (early ? launch_pp_cfg<T, ACT, false, false, true>(b, st) : launch_pp_cfg<T, ACT, false>(b, st));
-}
-
-// packed dropless layout: the 256 x 256 ping-pong kernel over the tile table (see tutel_expert_gemm_packed).  Always the RAGGED form
-// (an expert's last tile is partial); W_ONCE by the padded path's rule with one tile per expert, which is what the grid shape says
-// when the experts cover the chip -- an expert with more rows than one tile then streams its weights once per tile, as padded does.
-template <typename T, int ACT>
-static int launch_pp_packed(const GemmArgs &a, int tiles_bound, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = 1;
-  b.ntn = (a.N + 255) / 256;
-  const long long grid = (long long)tiles_bound * b.ntn;
-  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_expert_gemm_packed: grid too large");
-  auto kern = (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, true, true, false, false, true>
-                                                 : expert_gemm_pp_kernel<T, ACT, false, true, false, false, true>;
-  return launch_lds(kern, (unsigned)grid, GB_THREADS, PP_LDS_BYTES, st, b, "tutel_expert_gemm_packed");
-}
-
-// fused gate/up GEMM (GATE_UP ping-pong kernel): 256 x 128 output tiles, ntn = ceil(N / 128).  Padded: grid E_loc x M-tiles x N-tiles;
-// packed: tiles_bound x N-tiles over the tile table.  Always the RAGGED form (dropless row counts).  The packed form (the layer's hot
-// path) takes W_ONCE by the padded rule -- one M-tile per expert and the chip covered: every weight byte is fetched by one block --
-// the padded entry point never does (one instantiation fewer per activation; the hint changes no bits).
-template <typename T, int ACT, bool PACKED>
-static int launch_gate_up(const GemmArgs &a, int tiles_bound, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = PACKED ? 1 : (a.R + GB_BM - 1) / GB_BM;
-  b.ntn = (a.N + 127) / 128;
-  const long long grid = PACKED ? (long long)tiles_bound * b.ntn : (long long)a.E_loc * b.ntm * b.ntn;
-  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_gate_up: grid too large");
-  auto kern = PACKED && (long long)a.E_loc * b.ntn >= 256 ? expert_gemm_pp_kernel<T, ACT, PACKED, true, false, false, PACKED, true>
-                                                          : expert_gemm_pp_kernel<T, ACT, false, true, false, false, PACKED, true>;
-  return launch_lds(kern, (unsigned)grid, GB_THREADS, PP_LDS_BYTES, st, b, "tutel_amd_expert_gemm_gate_up");
-}
-
-template <typename T, bool KM, int ACT, int NI, int NS = 2, bool BUF = false, int BM = GB_BM, bool FL = false>
-static int launch_big(const GemmArgs &a, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = (a.R + BM - 1) / BM;
-  b.ntn = (a.N + NI * 64 - 1) / (NI * 64);
-  const size_t lds_k = (size_t)NS * (BM / 128 + NI / 2) * GL_STAGE * 2 + (FL ? 16384 : 0), lds_e = BUF ? (size_t)(BM / 32) * 64 * (NI * 64 + 16) : 0;
-  const size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  return launch_lds(expert_gemm_big_kernel<T, KM, ACT, NI, NS, BUF, BM, FL>, a.E_loc * b.ntm * b.ntn, BM * 2, lds, st, b, "tutel_amd_expert_gemm");
-}
-
-template <typename T, bool KM, int ACT>
-static int launch_glds(const GemmArgs &a, int grid, hipStream_t st) {
-  return launch_lds(expert_gemm_glds_kernel<T, KM, ACT, true, true>, grid, GM_THREADS, (size_t)4 * GL_STAGE * 2, st, a, "tutel_amd_expert_gemm");
-}
-
 // -------------------------------------------------------------------------------------------
 // ds_read_b64_tr_b16 permutation probe (self-test)
 // -------------------------------------------------------------------------------------------
@@ -940,91 +852,47 @@ extern "C" int tutel_amd_probe_tr16(uint16_t *out, tutel_stream_t stream) {
 // -------------------------------------------------------------------------------------------
 // C ABI
 // -------------------------------------------------------------------------------------------
-static constexpr size_t gemm_lds_bytes(bool kmajor) {
-  return (size_t)(2 * GM_BM * (64 + 8) + 2 * (kmajor ? GM_BN * (64 + 8) : 64 * GM_LDN)) * 2;
+// plan -> the one instantiation it names (every kernel of this file takes the argument block by value)
+using GemmKernel = void (*)(GemmArgs);
+template <typename T, int ACT>
+static GemmKernel plan_kernel(const GemmPlan &p) {
+  const bool km = p.w_kmajor != 0;
+  switch (p.family) {
+    case TUTEL_GEMM_STAGED_128: return km ? expert_gemm_kernel<T, true, ACT, true, true> : expert_gemm_kernel<T, false, ACT, true, true>;
+    case TUTEL_GEMM_GLDS_128: return km ? expert_gemm_glds_kernel<T, true, ACT, true, true> : expert_gemm_glds_kernel<T, false, ACT, true, true>;
+    case TUTEL_GEMM_PACKED_NMAJOR:
+      if constexpr (ACT == TUTEL_ACT_NONE || ACT == TUTEL_ACT_RELU) return expert_gemm_kernel<T, false, ACT, true, true, true>;
+      break;
+    case TUTEL_GEMM_RING:  // <T, KM, ACT, NI, NS, BUF, BM, FL>
+      if (p.bm == 128) return p.fl ? expert_gemm_big_kernel<T, true, ACT, 4, 3, true, 128, true> : expert_gemm_big_kernel<T, true, ACT, 4, 3, true, 128, false>;
+      if (p.ni == 4) return km ? expert_gemm_big_kernel<T, true, ACT, 4, 2> : expert_gemm_big_kernel<T, false, ACT, 4, 2>;
+      if (p.ns == 2) return expert_gemm_big_kernel<T, true, ACT, 2, 2>;
+      return p.buf ? expert_gemm_big_kernel<T, true, ACT, 2, 3, true> : expert_gemm_big_kernel<T, true, ACT, 2, 3>;
+    case TUTEL_GEMM_PINGPONG:  // <T, ACT, W_ONCE, RAGGED, EARLY_BIAS, SPLITK, PACKED, GATE_UP>
+      if (p.gate_up) {
+        if constexpr (ACT != TUTEL_ACT_NONE) {
+          if (!p.packed) return expert_gemm_pp_kernel<T, ACT, false, true, false, false, false, true>;
+          return p.w_once ? expert_gemm_pp_kernel<T, ACT, true, true, false, false, true, true> : expert_gemm_pp_kernel<T, ACT, false, true, false, false, true, true>;
+        }
+        break;
+      }
+      if (p.packed) return p.w_once ? expert_gemm_pp_kernel<T, ACT, true, true, false, false, true> : expert_gemm_pp_kernel<T, ACT, false, true, false, false, true>;
+      if (p.splitk) return expert_gemm_pp_kernel<T, ACT, false, false, false, true>;
+      if (p.ragged) return p.w_once ? expert_gemm_pp_kernel<T, ACT, true, true> : expert_gemm_pp_kernel<T, ACT, false, true>;
+      if (p.early_bias) return p.w_once ? expert_gemm_pp_kernel<T, ACT, true, false, true> : expert_gemm_pp_kernel<T, ACT, false, false, true>;
+      return p.w_once ? expert_gemm_pp_kernel<T, ACT, true> : expert_gemm_pp_kernel<T, ACT, false>;
+  }
+  return nullptr;
 }
 
-template <typename T, bool KM, int ACT>
-static int launch_cfg(const GemmArgs &a, int grid, hipStream_t st) {
-  return launch_lds(expert_gemm_kernel<T, KM, ACT, true, true>, grid, GM_THREADS, gemm_lds_bytes(KM), st, a, "tutel_amd_expert_gemm");
-}
-
-// Kernel choice per weight layout, from on-hardware A/B at the headline shape and at R = 1024
-// rows/expert (tools/gemm_sweep.py, MI355X, round 1):
-//   k-major W (fc1): LDS-DMA kernel          126-132 us  (register-staged: 136-140 us)
-//   n-major W (fc2): register-staged kernel  124-128 us  (LDS-DMA: 128-130 us; its tr-read image
-//                                                         has residual bank conflicts)
-// both with non-temporal weight loads and the rotated K order (rows are 4 KB apart in both layouts;
-// without the per-block stagger all resident blocks sit at the same k offset: k-major 158 -> 143 us,
-// n-major 142 -> 130 us when the weights really come from HBM, i.e. fc1/fc2 alternating as in the
-// layer -- a warm Infinity Cache hides this, so A/B runs must alternate the two weight sets).  What did NOT pay (kept out of the tree, see git history): BK=128, single
-// LDS buffer at 3 blocks/CU, prefetch distance 2 (two register sets), a 128x256 8-wave 3-stage
-// LDS-DMA ring, a single-stage LDS-DMA variant at 4 blocks/CU.  Ablation: compute alone 69 us, loads+staging alone 80-115 us -- the remaining
-// loss is phase serialisation inside a block, not DRAM (pure loads of the same pattern: 77-90 us).
-// tutel_amd_set_option(TUTEL_OPT_GEMM_IMPL, 0|1) forces register-staged | LDS-DMA for A/B runs.
-template <typename T, bool KM, int ACT>
-static int launch_gemm(const GemmArgs &a, int grid, hipStream_t st) {
-  const int impl = tutel_get_option(TUTEL_OPT_GEMM_IMPL), big = tutel_get_option(TUTEL_OPT_GEMM_TILE);
-  const bool ring256_ok = KM && a.fits32 && a.N >= 256 && a.R <= GM_BM;
-  const bool ring256 = ring256_ok && (impl == 4 || (impl < 0 && (long long)a.E_loc * ((a.N + 255) / 256) >= 256));
-  // Fused location FIRST: a request for it (or the eligibility query, fl_loc == NULL) must never fall into one of the launches
-  // below -- only the 128 x 256 ring kernel has the fused form (capacity <= 128 rows per expert), and a query launches nothing.
-  // K >= 128: the prologue's `s_waitcnt vmcnt(16)` counts the weight DMA of TWO K-tiles behind the idx bytes (with one
-  // K-tile only 8 follow and the wait would not cover them).
-  if (a.fl_idx8 != nullptr) {
-    if (!(ring256 && KM && big <= 0 && a.a_rows != nullptr && a.row_counts == nullptr && a.fl_n >= 1 && a.fl_n <= 15360 && a.E_loc <= 128 && a.K >= 2 * GL_BK)) {
-      tutel_set_error("tutel_expert_gemm_gather_fl: this launch does not take the fused-location ring kernel");
-      return TUTEL_AMD_ENOTSUP;
-    }
-    if (a.fl_loc == nullptr) return 0;  // eligibility query
-    return launch_big<T, true, ACT, 4, 3, true, 128, KM>(a, st);   // (FL = KM: the n-major instantiations never reach this line)
-  }
-  // R > 128 rows per expert: the 256-row tiles (more flop per byte crossing L2 -> CU) -- provided the grid
-  // still covers the chip: one such block occupies a CU, so with fewer than ~3/4 x 256 blocks CUs sit idle.
-  // 256 x 256 first, 256 x 128 when only that fills the chip (a pipeline stage of the overlapped
-  // all-to-all is half a GEMM), else the 128-tile kernels.  big = 1 forces 256 x 256, 2 / 3 force 256 x 128.
-  if (a.N >= GM_BN && big != 0) {
-    const long long mt256 = (long long)a.E_loc * ((a.R + GB_BM - 1) / GB_BM);
-    const long long t256 = mt256 * ((a.N + 255) / 256), t128 = mt256 * ((a.N + 127) / 128);
-    // more than one 128-row tile per expert (R > 128) already pays: the 128-tile kernels would stream every
-    // weight tile once per M-tile (dropless capacity 157 at the headline shape: fc1 214 us vs 118 at R = 128)
-    // Beside a co-running collective (a stage of the overlapped pipeline: RCCL's kernels hold whole CUs on the other stream) a grid of
-    // one workgroup per CU turns into two rounds as soon as a few CUs are taken: the 256 x 128 ring kernel at 4 x 1024 x 2048^2 goes
-    // from 42 us to 70 us with 16 CUs held and to 57 us beside a device copy, the 128-block 256 x 256 grid stays at 52 us
-    // (tools/contention_probe.py, profiles/r03_contention.json).  So with the co-run hint the half-filled 256 x 256 grid wins.
-    const bool corun_pp = tutel_gemm_corun() && big < 0 && a.R > GM_BM && t256 >= 96 && t256 < 192;
-    // Round 5: 96 .. 191 tiles of 256 x 256 (half the chip) CAN run two workgroups per tile, each over half of K (expert_gemm_pp_kernel
-    // <.., SPLITK>).  Built, correct (tests/test_ops_gpu.py::test_split_k_pingpong_kernel) and measured SLOWER than what it was to replace:
-    // the stage GEMM 4 x 1024 x 2048^2 takes 52.6-58.6 us split against 40.8 us on the 256 x 128 ring and 50.5 us on the unsplit half-chip
-    // grid -- the hand-over of 128 KB out + 128 KB in per workgroup through system-scope accesses costs more than the half K loop it saves
-    // (profiles/r05_splitk_probe.json).  So it is opt-in only: TUTEL_OPT_GEMM_SPLITK = 1.
-    if (KM && a.fits32 && a.mul == nullptr && a.R > GM_BM && t256 >= 96 && t256 < 192 && (big < 0 || big == 4) &&
-        tutel_get_option(TUTEL_OPT_GEMM_SPLITK) == 1) {
-      const int rc = launch_pp_splitk<T, ACT>(a, st);
-      if (rc <= 0) return rc;
-    }
-    // What the same A/B did show: with 129 .. 191 tiles the 256 x 128 ring needs TWO rounds of workgroups (2 x t256 > 256 CUs) where the
-    // unsplit 256 x 256 grid needs one at 1.5 x the flop per byte -- 5 x 1024 x 2048 x 4096: 124 us on the ring, 88.5 us on 160 ping-pong
-    // tiles (695 -> 971 TFLOP/s).  At <= 128 tiles the ring's single round wins (40.8 vs 50.5 us at 128).
-    const bool pp_one_round = big < 0 && a.R > GM_BM && t256 > 128 && t256 < 192;
-    if (KM && a.fits32 && (big == 4 || corun_pp || pp_one_round || (big < 0 && a.R > GM_BM && t256 >= 192))) return launch_pp<T, ACT>(a, st);
-    if (big == 1 || big == 4 || (big < 0 && a.R > GM_BM && t256 >= 192)) return launch_big<T, KM, ACT, 4>(a, st);
-    // 256 x 128: a three-slot ring (3 x 48 KB of LDS) keeps two tiles in flight: +3-4 % over two slots on the
-    // stage shapes it is chosen for (tools/stage_probe.py); big = 2 forces the two-slot form for A/B runs
-    if (KM && big == 2) return launch_big<T, true, ACT, 2, 2>(a, st);
-    if (KM && (big == 3 || (big < 0 && a.R > GM_BM && t128 >= 192)))
-      return a.fits32 && tutel_get_option(TUTEL_OPT_GEMM_IMPL) != 2 ? launch_big<T, true, ACT, 2, 3, true>(a, st) : launch_big<T, true, ACT, 2, 3>(a, st);
-  }
-  // Round 4: all rows of an expert in one M-tile (R <= 128: weight streaming from HBM is the bound) and k-major weights -> the
-  // 128 x 256 tile on a three-slot ring, one 4-wave block per CU: the token tile crosses L2 -> LDS once per 256 columns instead of
-  // once per 128 and 96 KB of DMA are in flight per CU.  Headline shape (64 x 128 rows, 2048^2): fc1 112.4 -> 108.1 us, fc2
-  // 111.9 -> 106.6 us, the forward 264.0 -> 258.4 us, same bits (profiles/r04_headline_ab.json).  Only when the grid still covers
-  // the chip (one 144 KB block per CU): with fewer tiles the 128 x 128 kernel's twice as many blocks keep more CUs busy.
-  // TUTEL_OPT_GEMM_IMPL = 4 forces it (where it applies), 1 forces the 128 x 128 LDS-DMA kernel.
-  if (ring256) return launch_big<T, true, ACT, 4, 3, true, 128>(a, st);
-  const bool use_dma = impl < 0 ? KM : (impl == 1 || impl == 4);
-  if (use_dma) return launch_glds<T, KM, ACT>(a, grid, st);
-  return launch_cfg<T, KM, ACT>(a, grid, st);
+template <typename T, int ACT>
+static int launch_plan(const GemmPlan &p, const GemmArgs &a, hipStream_t st) {
+  const GemmKernel kern = plan_kernel<T, ACT>(p);
+  TUTEL_REQUIRE(kern != nullptr, "%s: no kernel for this plan", p.entry);
+  GemmArgs b = a;
+  b.ntm = p.ntm;
+  b.ntn = p.ntn;
+  return launch_lds(kern, (unsigned)p.grid, p.threads, (size_t)p.lds_bytes, st, b, p.entry);
 }
 
 // dtype x activation -> f(ElemTag<element type>, std::integral_constant<int, ACT>) for the activations listed in ACTS, the only ones
@@ -1106,6 +974,32 @@ int tutel_gemm_args(const GemmProblem &g, GemmArgs *out) {
   return 0;
 }
 
+static int plan_refusal(const GemmPlan &pl, const GemmArgs &a) {
+  gemm_plan_report(pl, a);
+  tutel_set_error("%s", pl.error);
+  return pl.status;
+}
+
+// What every entry point does once the argument block and its plan stand, inside its own activation check (ACTS, other): refuse as
+// the plan says, hand the plan to an armed tutel_amd_expert_gemm_plan_next, or launch.  Per-stage timing brackets everything but
+// a call with stage < 0 (a fused-location query: nothing is launched, nothing timed) and an armed call, which makes no HIP call at all.
+template <int... ACTS, typename Other>
+static int run_plan(const GemmPlan &pl, const GemmArgs &a, int dtype, int act, int stage, hipStream_t st, Other &&other) {
+  auto go = [&] {
+    return dispatch_dtype_act<ACTS...>(
+        dtype, act,
+        [&](auto t, auto ac) {
+          if (pl.status != GEMM_PLAN_LAUNCH && pl.status != GEMM_PLAN_FL_QUERY) return plan_refusal(pl, a);
+          if (gemm_plan_report(pl, a) || pl.status == GEMM_PLAN_FL_QUERY) return 0;
+          return launch_plan<typename decltype(t)::type, decltype(ac)::value>(pl, a, st);
+        },
+        other);
+  };
+  if (gemm_plan_asked() || stage < 0) return go();
+  StageScope scope(stage, st);
+  return go();
+}
+
 // internal (common.h): one grouped GEMM, every form
 int tutel_expert_gemm(const GemmProblem &g, int w_kmajor, int act, hipStream_t st) {
   TUTEL_REQUIRE(g.d_can == nullptr || g.d_peer != nullptr, "tutel_expert_gemm_peer: null peer table");
@@ -1117,34 +1011,41 @@ int tutel_expert_gemm(const GemmProblem &g, int w_kmajor, int act, hipStream_t s
   GemmArgs a;
   const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
-  long long grid_ll = (long long)g.E_loc * a.ntm * a.ntn;
-  TUTEL_REQUIRE(grid_ll < 0x7fffffffLL, "tutel_amd_expert_gemm: grid too large");
-  const int grid = (int)grid_ll;
-  auto go = [&]() -> int {
-    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
-        g.dtype, act,
-        [&](auto t, auto ac) {
-          using T = typename decltype(t)::type;
-          return w_kmajor ? launch_gemm<T, true, decltype(ac)::value>(a, grid, st) : launch_gemm<T, false, decltype(ac)::value>(a, grid, st);
-        },
-        [&] { tutel_set_error("tutel_amd_expert_gemm: unknown activation %d", act); return -1; });
-  };
-  if (g.fl_idx8 != nullptr && g.fl_loc == nullptr) return go();  // eligibility query of the fused-location path: nothing is launched, nothing timed
+  GemmKnobs k = gemm_knobs();
+  GemmPlan pl = gemm_plan(a, w_kmajor != 0, false, 0, k);
+  if (pl.status == -1) return plan_refusal(pl, a);  // the grid: refused before the activation is looked at
+  // split-K needs its workspace; where there is none (first use inside a stream capture), the plan without it is the one launched
+  if (pl.splitk && !gemm_plan_asked() && !splitk_workspace(st, (size_t)pl.grid / 2, &a.sk_ws, &a.sk_flags)) {
+    k.splitk = 0;
+    pl = gemm_plan(a, w_kmajor != 0, false, 0, k);
+  }
   // per-stage timing: the launch with a fused activation is fc1, the one without is fc2 (callers that know better --
-  // the native pipeline -- set a hint)
-  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
-  return go();
+  // the native pipeline -- set a hint); the eligibility query of the fused-location path is not timed
+  const bool query = g.fl_idx8 != nullptr && g.fl_loc == nullptr;
+  return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+      pl, a, g.dtype, act, query ? -1 : (act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2), st,
+      [&] { tutel_set_error("tutel_amd_expert_gemm: unknown activation %d", act); return -1; });
+}
+
+// the operands the three padded C entry points share, field for field
+static GemmProblem padded_problem(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W, int64_t w_stride_e,
+                                  int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e, int64_t d_stride_w,
+                                  int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, const int32_t *row_counts, int row_align) {
+  GemmProblem g;
+  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
+  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
+  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
+  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  return g;
 }
 
 extern "C" int tutel_amd_expert_gemm(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W, int w_kmajor,
                                      int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e,
                                      int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
                                      const int32_t *row_counts, int row_align, tutel_stream_t stream) {
-  GemmProblem g;
-  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
-  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
-  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
-  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  GemmPlanScope scope;
+  const GemmProblem g = padded_problem(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_stride_e, ldw, bias, bias_stride_e, D, d_stride_e, d_stride_w,
+                                       d_rows_per_w, ldd, E_loc, R, N, K, dtype, row_counts, row_align);
   return tutel_expert_gemm(g, w_kmajor, act, (hipStream_t)stream);
 }
 
@@ -1152,12 +1053,10 @@ extern "C" int tutel_amd_expert_gemm_glu(const void *A, int64_t a_stride_e, int6
                                          int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, const void *G, void *D,
                                          int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype,
                                          int act, const int32_t *row_counts, int row_align, tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(G != nullptr || E_loc == 0 || R == 0, "tutel_amd_expert_gemm_glu: null gating operand");
-  GemmProblem g;
-  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
-  g.W = W; g.w_stride_e = w_stride_e; g.ldw = ldw; g.bias = bias; g.bias_stride_e = bias_stride_e;
-  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
-  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  GemmProblem g = padded_problem(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W, w_stride_e, ldw, bias, bias_stride_e, D, d_stride_e, d_stride_w,
+                                 d_rows_per_w, ldd, E_loc, R, N, K, dtype, row_counts, row_align);
   g.mul = G;
   return tutel_expert_gemm(g, w_kmajor, act, (hipStream_t)stream);
 }
@@ -1166,6 +1065,7 @@ extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_
                                             int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e,
                                             int ldd, int E_loc, int R, int N, int K, int dtype, int act, const int32_t *row_counts, int row_align,
                                             tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(slot_map != nullptr && T >= 1, "tutel_amd_expert_gemm_gather: need a slot map and T >= 1");
   GemmProblem g;
   g.A = X; g.lda = ldx;
@@ -1182,53 +1082,34 @@ extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_
 // addressing, the out-of-range zero rows and the row limit work unchanged; what changes per block is where its tile, expert and row
 // limit come from (the device tile table).
 
-// n-major weights over the packed layout: the register-staged 128 x 128 kernel (its transposing LDS read takes W [K][N] as stored),
-// two 128-row M-tiles per entry of the 256-row tile table, grid sized by the host's tile bound
-template <typename T, int ACT>
-static int launch_packed_nmajor(const GemmArgs &a, int tiles_bound, hipStream_t st) {
-  GemmArgs b = a;
-  b.ntm = 1;
-  b.ntn = (a.N + GM_BN - 1) / GM_BN;
-  const long long grid = (long long)tiles_bound * 2 * b.ntn;
-  TUTEL_REQUIRE(grid >= 1 && grid < 0x7fffffffLL, "tutel_amd_expert_gemm_packed: grid too large");
-  return launch_lds(expert_gemm_kernel<T, false, ACT, true, true, true>, (unsigned)grid, GM_THREADS, gemm_lds_bytes(false), st, b,
-                    "tutel_amd_expert_gemm_packed");
-}
-
 // ---- fused gate/up GEMM of a SwiGLU expert (GATE_UP ping-pong kernel) -------------------------------------------------------------
 static int gate_up_notsup(const char *why) {
   tutel_set_error("tutel_amd_expert_gemm_gate_up: not covered: %s", why);
   return TUTEL_AMD_ENOTSUP;
 }
 
-template <bool PACKED>
-static int gate_up_act(const GemmArgs &a, int dtype, int act, int tiles_bound, hipStream_t st) {
-  return dispatch_dtype_act<TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
-      dtype, act, [&](auto e, auto ac) { return launch_gate_up<typename decltype(e)::type, decltype(ac)::value, PACKED>(a, tiles_bound, st); },
-      [] { return gate_up_notsup("the gate activation must be relu, gelu or silu"); });
-}
 static bool gate_up_act_ok(int act) { return act == TUTEL_ACT_RELU || act == TUTEL_ACT_GELU || act == TUTEL_ACT_SILU; }
+static int gate_up_run(const GemmArgs &a, int dtype, int act, int tiles_bound, hipStream_t st) {
+  return run_plan<TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(gemm_plan(a, true, true, tiles_bound, gemm_knobs()), a, dtype, act, TUTEL_STAGE_FC1, st,
+                                                                 [] { return gate_up_notsup("the gate activation must be relu, gelu or silu"); });
+}
 
 extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
                                              const void *W_gate, const void *W_up, int64_t w_stride_e, int ldw, void *D, int64_t d_stride_e,
                                              int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
                                              const int32_t *row_counts, int row_align, tutel_stream_t stream) {
+  GemmPlanScope scope;
   if (!gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
-  GemmProblem g;
-  g.A = A; g.a_stride_e = a_stride_e; g.a_stride_w = a_stride_w; g.a_rows_per_w = a_rows_per_w; g.lda = lda;
-  g.W = W_gate; g.w_stride_e = w_stride_e; g.ldw = ldw;
-  g.D = D; g.d_stride_e = d_stride_e; g.d_stride_w = d_stride_w; g.d_rows_per_w = d_rows_per_w; g.ldd = ldd;
-  g.E_loc = E_loc; g.R = R; g.N = N; g.K = K; g.dtype = dtype; g.row_counts = row_counts; g.row_align = row_align;
+  const GemmProblem g = padded_problem(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W_gate, w_stride_e, ldw, nullptr, 0, D, d_stride_e, d_stride_w,
+                                       d_rows_per_w, ldd, E_loc, R, N, K, dtype, row_counts, row_align);
   GemmArgs a;
   const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_amd_expert_gemm_gate_up: W_up must be a 16-byte aligned pointer");
   if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
-  if ((ldd & 7) || (d_stride_e & 7) || (d_stride_w & 7) || ((uintptr_t)D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
+  if (!gemm_out_rows16(a)) return gate_up_notsup("output rows must be 16-byte aligned");
   a.w_up = W_up;
-  hipStream_t st = (hipStream_t)stream;
-  StageScope stage(TUTEL_STAGE_FC1, st);
-  return gate_up_act<false>(a, dtype, act, 0, st);
+  return gate_up_run(a, dtype, act, 0, (hipStream_t)stream);
 }
 
 // internal (common.h): the grouped GEMM over the packed layout; w_up != NULL: the fused gate/up GEMM over it
@@ -1243,21 +1124,21 @@ int tutel_expert_gemm_packed(const GemmProblem &g, int w_kmajor, int act, const 
   if (w_up != nullptr) {
     TUTEL_REQUIRE(((uintptr_t)w_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
     if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
-    if ((g.ldd & 7) || ((uintptr_t)g.D & 15)) return gate_up_notsup("output rows must be 16-byte aligned");
+    if (!gemm_out_rows16(a)) return gate_up_notsup("output rows must be 16-byte aligned");  // (the packed layout has no expert strides)
     a.w_up = w_up;
-    StageScope stage(TUTEL_STAGE_FC1, st);
-    return gate_up_act<true>(a, g.dtype, act, t.tiles_bound, st);
+    return gate_up_run(a, g.dtype, act, t.tiles_bound, st);
   }
   if (!a.fits32) {
     tutel_set_error("tutel_expert_gemm_packed: operands past 2 GiB are not covered");
     return TUTEL_AMD_ENOTSUP;
   }
-  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  const GemmPlan pl = gemm_plan(a, w_kmajor != 0, false, t.tiles_bound, gemm_knobs());
+  const int stage = act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2;
   if (!w_kmajor)
-    return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(
-        g.dtype, act, [&](auto e, auto ac) { return launch_packed_nmajor<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
-        [&] { tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu"); return TUTEL_AMD_ENOTSUP; });
-  return dispatch_dtype_act<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
-      g.dtype, act, [&](auto e, auto ac) { return launch_pp_packed<typename decltype(e)::type, decltype(ac)::value>(a, t.tiles_bound, st); },
-      [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
+    return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(pl, a, g.dtype, act, stage, st, [&] {
+      tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu");
+      return TUTEL_AMD_ENOTSUP;
+    });
+  return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
+      pl, a, g.dtype, act, stage, st, [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
 }

@@ -16,6 +16,21 @@ struct GemmArgs;
 int tutel_gemm_args(const GemmProblem &g, GemmArgs *out);
 bool tutel_lds_optin(const void *kern, size_t lds);
 
+// Which kernel a grouped GEMM runs, and on what grid: decided by gemm_plan (gemm_plan.hip), a pure function -- no HIP call, no
+// option read, no pointer followed -- of the finished argument block, the weight layout, the form (tiles_bound > 0: the packed
+// layout's tile table drives the grid; gate_up: the fused gate/up GEMM) and the knobs, which the caller reads ONCE per entry point.
+// Everything that launches (launch_plan) or asks (ffn_covers, tutel_amd_expert_gemm_plan_next) goes through it.
+struct GemmKnobs { int impl, tile, persist, splitk, corun; };  // TUTEL_OPT_GEMM_IMPL / _TILE / _PERSIST / _SPLITK, the co-run hint
+GemmKnobs gemm_knobs();
+enum { GEMM_PLAN_LAUNCH = 0, GEMM_PLAN_FL_QUERY = 1 };          // GemmPlan::status; else TUTEL_AMD_ENOTSUP / -1 with `error`
+struct GemmPlan : tutel_amd_gemm_plan_t {                       // the fields tutel_amd_expert_gemm_plan_next shows (include/tutel_amd.h)
+  const char *entry;                                            // the entry point a launch failure names
+  const char *error;                                            // refusals: the text for tutel_amd_last_error
+};
+GemmPlan gemm_plan(const GemmArgs &a, bool w_kmajor, bool gate_up, int tiles_bound, const GemmKnobs &k);
+// to a waiting tutel_amd_expert_gemm_plan_next (GemmPlanScope, common.h): the plan; true = "return now", false = nobody asked: launch
+bool gemm_plan_report(const GemmPlan &pl, const GemmArgs &a, int covered = 0);
+
 // one launch with `lds` bytes of dynamic LDS: the opt-in (needed above 64 KB only), the launch, the launch check
 template <typename Kern, typename Args>
 static int launch_lds(Kern kern, unsigned grid, int threads, size_t lds, hipStream_t st, const Args &args, const char *what) {
@@ -88,14 +103,14 @@ struct GemmArgs {
   const int32_t *a_rows; int a_rows_mod; const void *a_zero;  // optional row gather for A (fused fast_encode)
   int a_span_bytes;                                           // gather: bytes of the token array (a_rows_mod rows)
   bool fits32;                                                // operands addressable with 32-bit byte offsets
-  bool rot_on;                                                // K-tile rotation (see launch_gemm)
+  bool rot_on;                                                // K-tile rotation (see tutel_gemm_args)
   bool sgather;                                               // ring kernels: slot-map entries through the scalar cache (TUTEL_OPT_GEMM_GATHER)
   int d_store;                                                // LDS epilogue: 1 write-through (sc0 sc1) stores, 0 plain (write-back), 2 non-temporal (TUTEL_OPT_GEMM_STORE)
   const uint8_t *fl_idx8; int fl_n; int32_t *fl_loc;          // fused location (FL kernels): byte copy of idx [k*T], its length, loc out
   const void *mul;                                            // optional epilogue multiplier, D's layout
   const uint64_t *d_peer; long long d_peer_off;               // optional: rows of source rank w go to d_peer[w] + d_peer_off (bytes)
   PeerCanary d_can;                                           // peer stores: epoch canaries written behind the rows (common.h)
-  float *sk_ws; uint32_t *sk_flags;                           // split-K ping-pong kernel: partial accumulators + hand-over flags (see launch_pp_splitk)
+  float *sk_ws; uint32_t *sk_flags;                           // split-K ping-pong kernel: partial accumulators + hand-over flags (see splitk_workspace)
   int ntm, ntn;
   int act_rt;                                                 // the activation when the tile is instantiated with GEMM_ACT_RUNTIME (expert_ffn.hip)
   // packed dropless layout (the PACKED ping-pong kernel only; dropless.hip): rows are global packed rows, M-tile i of the
@@ -105,6 +120,11 @@ struct GemmArgs {
   // fused gate/up GEMM of a SwiGLU expert (the GATE_UP ping-pong kernel only): the up-projection weights, W's layout and strides
   const void *w_up;
 };
+
+// output rows start on 16-byte boundaries: what the LDS epilogues' 16-byte stores need (else the direct-store epilogue runs)
+__host__ __device__ __forceinline__ bool gemm_out_rows16(const GemmArgs &p) {
+  return !((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15));
+}
 
 // address of output row m of expert e (elements of 2 bytes).  Plain: D + e*stride_e + (m / rpw)*stride_w + (m % rpw)*ldd.
 // Peer stores (IPC transport of the expert-parallel pipeline, ep.hip): the rows that came from source rank w = m / rpw are
@@ -799,7 +819,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
 
   tail();
   GM_PRELOAD_BIAS_N(NI);
-  if (BUF && !((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15))) {
+  if (BUF && gemm_out_rows16(p)) {
     __syncthreads();  // every wave is done with the K-tile stages: LDS is free for the staging regions
     unsigned char *stage = smem + wid * (64 * (NI * 64 + 16));
     if (ACT == GEMM_ACT_RUNTIME) {  // one copy of everything above for all activations; the same epilogue code (and bits) per activation

@@ -293,6 +293,7 @@ extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_
                                             void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
                                             const int32_t *tiles, const int32_t *ntiles, const int32_t *capacity, int tiles_bound,
                                             tutel_stream_t stream) {
+  GemmPlanScope scope;
   TUTEL_REQUIRE(E >= 1 && rows_bound >= 1 && tiles_bound >= 1 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_packed: bad sizes E=%d rows=%d tiles=%d N=%d K=%d",
                 E, rows_bound, tiles_bound, N, K);
   if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) {
