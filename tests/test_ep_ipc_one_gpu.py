@@ -1,4 +1,4 @@
-"""The IPC transport of the expert-parallel pipeline (csrc/ep.hip, round 4) with 2 and 4 ranks ON ONE GPU.
+"""The IPC transport of the expert-parallel pipeline (csrc/ep_comm.hip + csrc/ep.hip, round 4) with 2 and 4 ranks ON ONE GPU.
 
 The rank processes all map cuda:0 and each other's exchange segments (hipIpcOpenMemHandle works between processes on one
 device), so what runs here is the device-side protocol of a multi-GPU node, not an emulation of it: fast_encode stores its

@@ -482,6 +482,44 @@ def test_native_pipeline_equals_python_orchestration(oracle, monkeypatch):
             monkeypatch.setattr(ep_native, "forward_from_logits", real_fast)
 
 
+@pytest.mark.parametrize("post", [True, False])
+def test_staged_pipeline_of_a_c_caller_without_communicator(oracle, monkeypatch, post):
+    """The one route of tutel_amd_ep_forward that the layer never takes (it aliases the stage buffers and forces degree 1 without a
+    communicator): no communicator, degree 2 and DISTINCT enc / recv and send / back arrays, so that the single-rank "exchange"
+    is a copy per stage.  The arguments are those of a real layer forward, with fresh recv / back / y.  4 experts in 2 stages are
+    expert-sliced -- every GEMM launch keeps its 256 rows per expert -- so degree 2 returns the bits of degree 1 (and of the layer's
+    own aliased call); the oracle bounds all of them at the tolerance of the single-rank layer tests."""
+    import ctypes
+    from tutel_amd import _lib, ops
+    from tutel_amd.impls import ep_native
+    T, M, H, E, k = 512, 128, 192, 4, 2
+    x, *weights = oracle.make_problem(T, M, H, E, dtype=torch.bfloat16, seed=12)
+    layer = make_layer(M, H, E, k, 1.0, torch.bfloat16, weights, is_postscore=post, gate={"fp32_gate": True}).eval()
+    monkeypatch.setattr(ep_native, "FAST_PATH", False)
+    monkeypatch.setattr(ep_native, "FUSE_ENCODE", False)   # the staged route: the enc / send arrays exist
+    crits, xd = [], x.cuda()   # (kept alive: the arguments point at the tokens and into the routing tensors)
+    real = ep_native.forward
+    monkeypatch.setattr(ep_native, "forward", lambda layer, x, crit, degree: crits.append(crit) or real(layer, x, crit, degree))
+    with torch.no_grad():
+        y_layer = layer(xd)
+    (ws,) = layer._ep_workspaces.values()
+    base = ws.args
+    assert len(crits) == 1 and base.enc == base.recv and base.send == base.back and base.degree == 1 and base.capacity == 256
+
+    def call(degree):
+        a = _lib.EpArgs.from_buffer_copy(base)
+        recv, back, y = torch.empty_like(ws.bufs["enc"]), torch.empty_like(ws.bufs["send"]), torch.empty_like(y_layer)
+        a.recv, a.back, a.y, a.degree = recv.data_ptr(), back.data_ptr(), y.data_ptr(), degree
+        _lib.check(_lib.lib().tutel_amd_ep_forward(None, ctypes.byref(a), ops._stream()), "tutel_amd_ep_forward")
+        torch.cuda.synchronize()
+        return y
+    y1, y2 = call(1), call(2)
+    assert torch.equal(y1, y_layer), "distinct stage buffers (a copy per exchange) vs aliased ones"
+    assert torch.equal(y2, y1), "degree 2 vs degree 1"
+    yo = oracle.moe_forward(x, *weights, top_k=k, capacity_factor=1.0, fp32_gate=True, is_postscore=post, accum_fp32=True)[0]
+    _close(y2, yo, torch.bfloat16)
+
+
 def test_native_pipeline_through_rccl_single_rank():
     """The staged native pipeline -- the library's own RCCL communicator (ncclCommInitRank from a broadcast id),
     its communication stream and event table, ncclAllToAll per stage -- forced onto one rank: degree 2 and 4

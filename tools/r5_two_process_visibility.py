@@ -6,7 +6,7 @@ returned rows of the batch in between with two rank processes on one GPU; a one-
 
 Two (or W) rank processes share cuda:0, rendezvous over gloo and attach the IPC transport exactly as the product does (flag
 segment in uncached memory, data segment from hipMalloc mapped with hipIpcOpenMemHandle, signal / wait kernels, epochs).  Then
-tutel_amd_ep_ipc_selfcheck (csrc/ep.hip) runs writer process -> flag kernel -> wait kernel -> reader kernel on `MB` MiB per peer,
+tutel_amd_ep_ipc_selfcheck (csrc/ep_comm.hip) runs writer process -> flag kernel -> wait kernel -> reader kernel on `MB` MiB per peer,
 PASSES passes back to back with NO host synchronisation, the payload changing every pass, for every store flavour
 (plain | sc1 | sc0 sc1 | nt) x both queue layouts of the pipeline (reader on the writer's stream | on a side stream of another
 priority), REPEATS times.  A vector that still carries an earlier pass' pattern is a stale read; the reader counts them on the

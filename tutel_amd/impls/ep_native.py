@@ -35,7 +35,7 @@ HOSTED = int(os.environ.get("TUTEL_AMD_NATIVE_HOSTED", "0")) != 0  # bring-up / 
 #           processes that SHARE one GPU, and the first multi-GPU run should not have to debug two transports at once.  Set
 #           TUTEL_AMD_EP_IPC_VERIFIED=1 once tests/test_multi_gpu_rccl.py has passed on the hardware in question to make "auto" prefer
 #           the peer stores again (attach + payload-sized self-check, RCCL when that fails)
-#   "ipc"   peer stores over xGMI (IPC transport, csrc/ep.hip) when every rank can map every other rank's segment and the tagged
+#   "ipc"   peer stores over xGMI (IPC transport, csrc/ep_comm.hip) when every rank can map every other rank's segment and the tagged
 #           self-check passes on all of them; also for process groups that are not on the "nccl" backend (ranks that share one GPU: the tests)
 #   "rccl"  never attach the IPC transport
 TRANSPORT = os.environ.get("TUTEL_AMD_EP_TRANSPORT", "auto").lower()

@@ -110,7 +110,7 @@ class GraphedForward:
     def __call__(self, x):
         # a replay makes no library call, so nothing would ever report an exchange of the IPC transport that gave up (a peer that
         # never arrived, rows behind their flag): ask before every replay -- one read of a pinned host word.  The
-        # replay that gave up has poisoned its own output with NaN on the device (csrc/ep.hip::ep_poison_kernel).
+        # replay that gave up has poisoned its own output with NaN on the device (csrc/ep_comm.hip::ep_poison_kernel).
         if self._ep:
             from . import ep_native
             ep_native.ipc_status(self.layer.group, self.static_in.device)
