@@ -206,7 +206,7 @@ int tutel_amd_gate_grad(const void *x, const void *buf, int dtype, const int32_t
  * expert e are skipped and left unwritten, exactly the rows sparse_bmm_infer leaves
  * uninitialised (custom_kernel.cpp:878-886).
  *
- * dtype: TUTEL_BF16 or TUTEL_F16 (fp32/fp64 experts stay on the ATen/rocBLAS bmm).
+ * dtype: TUTEL_BF16 or TUTEL_F16 (fp32 experts: tutel_amd_expert_gemm_f32 below; fp64 experts stay on the ATen/rocBLAS bmm).
  * Requirements: K % 64 == 0, N % 8 == 0, lda/ldw/ldd and strides % 8 == 0 (16-byte rows). */
 int tutel_amd_expert_gemm(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w,
                           int lda, const void *W, int w_kmajor, int64_t w_stride_e, int ldw,
@@ -227,6 +227,29 @@ int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_t *slot_map
                                  int64_t bias_stride_e, void *D, int64_t d_stride_e, int ldd,
                                  int E_loc, int R, int N, int K, int dtype, int act,
                                  const int32_t *row_counts, int row_align, tutel_stream_t stream);
+
+/* The grouped GEMM of FP32 experts (csrc/expert_gemm_f32.hip), on the exact-f32 matrix instruction v_mfma_f32_32x32x2_f32:
+ *     D[e, r, n] = act( chain(e, r, n) + bias[e, n] )          A, W, bias, D all fp32
+ * Numeric contract (part of the interface; replayable on a CPU, tests/expert_gemm_f32_ref.c):
+ *     chain(e, r, n) = fmaf(a[K-1], w[K-1], ... fmaf(a[1], w[1], fmaf(a[0], w[0], 0.f)))     a = row (e, r) of A, w = column n of op(W[e])
+ * -- ONE accumulator per output, k ascending from 0, starting from 0.f, one rounding per step; no split-K, no rotated K order,
+ * nothing depends on the tile, on E_loc, R or the launch.  Then ONE fp32 add of bias[e, n] (skipped when bias is NULL) and the
+ * activation in fp32 (no contraction anywhere): relu fmaxf(v, 0.f); gelu 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+ * silu v / (1.f + expf(-v)) -- the formulas of the 16-bit GEMMs' epilogue; erff / expf are the device library's.
+ *   w_kmajor = 1: W[e] is [N, K] (batched_fc1_w);  w_kmajor = 0: W[e] is [K, N] (batched_fc2_w) -- both read as stored, no copies.
+ *   Rows of A and D: tutel_amd_expert_gemm's addressing, e*stride_e + (r / rows_per_w)*stride_w + (r % rows_per_w)*ld (elements).
+ *   slot_map != NULL: A is the TOKEN array [T, lda] and row (e, r) is A[slot_map[e*R + r] % T], a negative slot reads zero_row
+ *   (>= K zeros) -- tutel_amd_expert_gemm_gather's rule; a_stride_e / a_stride_w / a_rows_per_w are then ignored.
+ * Covered: K % 32 == 0, N % 4 == 0 (tutel_amd_expert_gemm_f32_supported(N, K) == 1: a pure function, no HIP call), leading
+ * dimensions and strides % 4 == 0, any R >= 1 and E_loc >= 1 with E_loc * R and the tile count E_loc * ceil(R / 128) * ceil(N / 128)
+ * below 2^31 (addresses are 64-bit byte offsets: nothing wraps), act one of TUTEL_ACT_*.  Ragged last tiles clamp their loads and
+ * mask their stores: nothing is read or written outside the operands.  Anything else returns TUTEL_AMD_ENOTSUP with nothing
+ * enqueued; E_loc == 0 or R == 0 is a successful no-op.  A, W and zero_row 16-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_f32_supported(int N, int K);
+int tutel_amd_expert_gemm_f32(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *W,
+                              int w_kmajor, int64_t w_stride_e, int ldw, const void *bias, int64_t bias_stride_e, void *D,
+                              int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                              int act, const int32_t *slot_map, int T, const void *zero_row, tutel_stream_t stream);
 
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert

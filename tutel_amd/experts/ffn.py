@@ -13,7 +13,10 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
   * the gathered-weight modes -- adaptive_r = 0 (every rank's experts all-gathered, ffn.py:83-89) and sharded experts
     (num_local_experts < 0, ffn.py:91-109) -- run on the SAME MFMA grouped GEMM, fed the gathered [E, H', M] tensors
     (forward(), below the gathers);
-  * only fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
+  * fp32 experts, opt-in (TUTEL_AMD_NATIVE_FP32=1): two launches of tutel_amd_expert_gemm_f32 -- the exact-f32 MFMA, whose output is a
+    k-ordered fmaf chain bit for bit (include/tutel_amd.h) -- with the same fusions: bias + activation in the epilogue, fc1's rows
+    gathered from the tokens, fc2 read in its checkpoint layout.  No autograd, no megablocks row counts, local experts only;
+  * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
 import os
@@ -27,6 +30,9 @@ from .. import net, ops
 _PREPACK = int(os.environ.get("TUTEL_AMD_PREPACK", "1")) != 0
 # training: forward + data gradients of the bf16 / fp16 ReLU FFN on the MFMA grouped GEMM (weight gradients stay on ATen); 0 disables
 _TRAIN_FUSED = int(os.environ.get("TUTEL_AMD_TRAIN_FUSED", "1")) != 0
+# opt-in: fp32 experts on the native fp32 grouped GEMM (csrc/expert_gemm_f32.hip) instead of ATen's batched matmul.  Off: an fp32
+# layer runs exactly as before
+_NATIVE_FP32 = int(os.environ.get("TUTEL_AMD_NATIVE_FP32", "0")) != 0
 
 
 def _FFN_FUSED_ON():
@@ -289,6 +295,53 @@ class FusedExpertsNetwork(torch.nn.Module):
                 and ops.gemm_supported(dt, w1.size(1), w1.size(2)) and ops.gemm_supported(dt, w2.size(2), w2.size(1))
                 and ops.gemm_supported(dt, w2.size(1), w2.size(2)) and ops.gemm_supported(dt, w1.size(2), w1.size(1)))
 
+    def f32_refusal(self, x, ctx, megablocks_size=None):
+        """why this forward does not take the native fp32 grouped GEMM (a string), or None when it does.  megablocks_size: the value
+        this forward will run with, where ctx does not hold it yet"""
+        if not _NATIVE_FP32:
+            return "TUTEL_AMD_NATIVE_FP32 is off"
+        if self.skip_expert:
+            return "SKIP_EXPERT is set"
+        if not x.is_cuda:
+            return "the input is not on the HIP device"
+        if torch.is_autocast_enabled():
+            return "autocast is on"
+        params = (self.batched_fc1_w, self.batched_fc2_w, self.batched_fc1_bias, self.batched_fc2_bias)
+        if x.dtype != torch.float32 or any(p is not None and p.dtype != torch.float32 for p in params):
+            return "the input and the experts' parameters are not all fp32"
+        if not self._no_autograd(x):
+            return "autograd is live (training stays on ATen)"
+        if getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0:
+            return "gathered-weight modes (sharded experts, adaptive_r = 0) are not covered"
+        if (getattr(ctx, "megablocks_size", 0) if megablocks_size is None else megablocks_size) != 0:
+            return "megablocks row counts are not covered"
+        if self.fused_activation() is None:
+            return "the activation is not one of the fused epilogues"
+        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
+        if not (ops.gemm_f32_supported(w1.size(1), w1.size(2)) and ops.gemm_f32_supported(w2.size(2), w2.size(1))):
+            return "the shape is not covered (M and H multiples of 32, H and M_out multiples of 4)"
+        return None
+
+    def can_fuse_f32(self, x, ctx):
+        """fp32 experts on the native fp32 grouped GEMM: the switch, fp32 everywhere, no autocast, no autograd, this rank's own local
+        experts, no megablocks row counts, a recognised activation, both products covered"""
+        return self.f32_refusal(x, ctx) is None
+
+    def forward_fused_f32(self, x, ctx, R=None, slot_map=None):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M_out]; slot_map given: x is the TOKEN array [T, M] and fc1 gathers its rows
+        (R = capacity).  Two launches: fc1 k-major with bias + activation, fc2 in its [H, M_out] layout with b2[:, :output_dim]."""
+        w1, b1, w2, b2 = (p.detach() if p is not None else None
+                          for p in (self.batched_fc1_w, self.batched_fc1_bias, self.batched_fc2_w, self.batched_fc2_bias))
+        if b2 is not None:
+            b2 = b2[:, :self.output_dim]
+        h = ops.expert_gemm_f32(x, w1, b1, True, act=self.fused_activation(), slot_map=slot_map, R=R)
+        y = ops.expert_gemm_f32(h, w2, b2, False) if h is not None else None
+        if y is None:   # can_fuse_f32 asked the library's own coverage query: a refusal here is a bug, never a quiet ATen forward
+            from .. import _lib
+            raise _lib.TutelAmdError("tutel_amd_expert_gemm_f32 refused a shape its own query admits: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
     def fused_params(self, dtype):
         """(w1, b1, w2, b2, w2_kmajor) of this rank's experts in the GEMM's compute dtype: the parameters themselves, or
         cached casts under autocast; fc2 as a k-major copy in eval mode."""
@@ -361,6 +414,17 @@ class FusedExpertsNetwork(torch.nn.Module):
             return x
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)
+
+        if _NATIVE_FP32:   # fp32 experts on the native grouped GEMM (opt-in); the reason it did not run is kept for the caller
+            why = self.f32_refusal(x, ctx)
+            if why is None and not (x.dim() == 3 and x.size(0) == self.batched_fc1_w.size(0) and x.size(2) == self.batched_fc1_w.size(2)):
+                why = "the input is not [E_loc, R, M]"
+            try:
+                ctx._native_fp32_ran = True if why is None else why
+            except AttributeError:
+                pass
+            if why is None:
+                return self.forward_fused_f32(x.contiguous(), ctx)
 
         if self.can_fuse_training(x, ctx):
             dt = self.compute_dtype(x)

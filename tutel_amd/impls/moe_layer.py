@@ -31,6 +31,7 @@ from .overlap import a2a_ffn_overlap_forward, a2a_ffn_overlap_fused
 from . import ep_native
 from . import packed_train
 from .. import ops
+from ..experts import ffn as _ffn
 from ..experts.ffn import FusedExpertsNetwork
 from ..experts.llama_ffn import LlamaFFNNetwork
 from ..gates.top import LinearTopKGate
@@ -246,6 +247,8 @@ class MOELayer(torch.nn.Module):
     #                    native pipeline is switched off)
     #   "generic"        the reference's op sequence on the HIP ops: training (autograd), custom / fp32 experts, CPU tensors,
     #                    sharded experts, adaptive_r = 0, 2DH with overlap
+    # fp32 experts under TUTEL_AMD_NATIVE_FP32 (experts/ffn.py::can_fuse_f32) take "fused_encode" or "generic" only: their GEMM is
+    # tutel_amd_expert_gemm_f32, called from FusedExpertsNetwork
     def _plan(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
               original_dtype, crit=None, allow_native=True):
         W = self.world_size
@@ -255,9 +258,16 @@ class MOELayer(torch.nn.Module):
         fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
                    and (x.dtype == logits.dtype or (logits.dtype == torch.float32 and x.dtype == original_dtype))
-                   and (swiglu_packed or self.experts.can_fuse(x, self)))
+                   and (swiglu_packed or self.experts.can_fuse(x, self) or self.experts.can_fuse_f32(x, self)))
         if not fusable:
             return "generic"
+        if x.dtype == torch.float32 and not swiglu_packed:
+            # fp32 experts on the native fp32 grouped GEMM (can_fuse_f32; opt-in): never the one-call pipelines -- they have no fp32 GEMM.
+            # Single rank, is_postscore: fc1 gathers from the tokens; everything else reaches FusedExpertsNetwork.forward through "generic"
+            if (stage == "after_routing" and W == 1 and self.is_postscore and isinstance(crit, RoutingPlan) and crit[4] > 0 and _FUSE_ENCODE
+                    and crit.slot_map is not None):
+                return "fused_encode"
+            return "routed" if stage == "before_routing" else "generic"
         native = (allow_native and ep_native.ENABLED and not _FORCE_OVERLAP and degree <= 32 and (degree == 1 or not self.use_2dh)
                   and (W == 1 or ep_native.group_ok(self.group)))
         if stage == "before_routing":
@@ -390,6 +400,7 @@ class MOELayer(torch.nn.Module):
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
+        self._native_fp32_ran = None       # TUTEL_AMD_NATIVE_FP32: True, or why this forward's experts stayed on ATen
         if self.skip_moe:
             out = input
             out.l_aux = None
@@ -418,6 +429,10 @@ class MOELayer(torch.nn.Module):
             megablocks_size = 0
         if adaptive_r is not None:
             self.adaptive_degree = adaptive_r
+        if _ffn._NATIVE_FP32 and isinstance(self.experts, FusedExpertsNetwork):
+            # why this forward's experts will not run on the native fp32 grouped GEMM, known before routing (None: admitted so far;
+            # whoever runs them -- the "fused_encode" route below, FusedExpertsNetwork.forward -- sets True, or a later reason)
+            self._native_fp32_ran = self.experts.f32_refusal(x, self, megablocks_size=megablocks_size)
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega
@@ -521,7 +536,11 @@ class MOELayer(torch.nn.Module):
         if plan == "fused_encode":
             # single rank, is_postscore: fast_encode is a pure row copy, so fc1 gathers its rows straight
             # from the tokens through the slot map -- the [E,C,M] bucket array is never materialised
-            y = self.experts.forward_fused(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
+            if x.dtype == torch.float32:   # only can_fuse_f32 sends fp32 experts here
+                y = self.experts.forward_fused_f32(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
+                self._native_fp32_ran = True
+            else:
+                y = self.experts.forward_fused(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
             self.protected_shape = y.shape
             return finish(fast_decode(y, crit, self.is_postscore), l_aux)
 

@@ -411,6 +411,53 @@ def expert_gemm_gather(x, smap, w, bias, w_kmajor, act, R, row_counts=None, row_
     return out
 
 
+def gemm_f32_supported(N, K):
+    """shapes the fp32 grouped GEMM (tutel_amd_expert_gemm_f32) takes: K % 32 == 0, N % 4 == 0 -- the library's own answer"""
+    return bool(_lib.lib().tutel_amd_expert_gemm_f32_supported(int(N), int(K)))
+
+
+def expert_gemm_f32(a, w, bias, w_kmajor, act="none", slot_map=None, R=None, a_layout=None, out=None, d_layout=None):
+    """fp32 experts on the exact-f32 MFMA: D[e,r,n] = act(chain + bias[e,n]), chain the k-ascending fmaf chain from 0.f over
+    A[e,r,:] and column n of op(W[e]) (the contract of include/tutel_amd.h: bit for bit replayable on a CPU).
+
+    a: [E_loc, R, K] contiguous, any buffer described by a_layout=(stride_e, stride_w, rows_per_w, lda) with R, or -- with
+    slot_map [E_loc * R] -- the token array [T, K] whose rows fc1 gathers (fast_encode fused; negative slots read the zero row).
+    w: [E_loc, N, K] (w_kmajor) or [E_loc, K, N], as stored; bias [E_loc, N] or None, its rows may be strided (b2[:, :output_dim]).
+    out / d_layout as in expert_gemm.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, w, bias, out, slot_map)
+    assert w.dim() == 3 and w.is_contiguous() and a.dtype == torch.float32 and w.dtype == torch.float32
+    E_loc, N, K = (w.shape if w_kmajor else (w.shape[0], w.shape[2], w.shape[1]))
+    T, z = 0, None
+    if slot_map is not None:
+        assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K and a_layout is None and R is not None
+        assert slot_map.dtype == torch.int32 and slot_map.numel() == E_loc * R
+        a = _a16(a)
+        T, z = a.shape[0], zero_row(K, torch.float32, a.device)
+        a_layout = (0, 0, 1, a.stride(0))
+    elif a_layout is None:
+        assert a.dim() == 3 and a.is_contiguous() and a.shape[0] == E_loc and a.shape[2] == K
+        a = _a16(a)
+        R = a.shape[1]
+        a_layout = (R * K, 0, max(R, 1), K)
+    assert R is not None
+    if out is None:
+        out = torch.empty([E_loc, R, N], dtype=torch.float32, device=a.device)
+        d_layout = (R * N, 0, max(R, 1), N)
+    assert d_layout is not None and out.dtype == torch.float32
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == torch.float32
+    rc = _lib.lib().tutel_amd_expert_gemm_f32(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        _ptr(w), int(bool(w_kmajor)), w.stride(0), w.stride(1),
+        _ptr(bias), (bias.stride(0) if bias is not None else 0),
+        _ptr(out), d_layout[0], d_layout[1], d_layout[2], d_layout[3],
+        E_loc, R, N, K, ACT_CODES[act], _ptr(slot_map), T, _ptr(z), _stream())
+    if rc == _lib.ENOTSUP:
+        return None
+    _lib.check(rc, "tutel_amd_expert_gemm_f32")
+    return out
+
+
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     """fc1 -> activation -> fc2 of every local expert in ONE persistent launch (tutel_amd_expert_ffn, csrc/expert_ffn.hip):
     x [E_loc, R, M] -- or the token array [T, M] with smap [E_loc * R] (fast_encode fused) -- w1 [E_loc, H, M], w2_kmajor
