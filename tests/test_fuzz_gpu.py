@@ -8,7 +8,9 @@ expert-parallel one):
   train     training steps: output and all gradients vs the fp32 layer, bar relative to upstream's ATen op sequence
   ext       cosine top-k gate over SwiGLU experts
 The kernels of the packed dropless layout have their own fuzzers, against CPU references of each operation: tests/test_packed_fuzz_gpu.py
-(layout, gemm, grad, decode, layer).
+(layout, gemm, grad, decode, layer).  The routing fuzzer's rows are at most 64 sixteen-byte vectors long; encode, decode in all four
+TUTEL_OPT_DECODE launch shapes and the any-k kernel, and the padded gate gradient are swept over row lengths (through every unrolled
+loop and the scalar tail), bucket orders and k up to 24 by tests/test_dispatch_fuzz_gpu.py (decode, encode, ggrad).
 The default run takes 120 / 120 / 30 / 30 / 40 cases, --runslow the full-length forms; `python tests/test_fuzz_gpu.py [cases] [seed] [what]`
 runs any length and writes gpurun_out/r6_<what>_fuzz_<seed>.json (round 6's records, incl. a soak with other seeds: profiles/README.md)."""
 import json

@@ -462,7 +462,8 @@ static void launch_decode_cfg(const void *buf, const int32_t *idx, const int32_t
 #undef DEC
 }
 
-// TUTEL_OPT_DECODE (A/B on hardware, tools/decode_probe.py): -1 automatic; bit 0 = two waves per token, bit 1 = non-temporal stores
+// TUTEL_OPT_DECODE (A/B on hardware: profiles/r03_routing_fused_and_decode_ab.txt; all four values against one reference:
+// tests/test_dispatch_fuzz_gpu.py): -1 automatic; bit 0 = two waves per token, bit 1 = non-temporal stores
 template <typename T>
 static void launch_decode(const void *buf, const int32_t *idx, const int32_t *loc, const void *gates,
                           int gate_dtype, int Tn, int M, int k, int capacity, int num_experts, int chunk_rows, int expert_slice,
