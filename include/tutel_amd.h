@@ -251,6 +251,42 @@ int tutel_amd_expert_gemm_f32(const void *A, int64_t a_stride_e, int64_t a_strid
                               int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
                               int act, const int32_t *slot_map, int T, const void *zero_row, tutel_stream_t stream);
 
+/* W8A16 (csrc/expert_gemm_w8.hip): the grouped GEMM of bf16 / fp16 experts whose weights are stored as OCP e4m3fn bytes with one fp32
+ * scale per (expert, output channel).  Activations, bias and output stay in `dtype` (TUTEL_BF16 or TUTEL_F16).
+ * Numeric contract (part of the interface):
+ *     acc[e, r, n] = sum_k A[e, r, k] * dq(Wq[e, n, k])      accumulated in fp32 by v_mfma_f32_32x32x16_{bf16,f16}; ONE accumulator per
+ *                                                            output: no split-K, no atomics
+ *     dq(c) is the EXACT value of the e4m3 code c in `dtype` (all 254 finite codes are bf16 and fp16 values); 0x7F and 0xFF are NaN
+ *     and propagate.  Neither the fp8 matrix instruction nor the MX block-scaled one is used: the activations are not quantised.
+ *     v = acc * scale[e, n]          one fp32 multiply with its own rounding, not contracted with what follows
+ *     v = v + float(bias[e, n])      one fp32 add (skipped when bias is NULL)
+ *     v = act(v)                     the 16-bit epilogue's formulas in fp32 (see tutel_amd_expert_gemm_f32 above)
+ *     D[e, r, n] = v rounded once to `dtype`.
+ * The weight image Wq (the kernel's own layout; tutel_amd/experts/w8.py::pack / unpack) -- expert e at Wq + e * w_stride_e BYTES, then
+ *     [N / 32 channel groups][K / 32 k groups][64 lanes][16 bytes]:
+ *     byte b of lane l of block (g, t) is the code of channel n = 32 g + (l & 31) at k = 32 t + 16 (b >> 3) + 8 (l >> 5) + (b & 7)
+ *   -- one 16-byte load per lane is 1 KB contiguous per wave and holds the lane's matrix-instruction operands of two K-steps; a
+ *   channel group's whole K extent is one contiguous run of 32 K bytes.  N and K are padded up to multiples of 32 with code 0x00
+ *   (the shapes this entry point covers need no padding: an expert's image is N * K bytes).
+ * scale: fp32 [E_loc, N] contiguous.  bias: `dtype`, row e at bias + e * bias_stride_e elements, or NULL.
+ * Rows of A and D: tutel_amd_expert_gemm_f32's addressing in its plain form, [E_loc, R, *] with element strides (a_rows_per_w,
+ * d_rows_per_w >= R, a_stride_w = d_stride_w = 0), or gathered: slot_map != NULL, A is the TOKEN array [T, lda] and row (e, r) is
+ * A[slot_map[e*R + r] % T], a negative slot reads zero_row (>= K zeros); a_stride_e / a_stride_w / a_rows_per_w are then ignored.
+ * Covered (tutel_amd_expert_gemm_w8_supported(dtype, N, K) == 1: a pure function, no HIP call): bf16 / fp16, K % 64 == 0,
+ * N % 32 == 0; lda and a_stride_e % 8 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K; any
+ * R >= 1 (tuned for R <= 128, where one workgroup sees all rows of an expert; more rows stream the weights once per 128), E_loc * R
+ * and the tile count E_loc * ceil(R / 128) * ceil(N / 128) below 2^31.  Ragged last tiles clamp their loads and mask their stores:
+ * nothing is read or written outside the operands.  NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange layouts
+ * (rows_per_w < R or a stride_w), peer stores.  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or
+ * R == 0 is a successful no-op.  A, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte aligned.  Every check precedes the
+ * first HIP call. */
+int tutel_amd_expert_gemm_w8_supported(int dtype, int N, int K);
+int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
+                             int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
+                             int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                             int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                             tutel_stream_t stream);
+
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert
  * -- what FusedExpertsNetwork.forward computes with two batched matmuls, two bias adds and the activation

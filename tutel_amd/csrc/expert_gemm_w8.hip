@@ -1,0 +1,306 @@
+// expert_gemm_w8.hip -- W8A16: the grouped GEMM of bf16 / fp16 experts whose weights are stored as OCP e4m3fn bytes with one fp32
+// scale per (expert, output channel).
+//
+//   D[e, r, n] = round_T( act( acc(e, r, n) * scale[e, n] + bias[e, n] ) )          acc = sum_k A[e, r, k] * dq(Wq[e, n, k]) in fp32
+//
+// dq widens an e4m3 code to A's dtype EXACTLY (every finite code is a bf16 and an fp16 value; 0x7F / 0xFF are NaN and propagate):
+// v_cvt_scalef32_pk_{bf16,f16}_fp8 with scale 1.0, two elements per instruction.  The product then runs on the 16-bit matrix
+// instruction v_mfma_f32_32x32x16_{bf16,f16} with ONE fp32 accumulator per output (no split-K, no atomics); the scale is ONE fp32
+// multiply per output in the epilogue, then one fp32 add of the bias, the activation (gemm_dev.h::activate) and one rounding
+// (the library builds with -ffp-contract=off; the multiply and the add are written as __fmul_rn / __fadd_rn).  The contract is
+// written into include/tutel_amd.h.
+//
+// The launch is a weight-streaming problem (<= 128 rows per expert: every weight byte is used once), so the shape of the kernel
+// follows the bytes:
+//   * the weight image is the kernel's own layout (include/tutel_amd.h, tutel_amd/experts/w8.py::pack): blocked by (32 channels,
+//     32 k, lane) so that ONE global_load_dwordx4 per lane fetches 1 KB contiguous per wave -- the MFMA fragments of two K-steps of
+//     16 for the lane's channel -- and a wave walks its 32 channels' whole K extent as one contiguous run of K * 32 bytes.
+//     Weight bytes go global -> VGPR -> convert -> MFMA operand and never touch LDS; a register ring keeps W8_DEPTH K-tiles
+//     (2 KB per wave each) in flight;
+//   * one 4-wave workgroup per (expert, 128 rows, 128 channels): wave w owns channels 32 w .. 32 w + 31 of the tile and all 128
+//     rows (4 accumulators of 32 x 32; 32-row groups past R are skipped);
+//   * token rows go through LDS, K-tiles of 64 in two stages of 16 KB, in the swizzled 128-byte-row panel of the other GEMMs
+//     (16-byte chunk c of row r at c ^ ((r >> 1) & 7)): 16-byte global loads into registers, issued two tiles ahead, stored after the
+//     previous tile's matrix instructions, one barrier per K-tile.  Rows: the plain [E_loc, R, K] form, or gathered from the tokens through the
+//     slot map (negative slot: the zero row);
+//   * weights are the A operand of the matrix instruction and token rows the B operand: a lane ends with ONE row and, per
+//     register group, 4 consecutive channels -- 8-byte stores, scale and bias as 4-vectors fetched once per lane in front of the epilogue;
+//   * R > 128 runs as several row tiles that each stream the weights again: correct, not the design point.
+//   * ragged tiles: rows past R and channel groups past N clamp their loads (to the last row / the last 32-channel group) and mask
+//     their stores; nothing is read or written outside the operands.
+#include "gemm_dev.h"  // Mma<T>, activate<ACT>
+
+#define W8_BM 128
+#define W8_BN 128
+#define W8_BK 64
+#define W8_THREADS 256
+#define W8_DEPTH 4       // K-tiles of weights in flight per wave (even: the token registers alternate with it); 8 measured the same
+#define W8_STAGE (W8_BM * W8_BK * 2)
+
+struct W8Args {
+  const unsigned char *A; long long a_stride_e; int lda;     // elements
+  const unsigned char *Wq; long long w_stride_e;             // bytes
+  const float *scale;
+  const uint16_t *bias; long long bias_stride_e;             // elements
+  uint16_t *D; long long d_stride_e; int ldd;                // elements
+  int R, N, K, ntm, ntn;
+  const int32_t *slot_map; int T; const unsigned char *zero_row;
+};
+
+template <typename T> struct W8Cvt;
+template <> struct W8Cvt<bf16_t> {  // bytes 0, 1 (hi: 2, 3) of `u` -> two bf16 in one word
+  template <bool HI> __device__ static __forceinline__ uint32_t run(uint32_t u) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u, 1.0f, HI));
+  }
+};
+template <> struct W8Cvt<f16_t> {
+  template <bool HI> __device__ static __forceinline__ uint32_t run(uint32_t u) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(u, 1.0f, HI));
+  }
+};
+
+// 8 codes (two words) -> the 8-element MFMA operand
+template <typename T> __device__ __forceinline__ u32x4 w8_widen(uint32_t lo, uint32_t hi) {
+  u32x4 r;
+  r[0] = W8Cvt<T>::template run<false>(lo);
+  r[1] = W8Cvt<T>::template run<true>(lo);
+  r[2] = W8Cvt<T>::template run<false>(hi);
+  r[3] = W8Cvt<T>::template run<true>(hi);
+  return r;
+}
+
+// 16 weight bytes per lane through the channel group's descriptor, streamed (each byte is read once by one workgroup per row tile)
+__device__ __forceinline__ u32x4 w8_wload(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 2));
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8Args p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, kg = lane >> 5;
+  // the channel tiles of one (expert, row tile) are consecutive work items: on ONE XCD, so that its L2 fetches the tile's token rows
+  // once (placed round-robin, the eight XCDs each fetched them: 1.6 x the algorithmic bytes, measured with FETCH_SIZE)
+  const int b = xcd_work_item((int)gridDim.x);
+  const int tn = b % p.ntn, tm = (b / p.ntn) % p.ntm, e = b / (p.ntn * p.ntm);
+  const int m0 = tm * W8_BM, n0 = tn * W8_BN;
+  const int nk = p.K / W8_BK;
+  const int NT = p.N >> 5, KT32 = p.K >> 5;
+  const int nmi = min(4, (p.R - m0 + 31) >> 5);  // live 32-row groups of this tile
+
+  // ---- token rows: thread `tid` moves chunk (tid & 7) of rows 32 i + (tid >> 3), i < 4, of every K-tile -------------------------------
+  const unsigned char *rowp[4];
+  int ldst[4];
+  {
+    int slot[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) slot[i] = 0;
+    if (p.slot_map != nullptr) {  // the slots first, so that their loads are in flight together
+#pragma unroll
+      for (int i = 0; i < 4; ++i) slot[i] = p.slot_map[(long long)e * p.R + min(m0 + 32 * i + (tid >> 3), p.R - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 32 * i + (tid >> 3), c = tid & 7;
+      const int gr = min(m0 + r, p.R - 1);
+      const unsigned char *row;
+      if (p.slot_map != nullptr) row = slot[i] < 0 ? p.zero_row : p.A + (long long)(slot[i] % p.T) * p.lda * 2;
+      else row = p.A + ((long long)e * p.a_stride_e + (long long)gr * p.lda) * 2;
+      rowp[i] = row + c * 16;
+      ldst[i] = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
+    }
+  }
+
+  // ---- weights: the wave's 32-channel group, clamped to the last one (a clamped wave computes and stores nothing new) ---------------------
+  const int nt = min((n0 >> 5) + wn, NT - 1);
+  const bool wave_live = (n0 >> 5) + wn < NT;
+  // The group's run of K * 32 bytes is read through a buffer descriptor of exactly that size: every load of the K loop is
+  // UNCONDITIONAL (a load under a branch makes the compiler wait for all loads in flight where the branches join), and the refills
+  // past the last K-tile are out of the descriptor's range -- they fetch nothing and return zeros that are never used.
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned char *>(p.Wq + (long long)e * p.w_stride_e + (long long)nt * KT32 * 1024), 0, KT32 * 1024, 0x00020000);
+  const int wl = lane * 16;
+  u32x4 wreg[W8_DEPTH][2];
+#pragma unroll
+  for (int d = 0; d < W8_DEPTH; ++d) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) wreg[d][h] = w8_wload(rs_w, wl, d * 2048 + h * 1024);
+  }
+
+  f32x16 acc[4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
+
+  // Token rows run TWO tiles ahead in registers (treg[j]: a tile of parity j): the memory counter retires loads in order, so waiting
+  // for a token tile asked for only one step ago would also wait for every weight refill issued before it -- the ring would be one
+  // tile deep whatever W8_DEPTH says.  Tile 0 goes to LDS here, tile 1 waits in treg[1]
+  u32x4 treg[2][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) treg[0][i] = *reinterpret_cast<const u32x4 *>(rowp[i]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) treg[1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + (long long)min(1, nk - 1) * (W8_BK * 2));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4 *>(smem + ldst[i]) = treg[0][i];
+  __syncthreads();
+
+  const int sw = (l31 >> 1) & 7;
+  const int frag = l31 * 128;  // + mi * 32 rows
+
+  for (int kt0 = 0; kt0 < nk; kt0 += W8_DEPTH) {
+#pragma unroll
+    for (int d = 0; d < W8_DEPTH; ++d) {
+      const int kt = kt0 + d;
+      if (kt >= nk) break;  // block-uniform
+      // token tile kt + 2 (behind the last tile: that tile again -- it is stored into the free stage and never read)
+      const long long tnext = (long long)min(kt + 2, nk - 1) * (W8_BK * 2);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) treg[d & 1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + tnext);
+      // the K-tile's four operands of 8 k: word pair s of load h holds k = 64 kt + 32 h + 16 s + 8 kg .. + 7
+      u32x4 wa[4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) wa[2 * h + s] = w8_widen<T>(wreg[d][h][2 * s], wreg[d][h][2 * s + 1]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) wreg[d][h] = w8_wload(rs_w, wl, (kt + W8_DEPTH) * 2048 + h * 1024);
+      // operand q multiplies token chunk 2 q + kg of every row; the fragments of operand q + 1 are asked for before the matrix
+      // instructions of operand q (two sets of four in registers, not all sixteen)
+      const unsigned char *st = smem + (kt & 1) * W8_STAGE + frag;
+      u32x4 tb[2][4];
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) tb[0][mi] = *reinterpret_cast<const u32x4 *>(st + mi * (32 * 128) + ((kg ^ sw) << 4));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q < 3) {
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+            tb[(q + 1) & 1][mi] = *reinterpret_cast<const u32x4 *>(st + mi * (32 * 128) + (((2 * (q + 1) + kg) ^ sw) << 4));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+          if (mi < nmi) acc[mi] = Mma<T>::run(wa[q], tb[q & 1][mi], acc[mi]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      {  // the other stage is free since the last barrier (behind the last tile nobody reads what is stored)
+        unsigned char *nx = smem + ((kt + 1) & 1) * W8_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4 *>(nx + ldst[i]) = treg[(d + 1) & 1][i];
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue: lane = row m0 + 32 mi + l31; register 4 rg + r of accumulator mi = channel 32 nt + 8 rg + 4 kg + r ---------------------
+  if (!wave_live) return;
+  // scale and bias of the lane's channels 32 nt + 8 rg + 4 kg .. + 3, all fetched before the first is used
+  float4 sc[4];
+  uint2 bi[4];
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) {
+    const int n = nt * 32 + rg * 8 + kg * 4;
+    sc[rg] = *reinterpret_cast<const float4 *>(p.scale + (long long)e * p.N + n);
+    bi[rg] = p.bias != nullptr ? *reinterpret_cast<const uint2 *>(p.bias + (long long)e * p.bias_stride_e + n) : make_uint2(0u, 0u);
+  }
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+    const int m = m0 + mi * 32 + l31;
+    if (m >= p.R) continue;
+    uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 32 + kg * 4;
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+      const float s4[4] = {sc[rg].x, sc[rg].y, sc[rg].z, sc[rg].w};
+      const uint16_t b4[4] = {(uint16_t)(bi[rg].x & 0xffff), (uint16_t)(bi[rg].x >> 16), (uint16_t)(bi[rg].y & 0xffff), (uint16_t)(bi[rg].y >> 16)};
+      uint16_t o[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = __fmul_rn(acc[mi][rg * 4 + r], s4[r]);
+        if (p.bias != nullptr) {
+          T tb;
+          __builtin_memcpy(&tb, &b4[r], 2);
+          v = __fadd_rn(v, Elem<T>::to_f32(tb));
+        }
+        v = activate<ACT>(v);
+        asm("" : "+v"(v));  // the fp32 value exists before it is rounded (no fused multiply-and-round for fp16)
+        const T tv = Elem<T>::from_f32(v);
+        __builtin_memcpy(&o[r], &tv, 2);
+      }
+      uint2 ov;
+      ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
+      ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
+      *reinterpret_cast<uint2 *>(drow + rg * 8) = ov;
+    }
+  }
+}
+
+static bool w8_dtype_ok(int dtype) { return dtype == TUTEL_BF16 || dtype == TUTEL_F16; }
+static bool w8_shape_ok(int N, int K) { return N >= 32 && N % 32 == 0 && K >= W8_BK && K % W8_BK == 0; }
+
+extern "C" int tutel_amd_expert_gemm_w8_supported(int dtype, int N, int K) { return w8_dtype_ok(dtype) && w8_shape_ok(N, K) ? 1 : 0; }
+
+static int w8_notsup(const char *why) {
+  tutel_set_error("tutel_amd_expert_gemm_w8: not covered: %s", why);
+  return TUTEL_AMD_ENOTSUP;
+}
+
+template <typename T, int ACT> static int w8_launch(const W8Args &a, unsigned grid, hipStream_t st) {
+  hipLaunchKernelGGL((expert_gemm_w8_kernel<T, ACT>), dim3(grid), dim3(W8_THREADS), 0, st, a);
+  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_w8");
+  return 0;
+}
+
+template <typename T> static int w8_launch_act(const W8Args &a, int act, unsigned grid, hipStream_t st) {
+  switch (act) {
+    case TUTEL_ACT_NONE: return w8_launch<T, TUTEL_ACT_NONE>(a, grid, st);
+    case TUTEL_ACT_RELU: return w8_launch<T, TUTEL_ACT_RELU>(a, grid, st);
+    case TUTEL_ACT_GELU: return w8_launch<T, TUTEL_ACT_GELU>(a, grid, st);
+    default: return w8_launch<T, TUTEL_ACT_SILU>(a, grid, st);
+  }
+}
+
+extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
+                                        int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
+                                        int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                                        int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T,
+                                        const void *zero_row, tutel_stream_t stream) {
+  // every check stands in front of the first HIP call
+  TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_w8: bad sizes E_loc=%d R=%d N=%d K=%d", E_loc, R, N, K);
+  if (!w8_dtype_ok(dtype)) return w8_notsup("the activations must be bf16 or fp16");
+  if (K % W8_BK != 0) return w8_notsup("K must be a multiple of 64");
+  if (N % 32 != 0) return w8_notsup("N must be a multiple of 32");
+  if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
+    return w8_notsup("the activation must be none, relu, gelu or silu");
+  if (row_counts != nullptr) return w8_notsup("row_counts (megablocks) are not covered");
+  if ((slot_map == nullptr && (a_rows_per_w < R || a_stride_w != 0)) || d_rows_per_w < R || d_stride_w != 0)
+    return w8_notsup("the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
+  if (lda % 8 != 0 || ldd % 4 != 0 || a_stride_e % 8 != 0 || d_stride_e % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0)
+    return w8_notsup("rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
+  if (w_stride_e < (int64_t)N * K) return w8_notsup("w_stride_e is smaller than one expert's image (N * K bytes)");
+  const long long ntm = (R + W8_BM - 1) / W8_BM, ntn = (N + W8_BN - 1) / W8_BN;
+  if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL)
+    return w8_notsup("E_loc * R and the tile count must stay below 2^31");
+  if (E_loc == 0 || R == 0) return 0;
+  TUTEL_REQUIRE(A && Wq && scale && D, "tutel_amd_expert_gemm_w8: null pointer");
+  TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)D % 8) == 0 &&
+                    ((uintptr_t)bias % 8) == 0,
+                "tutel_amd_expert_gemm_w8: A, Wq and scale must be 16-byte aligned, D and bias 8-byte aligned");
+  if (slot_map != nullptr)
+    TUTEL_REQUIRE(T >= 1 && zero_row != nullptr && ((uintptr_t)zero_row % 16) == 0,
+                  "tutel_amd_expert_gemm_w8: a slot map needs T >= 1 and a 16-byte aligned zero row");
+
+  W8Args a;
+  a.A = (const unsigned char *)A; a.a_stride_e = a_stride_e; a.lda = lda;
+  a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
+  a.scale = scale;
+  a.bias = (const uint16_t *)bias; a.bias_stride_e = bias_stride_e;
+  a.D = (uint16_t *)D; a.d_stride_e = d_stride_e; a.ldd = ldd;
+  a.R = R; a.N = N; a.K = K; a.ntm = (int)ntm; a.ntn = (int)ntn;
+  a.slot_map = slot_map; a.T = T; a.zero_row = (const unsigned char *)zero_row;
+  hipStream_t st = (hipStream_t)stream;
+  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  const unsigned grid = (unsigned)((long long)E_loc * ntm * ntn);
+  return dtype == TUTEL_BF16 ? w8_launch_act<bf16_t>(a, act, grid, st) : w8_launch_act<f16_t>(a, act, grid, st);
+}

@@ -16,6 +16,9 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
   * fp32 experts, opt-in (TUTEL_AMD_NATIVE_FP32=1): two launches of tutel_amd_expert_gemm_f32 -- the exact-f32 MFMA, whose output is a
     k-ordered fmaf chain bit for bit (include/tutel_amd.h) -- with the same fusions: bias + activation in the epilogue, fc1's rows
     gathered from the tokens, fc2 read in its checkpoint layout.  No autograd, no megablocks row counts, local experts only;
+  * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): bf16 / fp16 experts in inference read e4m3 codes
+    with one fp32 scale per (expert, output channel) instead of the 16-bit weights (W8A16: activations are not quantised) -- two
+    launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py);
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
@@ -25,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import net, ops
+from . import w8
 
 # eval-mode weight pre-layout: keep a [E, N, K] (k-major) copy of weights stored [E, K, N]; 0 disables
 _PREPACK = int(os.environ.get("TUTEL_AMD_PREPACK", "1")) != 0
@@ -33,6 +37,9 @@ _TRAIN_FUSED = int(os.environ.get("TUTEL_AMD_TRAIN_FUSED", "1")) != 0
 # opt-in: fp32 experts on the native fp32 grouped GEMM (csrc/expert_gemm_f32.hip) instead of ATen's batched matmul.  Off: an fp32
 # layer runs exactly as before
 _NATIVE_FP32 = int(os.environ.get("TUTEL_AMD_NATIVE_FP32", "0")) != 0
+# opt-in: bf16 / fp16 experts in inference stream their weights as FP8 (e4m3) codes (csrc/expert_gemm_w8.hip); the default of every
+# module's `fp8_weights` switch.  Off: nothing changes
+_FP8_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP8_WEIGHTS", "0")) != 0
 
 
 def _FFN_FUSED_ON():
@@ -93,14 +100,32 @@ class KMajorCache:
     def __init__(self):
         self._store = {}
 
-    def get(self, name, w, transpose=True, dtype=None):
-        """cached derived copy of parameter `w`: transposed to k-major ([E, K, N] -> [E, N, K]) and / or cast to `dtype`
-        (autocast: fp32 master weights, low-precision compute copies)"""
+    @staticmethod
+    def _key(w, *what):
         try:
             version = w._version
         except RuntimeError:  # inference tensors (module built under torch.inference_mode()) carry no version counter
             version = -1
-        key = (w.data_ptr(), version, w.dtype, w.device, tuple(w.shape), bool(transpose), dtype)
+        return (w.data_ptr(), version, w.dtype, w.device, tuple(w.shape)) + what
+
+    def derived(self, name, w, what, make):
+        """cached `make(w.detach())` -- any derived copy of parameter `w` (the FP8 image and scales of experts/w8.py), rebuilt under
+        the same rule as the k-major copies; `what` names the derivation in the key"""
+        key = self._key(w, what)
+        hit = self._store.get(name)
+        if hit is None or hit[0] != key:
+            hit = (key, make(w.detach()))
+            self._store[name] = hit
+        return hit[1]
+
+    def holds(self, name, w, what):
+        hit = self._store.get(name)
+        return hit is not None and hit[0] == self._key(w, what)
+
+    def get(self, name, w, transpose=True, dtype=None):
+        """cached derived copy of parameter `w`: transposed to k-major ([E, K, N] -> [E, N, K]) and / or cast to `dtype`
+        (autocast: fp32 master weights, low-precision compute copies)"""
+        key = self._key(w, bool(transpose), dtype)
         hit = self._store.get(name)
         if hit is None or hit[0] != key:
             t = w.detach()
@@ -212,6 +237,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         self.activation_fn = activation_fn
         self._act_cache = {}
         self._kmajor = KMajorCache()
+        # FP8 (e4m3) weights in inference, W8A16 (w8_refusal / forward_fused_w8); the 16-bit parameters stay as they are
+        self.fp8_weights = _FP8_WEIGHTS
 
         E, H = num_experts_per_device, self.hidden_size
         self.batched_fc1_w = torch.nn.Parameter(torch.empty(E, H, model_dim))
@@ -342,6 +369,61 @@ class FusedExpertsNetwork(torch.nn.Module):
                                      _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
         return y
 
+    def w8_refusal(self, x, ctx, megablocks_size=None):
+        """why this forward does not read FP8 weights (a string), or None when it does.  megablocks_size: the value this forward will
+        run with, where ctx does not hold it yet"""
+        if not self.fp8_weights:
+            return "fp8_weights is off (TUTEL_AMD_FP8_WEIGHTS)"
+        if self.skip_expert:
+            return "SKIP_EXPERT is set"
+        if not x.is_cuda:
+            return "the input is not on the HIP device"
+        if not self._no_autograd(x):
+            return "autograd is live (FP8 weights are inference only)"
+        if self.training:
+            return "the module is in training mode (FP8 weights are inference only)"
+        if torch.is_autocast_enabled():
+            return "autocast is on"
+        params = (self.batched_fc1_w, self.batched_fc2_w, self.batched_fc1_bias, self.batched_fc2_bias)
+        if x.dtype not in (torch.bfloat16, torch.float16) or any(p is not None and p.dtype != x.dtype for p in params):
+            return "the input is not bf16 / fp16 in the experts' own dtype"
+        if getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0:
+            return "gathered-weight modes (sharded experts, adaptive_r = 0) are not covered"
+        if (getattr(ctx, "megablocks_size", 0) if megablocks_size is None else megablocks_size) != 0:
+            return "megablocks row counts are not covered"
+        if self.fused_activation() is None:
+            return "the activation is not one of the fused epilogues"
+        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
+        if not (ops.gemm_w8_supported(x.dtype, w1.size(1), w1.size(2)) and ops.gemm_w8_supported(x.dtype, w2.size(2), w2.size(1))):
+            return "the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)"
+        if torch.cuda.is_current_stream_capturing() and not (self._kmajor.holds("fc1.w8", w1, "w8") and self._kmajor.holds("fc2.w8", w2, "w8")):
+            # quantising here would allocate the images in the graph's pool and redo the work at every replay
+            return "the quantised weights are not cached yet: run one eager forward before capturing a graph"
+        return None
+
+    def w8_params(self):
+        """((image1, scale1), (image2, scale2)): the FP8 images and scales of fc1 (read as stored, k-major) and fc2 (from its
+        [E, H, M_out] storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy"""
+        p1 = self._kmajor.derived("fc1.w8", self.batched_fc1_w, "w8", lambda w: w8.prepare(w, True))
+        p2 = self._kmajor.derived("fc2.w8", self.batched_fc2_w, "w8", lambda w: w8.prepare(w, False))
+        return p1, p2
+
+    def forward_fused_w8(self, x, ctx, R=None, slot_map=None):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M_out]; slot_map given: x is the TOKEN array [T, M] and fc1 gathers its rows
+        (R = capacity).  Two launches of tutel_amd_expert_gemm_w8."""
+        (i1, s1), (i2, s2) = self.w8_params()
+        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
+        b1, b2 = (p.detach() if p is not None else None for p in (self.batched_fc1_bias, self.batched_fc2_bias))
+        if b2 is not None:
+            b2 = b2[:, :self.output_dim]
+        h = ops.expert_gemm_w8(x, i1, s1, b1, w1.size(1), w1.size(2), act=self.fused_activation(), slot_map=slot_map, R=R)
+        y = ops.expert_gemm_w8(h, i2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
+        if y is None:   # w8_refusal asked the library's own coverage query: a refusal here is a bug, never a quiet 16-bit forward
+            from .. import _lib
+            raise _lib.TutelAmdError("tutel_amd_expert_gemm_w8 refused a shape its own query admits: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
     def fused_params(self, dtype):
         """(w1, b1, w2, b2, w2_kmajor) of this rank's experts in the GEMM's compute dtype: the parameters themselves, or
         cached casts under autocast; fc2 as a k-major copy in eval mode."""
@@ -412,6 +494,17 @@ class FusedExpertsNetwork(torch.nn.Module):
     def forward(self, x, ctx):
         if self.skip_expert:
             return x
+        if self.fp8_weights:   # FP8 weights (opt-in); the reason they were not read is kept for the caller
+            why = self.w8_refusal(x, ctx)
+            if why is None and not (x.dim() == 3 and x.size(0) == self.batched_fc1_w.size(0) and x.size(2) == self.batched_fc1_w.size(2)):
+                why = "the input is not [E_loc, R, M]"
+            try:
+                ctx._fp8_weights_ran = True if why is None else why
+            except AttributeError:
+                pass
+            if why is None:
+                return self.forward_fused_w8(x.contiguous(), ctx)
+
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)
 

@@ -1,0 +1,77 @@
+"""FP8 (OCP e4m3fn) expert weights for the W8A16 grouped GEMM (csrc/expert_gemm_w8.hip): the quantiser and the weight image.
+
+Cold path, plain torch, runs on CPU and GPU.  The kernel multiplies the 16-bit activations with the EXACT value of every e4m3 code
+(widened to bf16 / fp16) and applies the per-channel scale once per output in fp32 (the contract of include/tutel_amd.h), so what
+is written here -- which code and which scale a weight gets -- is the whole of the quantisation's numerics.
+
+    scale[e, n] = fp32(amax_k |w[e, n, k]|) / 448.0f           (an all-zero channel: 1)
+    q[e, n, k]  = e4m3_rne(clamp(fp32(w[e, n, k]) / scale[e, n], -448, 448))
+
+The clamp is needed: the division can round a quotient a little above 448, and torch's cast turns anything above 464 into the NaN
+code.  Everything is elementwise or a max-reduction in fp32: deterministic.
+
+The image is the kernel's own layout (include/tutel_amd.h): per expert [N / 32][K / 32][64 lanes][16 bytes], byte b of lane l of
+block (g, t) = the code of channel 32 g + (l & 31) at k = 32 t + 16 (b >> 3) + 8 (l >> 5) + (b & 7); N and K padded up to multiples of
+32 with code 0x00.  pack / unpack are pure index operations.
+"""
+import torch
+
+E4M3_MAX = 448.0
+TILE_N = 32
+TILE_K = 32
+
+
+def quantize_e4m3(w, w_kmajor):
+    """w [E, N, K] (w_kmajor) or [E, K, N], 16-bit or fp32 -> (q_nk [E, N, K] float8_e4m3fn, scale [E, N] fp32)"""
+    assert w.dim() == 3 and w.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    w = w.detach()
+    if not w_kmajor:
+        w = w.transpose(1, 2)
+    wf = w.float().contiguous()
+    amax = wf.abs().amax(dim=2)
+    if not bool(torch.isfinite(amax).all()):   # amax is NaN / inf exactly when its channel holds a non-finite weight
+        bad = (~torch.isfinite(amax)).nonzero()[0].tolist()
+        raise ValueError(f"quantize_e4m3: channel (expert {bad[0]}, output {bad[1]}) holds a non-finite weight")
+    # tensor / tensor: a true fp32 division on every device (a Python-scalar divisor is turned into a multiplication by its rounded
+    # reciprocal on the GPU, which moves some scales by an ulp and with them the codes that sit on a rounding tie)
+    scale = amax / torch.full_like(amax, E4M3_MAX)
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    q = (wf / scale.unsqueeze(2)).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def dequantize(q_nk, scale, dtype=torch.float32):
+    """the weights the kernel multiplies with, q * scale, as [E, N, K] in `dtype` (exact in fp32 up to the one product's rounding)"""
+    return (q_nk.float() * scale.unsqueeze(2)).to(dtype)
+
+
+def padded(n, tile):
+    return (n + tile - 1) // tile * tile
+
+
+def pack(q_nk):
+    """q_nk [E, N, K] float8_e4m3fn -> the kernel's image, uint8 [E, Np / 32, Kp / 32, 64, 16] contiguous (Np, Kp: N, K padded to 32)"""
+    assert q_nk.dim() == 3 and q_nk.dtype == torch.float8_e4m3fn
+    E, N, K = q_nk.shape
+    Np, Kp = padded(N, TILE_N), padded(K, TILE_K)
+    b = q_nk.contiguous().view(torch.uint8)
+    if (Np, Kp) != (N, K):
+        b = torch.nn.functional.pad(b, (0, Kp - K, 0, Np - N), value=0)
+    # [E, g, l31, t, s, kg, j] -> [E, g, t, kg, l31, s, j]: lane = 32 kg + l31, byte = 8 s + j
+    b = b.view(E, Np // 32, 32, Kp // 32, 2, 2, 8).permute(0, 1, 3, 5, 2, 4, 6)
+    return b.contiguous().view(E, Np // 32, Kp // 32, 64, 16)
+
+
+def unpack(image, N, K):
+    """the inverse of pack: image -> q_nk [E, N, K] float8_e4m3fn (the pad bytes dropped)"""
+    E = image.size(0)
+    Np, Kp = padded(N, TILE_N), padded(K, TILE_K)
+    assert image.dtype == torch.uint8 and image.numel() == E * Np * Kp
+    b = image.view(E, Np // 32, Kp // 32, 2, 32, 2, 8).permute(0, 1, 4, 2, 5, 3, 6).contiguous().view(E, Np, Kp)
+    return b[:, :N, :K].contiguous().view(torch.float8_e4m3fn)
+
+
+def prepare(w, w_kmajor):
+    """quantise and lay out one parameter: (image, scale) as the kernel reads them"""
+    q, scale = quantize_e4m3(w, w_kmajor)
+    return pack(q), scale.contiguous()

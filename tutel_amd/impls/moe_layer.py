@@ -248,7 +248,8 @@ class MOELayer(torch.nn.Module):
     #   "generic"        the reference's op sequence on the HIP ops: training (autograd), custom / fp32 experts, CPU tensors,
     #                    sharded experts, adaptive_r = 0, 2DH with overlap
     # fp32 experts under TUTEL_AMD_NATIVE_FP32 (experts/ffn.py::can_fuse_f32) take "fused_encode" or "generic" only: their GEMM is
-    # tutel_amd_expert_gemm_f32, called from FusedExpertsNetwork
+    # tutel_amd_expert_gemm_f32, called from FusedExpertsNetwork; 16-bit experts with FP8 weights switched on (experts.fp8_weights,
+    # experts/ffn.py::w8_refusal) are routed the same way: their GEMM is tutel_amd_expert_gemm_w8
     def _plan(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
               original_dtype, crit=None, allow_native=True):
         W = self.world_size
@@ -261,8 +262,10 @@ class MOELayer(torch.nn.Module):
                    and (swiglu_packed or self.experts.can_fuse(x, self) or self.experts.can_fuse_f32(x, self)))
         if not fusable:
             return "generic"
-        if x.dtype == torch.float32 and not swiglu_packed:
-            # fp32 experts on the native fp32 grouped GEMM (can_fuse_f32; opt-in): never the one-call pipelines -- they have no fp32 GEMM.
+        w8 = (not swiglu_packed and self.experts.fp8_weights and self.experts.w8_refusal(x, self, megablocks_size=megablocks_size) is None)
+        if (x.dtype == torch.float32 or w8) and not swiglu_packed:
+            # fp32 experts on the native fp32 grouped GEMM (can_fuse_f32; opt-in), 16-bit experts on FP8 weights (w8_refusal; opt-in): never
+            # the one-call pipelines -- they have neither GEMM.
             # Single rank, is_postscore: fc1 gathers from the tokens; everything else reaches FusedExpertsNetwork.forward through "generic"
             if (stage == "after_routing" and W == 1 and self.is_postscore and isinstance(crit, RoutingPlan) and crit[4] > 0 and _FUSE_ENCODE
                     and crit.slot_map is not None):
@@ -401,6 +404,7 @@ class MOELayer(torch.nn.Module):
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
         self._native_fp32_ran = None       # TUTEL_AMD_NATIVE_FP32: True, or why this forward's experts stayed on ATen
+        self._fp8_weights_ran = None       # experts.fp8_weights (TUTEL_AMD_FP8_WEIGHTS): True, or why this forward's experts read 16-bit weights
         if self.skip_moe:
             out = input
             out.l_aux = None
@@ -433,6 +437,10 @@ class MOELayer(torch.nn.Module):
             # why this forward's experts will not run on the native fp32 grouped GEMM, known before routing (None: admitted so far;
             # whoever runs them -- the "fused_encode" route below, FusedExpertsNetwork.forward -- sets True, or a later reason)
             self._native_fp32_ran = self.experts.f32_refusal(x, self, megablocks_size=megablocks_size)
+
+        if isinstance(self.experts, FusedExpertsNetwork) and self.experts.fp8_weights:
+            # the same for FP8 weights: None = admitted so far; the route that runs the experts sets True, or a later reason
+            self._fp8_weights_ran = self.experts.w8_refusal(x, self, megablocks_size=megablocks_size)
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega
@@ -539,6 +547,9 @@ class MOELayer(torch.nn.Module):
             if x.dtype == torch.float32:   # only can_fuse_f32 sends fp32 experts here
                 y = self.experts.forward_fused_f32(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
                 self._native_fp32_ran = True
+            elif self.experts.fp8_weights and self.experts.w8_refusal(x, self) is None:
+                y = self.experts.forward_fused_w8(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
+                self._fp8_weights_ran = True
             else:
                 y = self.experts.forward_fused(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
             self.protected_shape = y.shape

@@ -458,6 +458,54 @@ def expert_gemm_f32(a, w, bias, w_kmajor, act="none", slot_map=None, R=None, a_l
     return out
 
 
+def gemm_w8_supported(dtype, N, K):
+    """shapes the W8A16 grouped GEMM (tutel_amd_expert_gemm_w8) takes: bf16 / fp16 activations, K % 64 == 0, N % 32 == 0 -- the
+    library's own answer"""
+    if dtype not in _DT:
+        return False
+    return bool(_lib.lib().tutel_amd_expert_gemm_w8_supported(_DT[dtype], int(N), int(K)))
+
+
+def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=None, out=None, row_counts=None):
+    """W8A16: D[e,r,n] = act(acc * scale[e,n] + bias[e,n]) rounded once to a.dtype, acc the fp32 sum over k of a[e,r,k] times the exact
+    value of the e4m3 code of weight (e, n, k) (the contract of include/tutel_amd.h).
+
+    a: [E_loc, R, K] contiguous bf16 / fp16, or -- with slot_map [E_loc * R] -- the token array [T, K] whose rows fc1 gathers (negative
+    slots read the zero row).  image: experts/w8.py::pack's uint8 image of the [E_loc, N, K] codes; scale [E_loc, N] fp32; bias [E_loc, N]
+    in a.dtype or None, its rows may be strided.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, image, scale, bias, out, slot_map, row_counts)
+    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
+    E_loc = image.shape[0]
+    assert scale.shape == (E_loc, N) and image.numel() % max(E_loc, 1) == 0
+    T, z = 0, None
+    if slot_map is not None:
+        assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K and R is not None
+        assert slot_map.dtype == torch.int32 and slot_map.numel() == E_loc * R
+        a = _a16(a)
+        T, z = a.shape[0], zero_row(K, a.dtype, a.device)
+        a_layout = (0, 0, 1, a.stride(0))
+    else:
+        assert a.dim() == 3 and a.is_contiguous() and a.shape[0] == E_loc and a.shape[2] == K
+        a = _a16(a)
+        R = a.shape[1]
+        a_layout = (R * K, 0, max(R, 1), K)
+    if out is None:
+        out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
+    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
+    rc = _lib.lib().tutel_amd_expert_gemm_w8(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        _ptr(image), image.numel() // max(E_loc, 1), _ptr(scale),
+        _ptr(bias), (bias.stride(0) if bias is not None else 0),
+        _ptr(out), R * N, 0, max(R, 1), N,
+        E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    if rc == _lib.ENOTSUP:
+        return None
+    _lib.check(rc, "tutel_amd_expert_gemm_w8")
+    return out
+
+
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     """fc1 -> activation -> fc2 of every local expert in ONE persistent launch (tutel_amd_expert_ffn, csrc/expert_ffn.hip):
     x [E_loc, R, M] -- or the token array [T, M] with smap [E_loc * R] (fast_encode fused) -- w1 [E_loc, H, M], w2_kmajor
