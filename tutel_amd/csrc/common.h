@@ -12,6 +12,11 @@
 // ---- error reporting ---------------------------------------------------------------------
 void tutel_set_error(const char *fmt, ...);
 int tutel_get_option(int key);  // TUTEL_OPT_*: -1 automatic, 0 / 1 forced (api.hip)
+// a refusal that names its reason: tutel_amd_last_error reads "<entry>: not covered: <why>", the caller gets TUTEL_AMD_ENOTSUP
+static inline int tutel_notsup(const char *entry, const char *why) {
+  tutel_set_error("%s: not covered: %s", entry, why);
+  return TUTEL_AMD_ENOTSUP;
+}
 
 // ---- per-stage timing (api.hip): HIP events around the launches of one C-ABI call, when enabled -------------
 int tutel_stage_begin(int stage, hipStream_t st);  // returns a token (-1: timing off)

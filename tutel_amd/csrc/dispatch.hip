@@ -610,10 +610,7 @@ extern "C" int tutel_amd_gate_grad_packed(const void *x, const void *buf, int dt
 extern "C" int tutel_amd_fast_decode_packed(const void *buf, int dtype, const int32_t *idx, const int32_t *loc, const void *gates, int gate_dtype,
                                             int T, int M, int k, int row_limit, const int32_t *offsets, void *out, tutel_stream_t stream) {
   TUTEL_REQUIRE(dtype == TUTEL_BF16 || dtype == TUTEL_F16, "tutel_amd_fast_decode_packed: dtype must be bf16 or fp16 (got %d)", dtype);
-  if (k > 16) {
-    tutel_set_error("tutel_amd_fast_decode_packed: not covered: k <= 16");
-    return TUTEL_AMD_ENOTSUP;
-  }
+  if (k > 16) return tutel_notsup("tutel_amd_fast_decode_packed", "k <= 16");
   TUTEL_REQUIRE(T >= 0 && M >= 1 && k >= 1 && row_limit >= 1 && (gates == nullptr || dtype_ok(gate_dtype)),
                 "tutel_amd_fast_decode_packed: bad arguments T=%d M=%d k=%d limit=%d", T, M, k, row_limit);
   return tutel_decode_packed_launch(buf, dtype, idx, loc, gates, gate_dtype, T, M, k, row_limit, offsets, out, (hipStream_t)stream);

@@ -136,10 +136,7 @@ extern "C" int tutel_amd_packed_plan(int T, int E, int k, int M, int H, int M_ou
   TUTEL_REQUIRE(out != nullptr && T >= 0 && E >= 1 && k >= 1 && M >= 1 && H >= 1 && M_out >= 1 && capacity_limit >= 0 && alignment >= 1,
                 "tutel_amd_packed_plan: bad sizes T=%d E=%d k=%d M=%d H=%d M_out=%d limit=%d alignment=%d", T, E, k, M, H, M_out,
                 capacity_limit, alignment);
-  auto notsup = [](const char *why) {
-    tutel_set_error("tutel_amd_packed_plan: not covered: %s", why);
-    return TUTEL_AMD_ENOTSUP;
-  };
+  auto notsup = [](const char *why) { return tutel_notsup("tutel_amd_packed_plan", why); };
   if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return notsup("16-bit experts only");
   if (k > 16 || k > E || E > LY_MAX_E || (long long)k * E > 8192) return notsup("1 <= k <= min(E, 16), E <= 4096, k * E <= 8192");
   if (M % 64 != 0 || H % 64 != 0) return notsup("M and H must be multiples of 64");
@@ -209,10 +206,8 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
   tutel_amd_packed_plan_t pl;
   int rc = tutel_amd_packed_plan(T, E, k, M, H, Mo, a.dtype, m->capacity_limit, m->alignment, &pl);
   if (rc) return rc;
-  if (!a.is_postscore || !a.w2_kmajor) {
-    tutel_set_error("tutel_amd_moe_forward_packed: not covered: needs is_postscore (gates in the decode) and k-major fc2 weights");
-    return TUTEL_AMD_ENOTSUP;
-  }
+  if (!a.is_postscore || !a.w2_kmajor)
+    return tutel_notsup("tutel_amd_moe_forward_packed", "needs is_postscore (gates in the decode) and k-major fc2 weights");
   TUTEL_REQUIRE(pk->offsets != nullptr && pk->capacity != nullptr && m->dispatch_count != nullptr && m->ws != nullptr,
                 "tutel_amd_moe_forward_packed: null pointer");
   TUTEL_REQUIRE(pk->ws != nullptr && ((uintptr_t)pk->ws & 15) == 0 && pk->ws_bytes >= pl.ws_bytes,
@@ -235,10 +230,8 @@ static int forward_packed(tutel_amd_ep_comm_t *c, const tutel_amd_moe_args_t *m,
   TUTEL_REQUIRE(a.act >= TUTEL_ACT_NONE && a.act <= TUTEL_ACT_SILU, "tutel_amd_moe_forward_packed: unknown activation %d", a.act);
   TUTEL_REQUIRE(w_up == nullptr || (a.b1 == nullptr && a.b2 == nullptr && ((uintptr_t)w_up & 15) == 0),
                 "tutel_amd_moe_forward_packed_glu: SwiGLU experts take no biases, and w_up must be 16-byte aligned");
-  if (w_up != nullptr && a.act != TUTEL_ACT_RELU && a.act != TUTEL_ACT_GELU && a.act != TUTEL_ACT_SILU) {
-    tutel_set_error("tutel_amd_moe_forward_packed_glu: not covered: the gate activation must be relu, gelu or silu");
-    return TUTEL_AMD_ENOTSUP;
-  }
+  if (w_up != nullptr && a.act != TUTEL_ACT_RELU && a.act != TUTEL_ACT_GELU && a.act != TUTEL_ACT_SILU)
+    return tutel_notsup("tutel_amd_moe_forward_packed_glu", "the gate activation must be relu, gelu or silu");
   auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
   TUTEL_REQUIRE(al16(a.x) && al16(a.w1) && al16(a.w2) && al16(a.y) && al16(a.zero_row) && ((uintptr_t)a.b1 & 7) == 0 && ((uintptr_t)a.b2 & 7) == 0,
                 "tutel_amd_moe_forward_packed: x / weights / y / zero_row must be 16-byte aligned (biases 8-byte)");

@@ -895,17 +895,6 @@ static int launch_plan(const GemmPlan &p, const GemmArgs &a, hipStream_t st) {
   return launch_lds(kern, (unsigned)p.grid, p.threads, (size_t)p.lds_bytes, st, b, p.entry);
 }
 
-// dtype x activation -> f(ElemTag<element type>, std::integral_constant<int, ACT>) for the activations listed in ACTS, the only ones
-// a site instantiates kernels for; any other activation answers other() -- each site's own error
-template <typename T> struct ElemTag { using type = T; };
-template <int... ACTS, typename F, typename Other>
-static int dispatch_dtype_act(int dtype, int act, F &&f, Other &&other) {
-  int rc = 0;
-  const bool hit = ((act == ACTS && ((rc = dtype == TUTEL_BF16 ? f(ElemTag<bf16_t>{}, std::integral_constant<int, ACTS>{})
-                                                                : f(ElemTag<f16_t>{}, std::integral_constant<int, ACTS>{})), true)) || ...);
-  return hit ? rc : other();
-}
-
 // Argument checks + the GemmArgs block of one grouped GEMM (shared with expert_ffn.hip, which runs two of them in one launch).
 // 0: *out is filled; 1: nothing to do (E_loc == 0 or R == 0); < 0: error (tutel_amd_last_error).
 int tutel_gemm_args(const GemmProblem &g, GemmArgs *out) {
@@ -1083,15 +1072,11 @@ extern "C" int tutel_amd_expert_gemm_gather(const void *X, int ldx, const int32_
 // limit come from (the device tile table).
 
 // ---- fused gate/up GEMM of a SwiGLU expert (GATE_UP ping-pong kernel) -------------------------------------------------------------
-static int gate_up_notsup(const char *why) {
-  tutel_set_error("tutel_amd_expert_gemm_gate_up: not covered: %s", why);
-  return TUTEL_AMD_ENOTSUP;
-}
-
+static const char GATE_UP[] = "tutel_amd_expert_gemm_gate_up";  // the entry its refusals name, the packed form's too
 static bool gate_up_act_ok(int act) { return act == TUTEL_ACT_RELU || act == TUTEL_ACT_GELU || act == TUTEL_ACT_SILU; }
 static int gate_up_run(const GemmArgs &a, int dtype, int act, int tiles_bound, hipStream_t st) {
   return run_plan<TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(gemm_plan(a, true, true, tiles_bound, gemm_knobs()), a, dtype, act, TUTEL_STAGE_FC1, st,
-                                                                 [] { return gate_up_notsup("the gate activation must be relu, gelu or silu"); });
+                                                                 [] { return tutel_notsup(GATE_UP, "the gate activation must be relu, gelu or silu"); });
 }
 
 extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
@@ -1099,15 +1084,15 @@ extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, 
                                              int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
                                              const int32_t *row_counts, int row_align, tutel_stream_t stream) {
   GemmPlanScope scope;
-  if (!gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  if (!gate_up_act_ok(act)) return tutel_notsup(GATE_UP, "the gate activation must be relu, gelu or silu");
   const GemmProblem g = padded_problem(A, a_stride_e, a_stride_w, a_rows_per_w, lda, W_gate, w_stride_e, ldw, nullptr, 0, D, d_stride_e, d_stride_w,
                                        d_rows_per_w, ldd, E_loc, R, N, K, dtype, row_counts, row_align);
   GemmArgs a;
   const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   TUTEL_REQUIRE(W_up != nullptr && ((uintptr_t)W_up % 16) == 0, "tutel_amd_expert_gemm_gate_up: W_up must be a 16-byte aligned pointer");
-  if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
-  if (!gemm_out_rows16(a)) return gate_up_notsup("output rows must be 16-byte aligned");
+  if (!a.fits32) return tutel_notsup(GATE_UP, "operands past 2 GiB");
+  if (!gemm_out_rows16(a)) return tutel_notsup(GATE_UP, "output rows must be 16-byte aligned");
   a.w_up = W_up;
   return gate_up_run(a, dtype, act, 0, (hipStream_t)stream);
 }
@@ -1116,15 +1101,15 @@ extern "C" int tutel_amd_expert_gemm_gate_up(const void *A, int64_t a_stride_e, 
 int tutel_expert_gemm_packed(const GemmProblem &g, int w_kmajor, int act, const PackedTable &t, const void *w_up, hipStream_t st) {
   TUTEL_REQUIRE(t.off && t.tiles && t.ntiles && t.cap && t.tiles_bound >= 1 && g.R >= 1 && (g.a_rows == nullptr || g.a_rows_mod >= 1),
                 "%s: bad arguments", w_up != nullptr ? "tutel_expert_gemm_gate_up_packed" : "tutel_expert_gemm_packed");
-  if (w_up != nullptr && !gate_up_act_ok(act)) return gate_up_notsup("the gate activation must be relu, gelu or silu");
+  if (w_up != nullptr && !gate_up_act_ok(act)) return tutel_notsup(GATE_UP, "the gate activation must be relu, gelu or silu");
   GemmArgs a;
   const int brc = tutel_gemm_args(g, &a);
   if (brc != 0) return brc < 0 ? brc : 0;
   a.pk_off = t.off; a.pk_tiles = t.tiles; a.pk_ntiles = t.ntiles; a.pk_cap = t.cap;
   if (w_up != nullptr) {
     TUTEL_REQUIRE(((uintptr_t)w_up % 16) == 0, "tutel_expert_gemm_gate_up_packed: W_up must be a 16-byte aligned pointer");
-    if (!a.fits32) return gate_up_notsup("operands past 2 GiB");
-    if (!gemm_out_rows16(a)) return gate_up_notsup("output rows must be 16-byte aligned");  // (the packed layout has no expert strides)
+    if (!a.fits32) return tutel_notsup(GATE_UP, "operands past 2 GiB");
+    if (!gemm_out_rows16(a)) return tutel_notsup(GATE_UP, "output rows must be 16-byte aligned");  // (the packed layout has no expert strides)
     a.w_up = w_up;
     return gate_up_run(a, g.dtype, act, t.tiles_bound, st);
   }
@@ -1135,10 +1120,7 @@ int tutel_expert_gemm_packed(const GemmProblem &g, int w_kmajor, int act, const 
   const GemmPlan pl = gemm_plan(a, w_kmajor != 0, false, t.tiles_bound, gemm_knobs());
   const int stage = act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2;
   if (!w_kmajor)
-    return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(pl, a, g.dtype, act, stage, st, [&] {
-      tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu");
-      return TUTEL_AMD_ENOTSUP;
-    });
+    return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU>(pl, a, g.dtype, act, stage, st, [] { return tutel_notsup("tutel_amd_expert_gemm_packed", "n-major weights take act none or relu"); });
   return run_plan<TUTEL_ACT_NONE, TUTEL_ACT_RELU, TUTEL_ACT_GELU, TUTEL_ACT_SILU>(
       pl, a, g.dtype, act, stage, st, [&] { tutel_set_error("tutel_expert_gemm_packed: unknown activation %d", act); return -1; });
 }

@@ -216,24 +216,19 @@ static bool xf_shape_ok(int N, int K) { return N >= 4 && N % 4 == 0 && K >= XF_B
 
 extern "C" int tutel_amd_expert_gemm_f32_supported(int N, int K) { return xf_shape_ok(N, K) ? 1 : 0; }
 
-static int xf_notsup(const char *why) {
-  tutel_set_error("tutel_amd_expert_gemm_f32: not covered: %s", why);
-  return TUTEL_AMD_ENOTSUP;
-}
+static const char XF_ENTRY[] = "tutel_amd_expert_gemm_f32";
+static int xf_bad_act() { return tutel_notsup(XF_ENTRY, "the activation must be none, relu, gelu or silu"); }
 
-template <int WK, int ACT, int TT> static int xf_launch(const XfArgs &a, unsigned grid, hipStream_t st) {
-  hipLaunchKernelGGL((expert_gemm_f32_kernel<WK, ACT, TT>), dim3(grid), dim3(XF_THREADS), 4 * (64 * TT) * XF_BK * 4, st, a);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_f32");
-  return 0;
-}
-
-template <int WK, int TT> static int xf_launch_act(const XfArgs &a, int act, unsigned grid, hipStream_t st) {
-  switch (act) {
-    case TUTEL_ACT_NONE: return xf_launch<WK, TUTEL_ACT_NONE, TT>(a, grid, st);
-    case TUTEL_ACT_RELU: return xf_launch<WK, TUTEL_ACT_RELU, TT>(a, grid, st);
-    case TUTEL_ACT_GELU: return xf_launch<WK, TUTEL_ACT_GELU, TT>(a, grid, st);
-    default: return xf_launch<WK, TUTEL_ACT_SILU, TT>(a, grid, st);
-  }
+// (the activations last to first: the compiler instantiates the list's kernels from its end, and they keep their order in the code object)
+template <int WK, int TT> static int xf_launch(const XfArgs &a, int act, unsigned grid, hipStream_t st) {
+  return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
+      act,
+      [&](auto ac) {
+        hipLaunchKernelGGL((expert_gemm_f32_kernel<WK, decltype(ac)::value, TT>), dim3(grid), dim3(XF_THREADS), 4 * (64 * TT) * XF_BK * 4, st, a);
+        TUTEL_CHECK_LAUNCH(XF_ENTRY);
+        return 0;
+      },
+      xf_bad_act);
 }
 
 // The tile: a pure function of (E_loc, R, N).  128 x 128 where that fills the chip (one tile per CU or more); 64 x 64 below that --
@@ -251,17 +246,17 @@ extern "C" int tutel_amd_expert_gemm_f32(const void *A, int64_t a_stride_e, int6
                                          int act, const int32_t *slot_map, int T, const void *zero_row, tutel_stream_t stream) {
   // every check stands in front of the first HIP call
   TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_f32: bad sizes E_loc=%d R=%d N=%d K=%d", E_loc, R, N, K);
-  if (K % XF_BK != 0) return xf_notsup("K must be a multiple of 32");
-  if (N % 4 != 0) return xf_notsup("N must be a multiple of 4");
+  if (K % XF_BK != 0) return tutel_notsup(XF_ENTRY, "K must be a multiple of 32");
+  if (N % 4 != 0) return tutel_notsup(XF_ENTRY, "N must be a multiple of 4");
   if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
-    return xf_notsup("the activation must be none, relu, gelu or silu");
+    return xf_bad_act();
   if (lda % 4 != 0 || ldw % 4 != 0 || ldd % 4 != 0 || a_stride_e % 4 != 0 || a_stride_w % 4 != 0 || w_stride_e % 4 != 0 || d_stride_e % 4 != 0 ||
       d_stride_w % 4 != 0)
-    return xf_notsup("leading dimensions and strides must keep rows 16-byte aligned (multiples of 4)");
+    return tutel_notsup(XF_ENTRY, "leading dimensions and strides must keep rows 16-byte aligned (multiples of 4)");
   const int tile = xf_tile(E_loc, R, N);
   const long long ntm = (R + tile - 1) / tile, ntn = (N + tile - 1) / tile;
   if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL)
-    return xf_notsup("E_loc * R and the tile count must stay below 2^31");
+    return tutel_notsup(XF_ENTRY, "E_loc * R and the tile count must stay below 2^31");
   if (E_loc == 0 || R == 0) return 0;
   TUTEL_REQUIRE(A && W && D, "tutel_amd_expert_gemm_f32: null pointer");
   TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)D % 4) == 0 && ((uintptr_t)bias % 4) == 0,
@@ -283,6 +278,6 @@ extern "C" int tutel_amd_expert_gemm_f32(const void *A, int64_t a_stride_e, int6
   hipStream_t st = (hipStream_t)stream;
   StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
   const unsigned grid = (unsigned)((long long)E_loc * ntm * ntn);
-  if (tile == 128) return w_kmajor ? xf_launch_act<1, 2>(a, act, grid, st) : xf_launch_act<0, 2>(a, act, grid, st);
-  return w_kmajor ? xf_launch_act<1, 1>(a, act, grid, st) : xf_launch_act<0, 1>(a, act, grid, st);
+  if (tile == 128) return w_kmajor ? xf_launch<1, 2>(a, act, grid, st) : xf_launch<0, 2>(a, act, grid, st);
+  return w_kmajor ? xf_launch<1, 1>(a, act, grid, st) : xf_launch<0, 1>(a, act, grid, st);
 }

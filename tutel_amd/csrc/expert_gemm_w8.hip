@@ -241,24 +241,19 @@ static bool w8_shape_ok(int N, int K) { return N >= 32 && N % 32 == 0 && K >= W8
 
 extern "C" int tutel_amd_expert_gemm_w8_supported(int dtype, int N, int K) { return w8_dtype_ok(dtype) && w8_shape_ok(N, K) ? 1 : 0; }
 
-static int w8_notsup(const char *why) {
-  tutel_set_error("tutel_amd_expert_gemm_w8: not covered: %s", why);
-  return TUTEL_AMD_ENOTSUP;
-}
+static const char W8_ENTRY[] = "tutel_amd_expert_gemm_w8";
+static int w8_bad_act() { return tutel_notsup(W8_ENTRY, "the activation must be none, relu, gelu or silu"); }
 
-template <typename T, int ACT> static int w8_launch(const W8Args &a, unsigned grid, hipStream_t st) {
-  hipLaunchKernelGGL((expert_gemm_w8_kernel<T, ACT>), dim3(grid), dim3(W8_THREADS), 0, st, a);
-  TUTEL_CHECK_LAUNCH("tutel_amd_expert_gemm_w8");
-  return 0;
-}
-
-template <typename T> static int w8_launch_act(const W8Args &a, int act, unsigned grid, hipStream_t st) {
-  switch (act) {
-    case TUTEL_ACT_NONE: return w8_launch<T, TUTEL_ACT_NONE>(a, grid, st);
-    case TUTEL_ACT_RELU: return w8_launch<T, TUTEL_ACT_RELU>(a, grid, st);
-    case TUTEL_ACT_GELU: return w8_launch<T, TUTEL_ACT_GELU>(a, grid, st);
-    default: return w8_launch<T, TUTEL_ACT_SILU>(a, grid, st);
-  }
+// (the activations last to first: the compiler instantiates the list's kernels from its end, and they keep their order in the code object)
+template <typename T> static int w8_launch(const W8Args &a, int act, unsigned grid, hipStream_t st) {
+  return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
+      act,
+      [&](auto ac) {
+        hipLaunchKernelGGL((expert_gemm_w8_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W8_THREADS), 0, st, a);
+        TUTEL_CHECK_LAUNCH(W8_ENTRY);
+        return 0;
+      },
+      w8_bad_act);
 }
 
 extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
@@ -268,20 +263,20 @@ extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64
                                         const void *zero_row, tutel_stream_t stream) {
   // every check stands in front of the first HIP call
   TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_w8: bad sizes E_loc=%d R=%d N=%d K=%d", E_loc, R, N, K);
-  if (!w8_dtype_ok(dtype)) return w8_notsup("the activations must be bf16 or fp16");
-  if (K % W8_BK != 0) return w8_notsup("K must be a multiple of 64");
-  if (N % 32 != 0) return w8_notsup("N must be a multiple of 32");
+  if (!w8_dtype_ok(dtype)) return tutel_notsup(W8_ENTRY, "the activations must be bf16 or fp16");
+  if (K % W8_BK != 0) return tutel_notsup(W8_ENTRY, "K must be a multiple of 64");
+  if (N % 32 != 0) return tutel_notsup(W8_ENTRY, "N must be a multiple of 32");
   if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
-    return w8_notsup("the activation must be none, relu, gelu or silu");
-  if (row_counts != nullptr) return w8_notsup("row_counts (megablocks) are not covered");
+    return w8_bad_act();
+  if (row_counts != nullptr) return tutel_notsup(W8_ENTRY, "row_counts (megablocks) are not covered");
   if ((slot_map == nullptr && (a_rows_per_w < R || a_stride_w != 0)) || d_rows_per_w < R || d_stride_w != 0)
-    return w8_notsup("the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
+    return tutel_notsup(W8_ENTRY, "the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
   if (lda % 8 != 0 || ldd % 4 != 0 || a_stride_e % 8 != 0 || d_stride_e % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0)
-    return w8_notsup("rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
-  if (w_stride_e < (int64_t)N * K) return w8_notsup("w_stride_e is smaller than one expert's image (N * K bytes)");
+    return tutel_notsup(W8_ENTRY, "rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
+  if (w_stride_e < (int64_t)N * K) return tutel_notsup(W8_ENTRY, "w_stride_e is smaller than one expert's image (N * K bytes)");
   const long long ntm = (R + W8_BM - 1) / W8_BM, ntn = (N + W8_BN - 1) / W8_BN;
   if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL)
-    return w8_notsup("E_loc * R and the tile count must stay below 2^31");
+    return tutel_notsup(W8_ENTRY, "E_loc * R and the tile count must stay below 2^31");
   if (E_loc == 0 || R == 0) return 0;
   TUTEL_REQUIRE(A && Wq && scale && D, "tutel_amd_expert_gemm_w8: null pointer");
   TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)D % 8) == 0 &&
@@ -302,5 +297,5 @@ extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64
   hipStream_t st = (hipStream_t)stream;
   StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
   const unsigned grid = (unsigned)((long long)E_loc * ntm * ntn);
-  return dtype == TUTEL_BF16 ? w8_launch_act<bf16_t>(a, act, grid, st) : w8_launch_act<f16_t>(a, act, grid, st);
+  return dtype == TUTEL_BF16 ? w8_launch<bf16_t>(a, act, grid, st) : w8_launch<f16_t>(a, act, grid, st);
 }

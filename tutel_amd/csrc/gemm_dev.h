@@ -3,6 +3,8 @@
 // device function.  expert_gemm.hip launches the tile one per workgroup; expert_ffn.hip (round 6) runs it item after item inside one
 // persistent launch for fc1 -> activation -> fc2.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 // probe points of the ring tile (tools/scratch/tile_bench.hip defines this to timestamp them; empty in the library)
@@ -38,6 +40,24 @@ static int launch_lds(Kern kern, unsigned grid, int threads, size_t lds, hipStre
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, args);
   TUTEL_CHECK_LAUNCH(what);
   return 0;
+}
+
+// Host side, dispatch_act: run-time activation -> f(std::integral_constant<int, ACT>) for the activations listed in ACTS, the only ones
+// a site instantiates kernels for; any other activation answers other() -- each site's own error.
+// dispatch_dtype_act: the same over bf16 / fp16 as well -> f(ElemTag<element type>, std::integral_constant<int, ACT>)
+template <int... ACTS, typename F, typename Other>
+static int dispatch_act(int act, F &&f, Other &&other) {
+  int rc = 0;
+  const bool hit = ((act == ACTS && ((rc = f(std::integral_constant<int, ACTS>{})), true)) || ...);
+  return hit ? rc : other();
+}
+template <typename T> struct ElemTag { using type = T; };
+template <int... ACTS, typename F, typename Other>
+static int dispatch_dtype_act(int dtype, int act, F &&f, Other &&other) {
+  int rc = 0;
+  const bool hit = ((act == ACTS && ((rc = dtype == TUTEL_BF16 ? f(ElemTag<bf16_t>{}, std::integral_constant<int, ACTS>{})
+                                                                : f(ElemTag<f16_t>{}, std::integral_constant<int, ACTS>{})), true)) || ...);
+  return hit ? rc : other();
 }
 
 #define GM_BM 128

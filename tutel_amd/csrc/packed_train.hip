@@ -181,22 +181,17 @@ __global__ __launch_bounds__(256) void packed_bgrad_kernel(const T *__restrict__
 
 // the three entry points of each gradient share their checks and launches: `what` names the caller in errors, out_f32 picks the
 // output form, acc (with out_f32) the accumulating epilogue
-static int wgrad_notsup(const char *what, const char *why) {
-  tutel_set_error("%s: not covered: %s", what, why);
-  return TUTEL_AMD_ENOTSUP;
-}
-
 static int wgrad_packed(const char *what, bool out_f32, bool acc, const void *A, int lda, const void *B, int ldb, const int32_t *rows_map, int gather, int T,
                         const void *zero_row, void *D, int E, int rows_bound, int Na, int Nb, int dtype, const int32_t *offsets,
                         tutel_stream_t stream) {
   TUTEL_REQUIRE(E >= 1 && rows_bound >= 0 && Na >= 1 && Nb >= 1 && lda >= Na && ldb >= Nb && gather >= 0 && gather <= 2 &&
                     (gather == 0 || (rows_map != nullptr && T >= 1)),
                 "%s: bad sizes E=%d rows=%d Na=%d Nb=%d lda=%d ldb=%d gather=%d T=%d", what, E, rows_bound, Na, Nb, lda, ldb, gather, T);
-  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup(what, "16-bit operands only");
+  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return tutel_notsup(what, "16-bit operands only");
   if (Na % 8 != 0 || Nb % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0)
-    return wgrad_notsup(what, "N_a, N_b and the leading dimensions must be multiples of 8");
+    return tutel_notsup(what, "N_a, N_b and the leading dimensions must be multiples of 8");
   const long long tiles = (long long)E * ((Na + WG_T - 1) / WG_T) * ((Nb + WG_T - 1) / WG_T);
-  if (tiles >= 0x7fffffffLL) return wgrad_notsup(what, "more than 2^31 output tiles");
+  if (tiles >= 0x7fffffffLL) return tutel_notsup(what, "more than 2^31 output tiles");
   TUTEL_REQUIRE(A && B && D && offsets && (gather == 0 || zero_row), "%s: null pointer", what);
   auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
   TUTEL_REQUIRE(al16(A) && al16(B) && al16(zero_row) && ((uintptr_t)D & (out_f32 ? 15 : 7)) == 0,
@@ -247,7 +242,7 @@ extern "C" int tutel_amd_expert_wgrad_packed_acc_f32(const void *A, int lda, con
 static int bgrad_packed(const char *what, bool out_f32, bool acc, const void *B, int ldb, void *D, int E, int N, int dtype, const int32_t *offsets,
                         tutel_stream_t stream) {
   TUTEL_REQUIRE(E >= 1 && N >= 1 && ldb >= N, "%s: bad sizes E=%d N=%d ldb=%d", what, E, N, ldb);
-  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return wgrad_notsup(what, "16-bit operands only");
+  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return tutel_notsup(what, "16-bit operands only");
   TUTEL_REQUIRE(E <= 65535, "%s: E=%d above the grid's 65535", what, E);
   TUTEL_REQUIRE(B && D && offsets, "%s: null pointer", what);
   TUTEL_REQUIRE(!out_f32 || ((uintptr_t)D & 15) == 0, "%s: D must be 16-byte aligned", what);
@@ -296,18 +291,10 @@ extern "C" int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_
   GemmPlanScope scope;
   TUTEL_REQUIRE(E >= 1 && rows_bound >= 1 && tiles_bound >= 1 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_packed: bad sizes E=%d rows=%d tiles=%d N=%d K=%d",
                 E, rows_bound, tiles_bound, N, K);
-  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) {
-    tutel_set_error("tutel_amd_expert_gemm_packed: not covered: 16-bit operands only");
-    return TUTEL_AMD_ENOTSUP;
-  }
-  if (!w_kmajor && (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU)) {
-    tutel_set_error("tutel_amd_expert_gemm_packed: not covered: n-major weights take act none or relu");
-    return TUTEL_AMD_ENOTSUP;
-  }
-  if (!w_kmajor && mul != nullptr) {
-    tutel_set_error("tutel_amd_expert_gemm_packed: not covered: the gated form takes k-major weights");
-    return TUTEL_AMD_ENOTSUP;
-  }
+  if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return tutel_notsup("tutel_amd_expert_gemm_packed", "16-bit operands only");
+  if (!w_kmajor && (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU))
+    return tutel_notsup("tutel_amd_expert_gemm_packed", "n-major weights take act none or relu");
+  if (!w_kmajor && mul != nullptr) return tutel_notsup("tutel_amd_expert_gemm_packed", "the gated form takes k-major weights");
   TUTEL_REQUIRE(offsets && tiles && ntiles && capacity, "tutel_amd_expert_gemm_packed: null pointer");
   TUTEL_REQUIRE(((uintptr_t)D & 15) == 0 && ldd % 8 == 0 && ((uintptr_t)mul & 15) == 0,
                 "tutel_amd_expert_gemm_packed: D and mul must be 16-byte aligned, ldd a multiple of 8");

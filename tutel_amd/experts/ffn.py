@@ -23,6 +23,7 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     hipBLASLt), op for op as the reference.
 """
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -206,6 +207,97 @@ def classify_activation(fn, dtype=None):
     return None
 
 
+# ---- the opt-in engines: replacements of the experts' default grouped GEMM -------------------------------------------------------
+class Engine(NamedTuple):
+    """One opt-in engine, by what differs between them.  Everything else is written once: FusedExpertsNetwork.engine_refusal walks
+    the ladder, admitted_engine picks the engine a forward takes, forward_engine runs it (MOELayer._plan routes by the same answer)."""
+    ran: str        # the attribute of the layer it reports into: True, or why this forward's experts did not take it
+    ladder: tuple   # checks (net, x, ctx, megablocks_size) -> reason or None, the switch first; the ORDER is behaviour (users read the first)
+    entry: str      # the library entry point `run` calls twice
+    run: object     # (net, x, R, slot_map) -> y [E_loc, R, M_out], or None where the library refused
+
+    def on(self, net):
+        return self.ladder[0](net, None, None, None) is None
+
+
+def _rung(reason, failed):
+    """one check of a ladder: `reason` where failed(net, x, ctx, megablocks_size) holds"""
+    return lambda net, x, ctx, mb: reason if failed(net, x, ctx, mb) else None
+
+
+def _params(net):
+    return net.batched_fc1_w, net.batched_fc2_w, net.batched_fc1_bias, net.batched_fc2_bias
+
+
+def _dtypes(reason, allowed):
+    """the input in one of the `allowed` dtypes and every parameter in the input's"""
+    return _rung(reason, lambda net, x, ctx, mb: x.dtype not in allowed or any(p is not None and p.dtype != x.dtype for p in _params(net)))
+
+
+def _shape(reason, covers):
+    """both products covered by the library's own query: covers(x, N, K) for fc1 (N = H, K = M) and fc2 (N = M_out, K = H)"""
+    return _rung(reason, lambda net, x, ctx, mb: not (covers(x, net.batched_fc1_w.size(1), net.batched_fc1_w.size(2))
+                                                      and covers(x, net.batched_fc2_w.size(2), net.batched_fc2_w.size(1))))
+
+
+_SKIP = _rung("SKIP_EXPERT is set", lambda net, x, ctx, mb: net.skip_expert)
+_DEVICE = _rung("the input is not on the HIP device", lambda net, x, ctx, mb: not x.is_cuda)
+_AUTOCAST = _rung("autocast is on", lambda net, x, ctx, mb: torch.is_autocast_enabled())
+_GATHERED = _rung("gathered-weight modes (sharded experts, adaptive_r = 0) are not covered",
+                  lambda net, x, ctx, mb: getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0)
+_MEGABLOCKS = _rung("megablocks row counts are not covered",   # mb: the value this forward will run with, where ctx does not hold it yet
+                    lambda net, x, ctx, mb: (getattr(ctx, "megablocks_size", 0) if mb is None else mb) != 0)
+_AUTOGRAD_F32 = _rung("autograd is live (training stays on ATen)", lambda net, x, ctx, mb: not net._no_autograd(x))
+_AUTOGRAD_W8 = _rung("autograd is live (FP8 weights are inference only)", lambda net, x, ctx, mb: not net._no_autograd(x))
+_ACTIVATION = _rung("the activation is not one of the fused epilogues", lambda net, x, ctx, mb: net.fused_activation() is None)
+
+
+def _inference_params(net):
+    """(w1, b1, w2, b2) detached, b2 cut to the output's width"""
+    w1, w2, b1, b2 = (p.detach() if p is not None else None for p in _params(net))
+    return w1, b1, w2, (b2[:, :net.output_dim] if b2 is not None else None)
+
+
+def _run_f32(net, x, R, slot_map):
+    """fc1 k-major with bias + activation, fc2 in its [H, M_out] layout"""
+    w1, b1, w2, b2 = _inference_params(net)
+    h = ops.expert_gemm_f32(x, w1, b1, True, act=net.fused_activation(), slot_map=slot_map, R=R)
+    return ops.expert_gemm_f32(h, w2, b2, False) if h is not None else None
+
+
+def _run_w8(net, x, R, slot_map):
+    (i1, s1), (i2, s2) = net.w8_params()
+    w1, b1, w2, b2 = _inference_params(net)
+    h = ops.expert_gemm_w8(x, i1, s1, b1, w1.size(1), w1.size(2), act=net.fused_activation(), slot_map=slot_map, R=R)
+    return ops.expert_gemm_w8(h, i2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
+
+
+# fp32 experts on the native fp32 grouped GEMM (the switch is read from the module at call time)
+F32 = Engine(
+    ran="_native_fp32_ran", entry="tutel_amd_expert_gemm_f32", run=_run_f32,
+    ladder=(_rung("TUTEL_AMD_NATIVE_FP32 is off", lambda net, x, ctx, mb: not _NATIVE_FP32),
+            _SKIP, _DEVICE, _AUTOCAST,
+            _dtypes("the input and the experts' parameters are not all fp32", (torch.float32,)),
+            _AUTOGRAD_F32, _GATHERED, _MEGABLOCKS, _ACTIVATION,
+            _shape("the shape is not covered (M and H multiples of 32, H and M_out multiples of 4)",
+                   lambda x, N, K: ops.gemm_f32_supported(N, K))))
+# bf16 / fp16 experts in inference reading FP8 weights
+W8 = Engine(
+    ran="_fp8_weights_ran", entry="tutel_amd_expert_gemm_w8", run=_run_w8,
+    ladder=(_rung("fp8_weights is off (TUTEL_AMD_FP8_WEIGHTS)", lambda net, x, ctx, mb: not net.fp8_weights),
+            _SKIP, _DEVICE, _AUTOGRAD_W8,
+            _rung("the module is in training mode (FP8 weights are inference only)", lambda net, x, ctx, mb: net.training),
+            _AUTOCAST, _dtypes("the input is not bf16 / fp16 in the experts' own dtype", (torch.bfloat16, torch.float16)),
+            _GATHERED, _MEGABLOCKS, _ACTIVATION,
+            _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
+                   lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K)),
+            # (quantising inside a capture would allocate the images in the graph's pool and redo the work at every replay)
+            _rung("the quantised weights are not cached yet: run one eager forward before capturing a graph",
+                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not (
+                      net._kmajor.holds("fc1.w8", net.batched_fc1_w, "w8") and net._kmajor.holds("fc2.w8", net.batched_fc2_w, "w8")))))
+ENGINES = (W8, F32)   # the order FusedExpertsNetwork.forward tries them in; their dtype checks exclude each other
+
+
 class FusedExpertsNetwork(torch.nn.Module):
     def __init__(self, model_dim, hidden_size_per_expert, num_experts_per_device, sharded_count,
                  activation_fn=None, activation_fn_with_self=None, output_dim=None,
@@ -237,7 +329,7 @@ class FusedExpertsNetwork(torch.nn.Module):
         self.activation_fn = activation_fn
         self._act_cache = {}
         self._kmajor = KMajorCache()
-        # FP8 (e4m3) weights in inference, W8A16 (w8_refusal / forward_fused_w8); the 16-bit parameters stay as they are
+        # FP8 (e4m3) weights in inference, W8A16 (the W8 engine); the 16-bit parameters stay as they are
         self.fp8_weights = _FP8_WEIGHTS
 
         E, H = num_experts_per_device, self.hidden_size
@@ -322,84 +414,55 @@ class FusedExpertsNetwork(torch.nn.Module):
                 and ops.gemm_supported(dt, w1.size(1), w1.size(2)) and ops.gemm_supported(dt, w2.size(2), w2.size(1))
                 and ops.gemm_supported(dt, w2.size(1), w2.size(2)) and ops.gemm_supported(dt, w1.size(2), w1.size(1)))
 
-    def f32_refusal(self, x, ctx, megablocks_size=None):
-        """why this forward does not take the native fp32 grouped GEMM (a string), or None when it does.  megablocks_size: the value
-        this forward will run with, where ctx does not hold it yet"""
-        if not _NATIVE_FP32:
-            return "TUTEL_AMD_NATIVE_FP32 is off"
-        if self.skip_expert:
-            return "SKIP_EXPERT is set"
-        if not x.is_cuda:
-            return "the input is not on the HIP device"
-        if torch.is_autocast_enabled():
-            return "autocast is on"
-        params = (self.batched_fc1_w, self.batched_fc2_w, self.batched_fc1_bias, self.batched_fc2_bias)
-        if x.dtype != torch.float32 or any(p is not None and p.dtype != torch.float32 for p in params):
-            return "the input and the experts' parameters are not all fp32"
-        if not self._no_autograd(x):
-            return "autograd is live (training stays on ATen)"
-        if getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0:
-            return "gathered-weight modes (sharded experts, adaptive_r = 0) are not covered"
-        if (getattr(ctx, "megablocks_size", 0) if megablocks_size is None else megablocks_size) != 0:
-            return "megablocks row counts are not covered"
-        if self.fused_activation() is None:
-            return "the activation is not one of the fused epilogues"
-        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
-        if not (ops.gemm_f32_supported(w1.size(1), w1.size(2)) and ops.gemm_f32_supported(w2.size(2), w2.size(1))):
-            return "the shape is not covered (M and H multiples of 32, H and M_out multiples of 4)"
-        return None
+    # -- the opt-in engines (Engine, above) ---------------------------------------------------------
+    def engine_refusal(self, engine, x, ctx, megablocks_size=None):
+        """why this forward does not take `engine` (a string: its first failing check), or None when it does.  megablocks_size: the
+        value this forward will run with, where ctx does not hold it yet"""
+        reasons = (check(self, x, ctx, megablocks_size) for check in engine.ladder)
+        return next((why for why in reasons if why is not None), None)
 
-    def can_fuse_f32(self, x, ctx):
-        """fp32 experts on the native fp32 grouped GEMM: the switch, fp32 everywhere, no autocast, no autograd, this rank's own local
-        experts, no megablocks row counts, a recognised activation, both products covered"""
-        return self.f32_refusal(x, ctx) is None
+    def admitted_engine(self, x, ctx, megablocks_size=None):
+        """the opt-in engine this forward's experts run on, or None: the default GEMMs.  An engine that is switched off costs its
+        switch and nothing else"""
+        return next((e for e in ENGINES if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
 
-    def forward_fused_f32(self, x, ctx, R=None, slot_map=None):
-        """x [E_loc, R, M] contiguous -> [E_loc, R, M_out]; slot_map given: x is the TOKEN array [T, M] and fc1 gathers its rows
-        (R = capacity).  Two launches: fc1 k-major with bias + activation, fc2 in its [H, M_out] layout with b2[:, :output_dim]."""
-        w1, b1, w2, b2 = (p.detach() if p is not None else None
-                          for p in (self.batched_fc1_w, self.batched_fc1_bias, self.batched_fc2_w, self.batched_fc2_bias))
-        if b2 is not None:
-            b2 = b2[:, :self.output_dim]
-        h = ops.expert_gemm_f32(x, w1, b1, True, act=self.fused_activation(), slot_map=slot_map, R=R)
-        y = ops.expert_gemm_f32(h, w2, b2, False) if h is not None else None
-        if y is None:   # can_fuse_f32 asked the library's own coverage query: a refusal here is a bug, never a quiet ATen forward
+    def forward_engine(self, engine, x, R=None, slot_map=None):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M_out] in two launches of engine.entry; slot_map given: x is the TOKEN array [T, M]
+        and fc1 gathers its rows (R = capacity)"""
+        y = engine.run(self, x, R, slot_map)
+        if y is None:   # the ladder asked the library's own coverage query: a refusal here is a bug, never a quiet forward elsewhere
             from .. import _lib
-            raise _lib.TutelAmdError("tutel_amd_expert_gemm_f32 refused a shape its own query admits: " +
+            raise _lib.TutelAmdError(engine.entry + " refused a shape its own query admits: " +
                                      _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
         return y
 
+    def _forward_if_admitted(self, engine, x, ctx):
+        """forward()'s step for one engine: its output, or None where it is off or refuses -- the reason is kept for the caller"""
+        if not engine.on(self):
+            return None
+        why = self.engine_refusal(engine, x, ctx)
+        if why is None and not (x.dim() == 3 and x.size(0) == self.batched_fc1_w.size(0) and x.size(2) == self.batched_fc1_w.size(2)):
+            why = "the input is not [E_loc, R, M]"
+        try:
+            setattr(ctx, engine.ran, True if why is None else why)
+        except AttributeError:
+            pass
+        return self.forward_engine(engine, x.contiguous()) if why is None else None
+
+    def f32_refusal(self, x, ctx, megablocks_size=None):
+        return self.engine_refusal(F32, x, ctx, megablocks_size)
+
+    def can_fuse_f32(self, x, ctx):
+        return self.engine_refusal(F32, x, ctx) is None
+
+    def forward_fused_f32(self, x, ctx, R=None, slot_map=None):
+        return self.forward_engine(F32, x, R, slot_map)
+
     def w8_refusal(self, x, ctx, megablocks_size=None):
-        """why this forward does not read FP8 weights (a string), or None when it does.  megablocks_size: the value this forward will
-        run with, where ctx does not hold it yet"""
-        if not self.fp8_weights:
-            return "fp8_weights is off (TUTEL_AMD_FP8_WEIGHTS)"
-        if self.skip_expert:
-            return "SKIP_EXPERT is set"
-        if not x.is_cuda:
-            return "the input is not on the HIP device"
-        if not self._no_autograd(x):
-            return "autograd is live (FP8 weights are inference only)"
-        if self.training:
-            return "the module is in training mode (FP8 weights are inference only)"
-        if torch.is_autocast_enabled():
-            return "autocast is on"
-        params = (self.batched_fc1_w, self.batched_fc2_w, self.batched_fc1_bias, self.batched_fc2_bias)
-        if x.dtype not in (torch.bfloat16, torch.float16) or any(p is not None and p.dtype != x.dtype for p in params):
-            return "the input is not bf16 / fp16 in the experts' own dtype"
-        if getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0:
-            return "gathered-weight modes (sharded experts, adaptive_r = 0) are not covered"
-        if (getattr(ctx, "megablocks_size", 0) if megablocks_size is None else megablocks_size) != 0:
-            return "megablocks row counts are not covered"
-        if self.fused_activation() is None:
-            return "the activation is not one of the fused epilogues"
-        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
-        if not (ops.gemm_w8_supported(x.dtype, w1.size(1), w1.size(2)) and ops.gemm_w8_supported(x.dtype, w2.size(2), w2.size(1))):
-            return "the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)"
-        if torch.cuda.is_current_stream_capturing() and not (self._kmajor.holds("fc1.w8", w1, "w8") and self._kmajor.holds("fc2.w8", w2, "w8")):
-            # quantising here would allocate the images in the graph's pool and redo the work at every replay
-            return "the quantised weights are not cached yet: run one eager forward before capturing a graph"
-        return None
+        return self.engine_refusal(W8, x, ctx, megablocks_size)
+
+    def forward_fused_w8(self, x, ctx, R=None, slot_map=None):
+        return self.forward_engine(W8, x, R, slot_map)
 
     def w8_params(self):
         """((image1, scale1), (image2, scale2)): the FP8 images and scales of fc1 (read as stored, k-major) and fc2 (from its
@@ -407,22 +470,6 @@ class FusedExpertsNetwork(torch.nn.Module):
         p1 = self._kmajor.derived("fc1.w8", self.batched_fc1_w, "w8", lambda w: w8.prepare(w, True))
         p2 = self._kmajor.derived("fc2.w8", self.batched_fc2_w, "w8", lambda w: w8.prepare(w, False))
         return p1, p2
-
-    def forward_fused_w8(self, x, ctx, R=None, slot_map=None):
-        """x [E_loc, R, M] contiguous -> [E_loc, R, M_out]; slot_map given: x is the TOKEN array [T, M] and fc1 gathers its rows
-        (R = capacity).  Two launches of tutel_amd_expert_gemm_w8."""
-        (i1, s1), (i2, s2) = self.w8_params()
-        w1, w2 = self.batched_fc1_w, self.batched_fc2_w
-        b1, b2 = (p.detach() if p is not None else None for p in (self.batched_fc1_bias, self.batched_fc2_bias))
-        if b2 is not None:
-            b2 = b2[:, :self.output_dim]
-        h = ops.expert_gemm_w8(x, i1, s1, b1, w1.size(1), w1.size(2), act=self.fused_activation(), slot_map=slot_map, R=R)
-        y = ops.expert_gemm_w8(h, i2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
-        if y is None:   # w8_refusal asked the library's own coverage query: a refusal here is a bug, never a quiet 16-bit forward
-            from .. import _lib
-            raise _lib.TutelAmdError("tutel_amd_expert_gemm_w8 refused a shape its own query admits: " +
-                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
-        return y
 
     def fused_params(self, dtype):
         """(w1, b1, w2, b2, w2_kmajor) of this rank's experts in the GEMM's compute dtype: the parameters themselves, or
@@ -494,30 +541,17 @@ class FusedExpertsNetwork(torch.nn.Module):
     def forward(self, x, ctx):
         if self.skip_expert:
             return x
-        if self.fp8_weights:   # FP8 weights (opt-in); the reason they were not read is kept for the caller
-            why = self.w8_refusal(x, ctx)
-            if why is None and not (x.dim() == 3 and x.size(0) == self.batched_fc1_w.size(0) and x.size(2) == self.batched_fc1_w.size(2)):
-                why = "the input is not [E_loc, R, M]"
-            try:
-                ctx._fp8_weights_ran = True if why is None else why
-            except AttributeError:
-                pass
-            if why is None:
-                return self.forward_fused_w8(x.contiguous(), ctx)
+        # the opt-in engines (W8 in front of the default GEMMs, F32 behind them); the reason one did not run is kept for the caller
+        y = self._forward_if_admitted(W8, x, ctx)
+        if y is not None:
+            return y
 
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)
 
-        if _NATIVE_FP32:   # fp32 experts on the native grouped GEMM (opt-in); the reason it did not run is kept for the caller
-            why = self.f32_refusal(x, ctx)
-            if why is None and not (x.dim() == 3 and x.size(0) == self.batched_fc1_w.size(0) and x.size(2) == self.batched_fc1_w.size(2)):
-                why = "the input is not [E_loc, R, M]"
-            try:
-                ctx._native_fp32_ran = True if why is None else why
-            except AttributeError:
-                pass
-            if why is None:
-                return self.forward_fused_f32(x.contiguous(), ctx)
+        y = self._forward_if_admitted(F32, x, ctx)
+        if y is not None:
+            return y
 
         if self.can_fuse_training(x, ctx):
             dt = self.compute_dtype(x)

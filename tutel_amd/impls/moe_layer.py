@@ -247,30 +247,34 @@ class MOELayer(torch.nn.Module):
     #                    native pipeline is switched off)
     #   "generic"        the reference's op sequence on the HIP ops: training (autograd), custom / fp32 experts, CPU tensors,
     #                    sharded experts, adaptive_r = 0, 2DH with overlap
-    # fp32 experts under TUTEL_AMD_NATIVE_FP32 (experts/ffn.py::can_fuse_f32) take "fused_encode" or "generic" only: their GEMM is
-    # tutel_amd_expert_gemm_f32, called from FusedExpertsNetwork; 16-bit experts with FP8 weights switched on (experts.fp8_weights,
-    # experts/ffn.py::w8_refusal) are routed the same way: their GEMM is tutel_amd_expert_gemm_w8
-    def _plan(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
-              original_dtype, crit=None, allow_native=True):
+    # Experts admitted to an opt-in engine (experts/ffn.py::ENGINES: fp32 experts under TUTEL_AMD_NATIVE_FP32, 16-bit experts with
+    # experts.fp8_weights) take "fused_encode" or "generic" only: the one-call pipelines have neither GEMM.  Admission is asked ONCE per
+    # stage (FusedExpertsNetwork.admitted_engine, with THIS forward's megablocks_size) and handed on with the route: _route returns
+    # (path, engine or None), _plan the path alone.
+    def _plan(self, *args, **kwargs):
+        return self._route(*args, **kwargs)[0]
+
+    def _route(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
+               original_dtype, crit=None, allow_native=True):
         W = self.world_size
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
         # reason: ep_native.packed_cover, asked in _run_native_moe)
         swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
         fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
-                   and (x.dtype == logits.dtype or (logits.dtype == torch.float32 and x.dtype == original_dtype))
-                   and (swiglu_packed or self.experts.can_fuse(x, self) or self.experts.can_fuse_f32(x, self)))
+                   and (x.dtype == logits.dtype or (logits.dtype == torch.float32 and x.dtype == original_dtype)))
+        engine = None
+        if fusable and not swiglu_packed:
+            engine = self.experts.admitted_engine(x, self, megablocks_size=megablocks_size)
+            fusable = engine is not None or self.experts.can_fuse(x, self)
         if not fusable:
-            return "generic"
-        w8 = (not swiglu_packed and self.experts.fp8_weights and self.experts.w8_refusal(x, self, megablocks_size=megablocks_size) is None)
-        if (x.dtype == torch.float32 or w8) and not swiglu_packed:
-            # fp32 experts on the native fp32 grouped GEMM (can_fuse_f32; opt-in), 16-bit experts on FP8 weights (w8_refusal; opt-in): never
-            # the one-call pipelines -- they have neither GEMM.
+            return "generic", None
+        if engine is not None:
             # Single rank, is_postscore: fc1 gathers from the tokens; everything else reaches FusedExpertsNetwork.forward through "generic"
             if (stage == "after_routing" and W == 1 and self.is_postscore and isinstance(crit, RoutingPlan) and crit[4] > 0 and _FUSE_ENCODE
                     and crit.slot_map is not None):
-                return "fused_encode"
-            return "routed" if stage == "before_routing" else "generic"
+                return "fused_encode", engine
+            return ("routed" if stage == "before_routing" else "generic"), engine
         native = (allow_native and ep_native.ENABLED and not _FORCE_OVERLAP and degree <= 32 and (degree == 1 or not self.use_2dh)
                   and (W == 1 or ep_native.group_ok(self.group)))
         if stage == "before_routing":
@@ -287,17 +291,17 @@ class MOELayer(torch.nn.Module):
             elif ok:
                 ok = megablocks_size == 0 and self._static_capacity(T, E, k, cf, alignment) > 0 \
                     and self._static_capacity(T, E, k, cf, alignment) % max(degree, 1) == 0
-            return "native_moe" if ok else "routed"
+            return ("native_moe" if ok else "routed"), None
         # after routing: crit is known
         plan_ok = isinstance(crit, RoutingPlan)
         if native and plan_ok and ep_native.usable(self, x, crit, degree):
-            return "native_ep"
+            return "native_ep", None
         if (degree > 1 and plan_ok and (W > 1 or _FORCE_OVERLAP) and crit[4] > 0 and crit[4] % degree == 0 and not self.use_2dh
                 and crit.gates2d is not None):   # (a trainable router keeps its gates in crit[3] with autograd -> generic)
-            return "python_overlap"
+            return "python_overlap", None
         if W == 1 and self.is_postscore and plan_ok and crit[4] > 0 and _FUSE_ENCODE:
-            return "fused_encode"
-        return "generic"
+            return "fused_encode", None
+        return "generic", None
 
     @staticmethod
     def _static_capacity(T, E, k, cf, alignment):
@@ -403,8 +407,8 @@ class MOELayer(torch.nn.Module):
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
-        self._native_fp32_ran = None       # TUTEL_AMD_NATIVE_FP32: True, or why this forward's experts stayed on ATen
-        self._fp8_weights_ran = None       # experts.fp8_weights (TUTEL_AMD_FP8_WEIGHTS): True, or why this forward's experts read 16-bit weights
+        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_weights_ran: True, or why this forward's experts did not take the engine
+            setattr(self, engine.ran, None)
         if self.skip_moe:
             out = input
             out.l_aux = None
@@ -433,14 +437,12 @@ class MOELayer(torch.nn.Module):
             megablocks_size = 0
         if adaptive_r is not None:
             self.adaptive_degree = adaptive_r
-        if _ffn._NATIVE_FP32 and isinstance(self.experts, FusedExpertsNetwork):
-            # why this forward's experts will not run on the native fp32 grouped GEMM, known before routing (None: admitted so far;
+        if isinstance(self.experts, FusedExpertsNetwork):
+            # why this forward's experts will not take an engine that is switched on, known before routing (None: admitted so far;
             # whoever runs them -- the "fused_encode" route below, FusedExpertsNetwork.forward -- sets True, or a later reason)
-            self._native_fp32_ran = self.experts.f32_refusal(x, self, megablocks_size=megablocks_size)
-
-        if isinstance(self.experts, FusedExpertsNetwork) and self.experts.fp8_weights:
-            # the same for FP8 weights: None = admitted so far; the route that runs the experts sets True, or a later reason
-            self._fp8_weights_ran = self.experts.w8_refusal(x, self, megablocks_size=megablocks_size)
+            for engine in _ffn.ENGINES:
+                if engine.on(self.experts):
+                    setattr(self, engine.ran, self.experts.engine_refusal(engine, x, self, megablocks_size))
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega
@@ -527,7 +529,7 @@ class MOELayer(torch.nn.Module):
         self.dispatch_count = get_dispatch_count(crit)
         if getattr(self, "_keep_routing", False):   # tests: the routing this forward used, element by element
             self.last_routing = (torch.stack([t.to(torch.int32) for t in crit[1]]), torch.stack([t.to(torch.int32) for t in crit[2]]))
-        plan = self._plan("after_routing", x, logits, *plan_args, crit=crit)
+        plan, engine = self._route("after_routing", x, logits, *plan_args, crit=crit)
 
         if plan == "native_ep":
             # the whole post-routing pipeline behind ONE native call (csrc/ep.hip): encode -> all-to-all -> expert FFN ->
@@ -535,7 +537,7 @@ class MOELayer(torch.nn.Module):
             y = ep_native.forward(self, x if x.is_contiguous() else x.contiguous(), crit, degree)
             if y is not None:
                 return finish(y, l_aux)
-            plan = self._plan("after_routing", x, logits, *plan_args, crit=crit, allow_native=False)   # no communicator: all ranks agree
+            plan, engine = self._route("after_routing", x, logits, *plan_args, crit=crit, allow_native=False)   # no communicator: all ranks agree
 
         if plan == "python_overlap":   # overlapped expert parallelism driven from Python: one fused routine, no layout copies
             y = a2a_ffn_overlap_fused(self, x if x.is_contiguous() else x.contiguous(), crit, degree, self.is_postscore)
@@ -544,14 +546,12 @@ class MOELayer(torch.nn.Module):
         if plan == "fused_encode":
             # single rank, is_postscore: fast_encode is a pure row copy, so fc1 gathers its rows straight
             # from the tokens through the slot map -- the [E,C,M] bucket array is never materialised
-            if x.dtype == torch.float32:   # only can_fuse_f32 sends fp32 experts here
-                y = self.experts.forward_fused_f32(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
-                self._native_fp32_ran = True
-            elif self.experts.fp8_weights and self.experts.w8_refusal(x, self) is None:
-                y = self.experts.forward_fused_w8(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
-                self._fp8_weights_ran = True
+            xc = x if x.is_contiguous() else x.contiguous()
+            if engine is not None:   # the opt-in engine _route admitted
+                y = self.experts.forward_engine(engine, xc, R=crit[4], slot_map=crit.slot_map)
+                setattr(self, engine.ran, True)
             else:
-                y = self.experts.forward_fused(x if x.is_contiguous() else x.contiguous(), self, R=crit[4], slot_map=crit.slot_map)
+                y = self.experts.forward_fused(xc, self, R=crit[4], slot_map=crit.slot_map)
             self.protected_shape = y.shape
             return finish(fast_decode(y, crit, self.is_postscore), l_aux)
 

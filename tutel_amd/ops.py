@@ -411,6 +411,31 @@ def expert_gemm_gather(x, smap, w, bias, w_kmajor, act, R, row_counts=None, row_
     return out
 
 
+def _a_rows(a, E_loc, K, slot_map, R, a_layout):
+    """where a grouped GEMM's A rows come from -> (a at a 16-byte aligned address, R, a_layout, T, zero row): the token array [T, K]
+    gathered through slot_map [E_loc * R], any buffer described by a_layout with R, or [E_loc, R, K] contiguous"""
+    if slot_map is not None:
+        assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K and a_layout is None and R is not None
+        assert slot_map.dtype == torch.int32 and slot_map.numel() == E_loc * R
+        a = _a16(a)
+        return a, R, (0, 0, 1, a.stride(0)), a.shape[0], zero_row(K, a.dtype, a.device)
+    if a_layout is None:
+        assert a.dim() == 3 and a.is_contiguous() and a.shape[0] == E_loc and a.shape[2] == K
+        a = _a16(a)
+        R = a.shape[1]
+        a_layout = (R * K, 0, max(R, 1), K)
+    assert R is not None
+    return a, R, a_layout, 0, None
+
+
+def _unless_notsup(rc, what, out):
+    """the end of a call that may refuse: None where the library answered ENOTSUP (nothing was enqueued), any other failure raises"""
+    if rc == _lib.ENOTSUP:
+        return None
+    _lib.check(rc, what)
+    return out
+
+
 def gemm_f32_supported(N, K):
     """shapes the fp32 grouped GEMM (tutel_amd_expert_gemm_f32) takes: K % 32 == 0, N % 4 == 0 -- the library's own answer"""
     return bool(_lib.lib().tutel_amd_expert_gemm_f32_supported(int(N), int(K)))
@@ -427,19 +452,7 @@ def expert_gemm_f32(a, w, bias, w_kmajor, act="none", slot_map=None, R=None, a_l
     _dev(a, w, bias, out, slot_map)
     assert w.dim() == 3 and w.is_contiguous() and a.dtype == torch.float32 and w.dtype == torch.float32
     E_loc, N, K = (w.shape if w_kmajor else (w.shape[0], w.shape[2], w.shape[1]))
-    T, z = 0, None
-    if slot_map is not None:
-        assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K and a_layout is None and R is not None
-        assert slot_map.dtype == torch.int32 and slot_map.numel() == E_loc * R
-        a = _a16(a)
-        T, z = a.shape[0], zero_row(K, torch.float32, a.device)
-        a_layout = (0, 0, 1, a.stride(0))
-    elif a_layout is None:
-        assert a.dim() == 3 and a.is_contiguous() and a.shape[0] == E_loc and a.shape[2] == K
-        a = _a16(a)
-        R = a.shape[1]
-        a_layout = (R * K, 0, max(R, 1), K)
-    assert R is not None
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, a_layout)
     if out is None:
         out = torch.empty([E_loc, R, N], dtype=torch.float32, device=a.device)
         d_layout = (R * N, 0, max(R, 1), N)
@@ -452,10 +465,7 @@ def expert_gemm_f32(a, w, bias, w_kmajor, act="none", slot_map=None, R=None, a_l
         _ptr(bias), (bias.stride(0) if bias is not None else 0),
         _ptr(out), d_layout[0], d_layout[1], d_layout[2], d_layout[3],
         E_loc, R, N, K, ACT_CODES[act], _ptr(slot_map), T, _ptr(z), _stream())
-    if rc == _lib.ENOTSUP:
-        return None
-    _lib.check(rc, "tutel_amd_expert_gemm_f32")
-    return out
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_f32", out)
 
 
 def gemm_w8_supported(dtype, N, K):
@@ -477,18 +487,7 @@ def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=Non
     assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
     E_loc = image.shape[0]
     assert scale.shape == (E_loc, N) and image.numel() % max(E_loc, 1) == 0
-    T, z = 0, None
-    if slot_map is not None:
-        assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K and R is not None
-        assert slot_map.dtype == torch.int32 and slot_map.numel() == E_loc * R
-        a = _a16(a)
-        T, z = a.shape[0], zero_row(K, a.dtype, a.device)
-        a_layout = (0, 0, 1, a.stride(0))
-    else:
-        assert a.dim() == 3 and a.is_contiguous() and a.shape[0] == E_loc and a.shape[2] == K
-        a = _a16(a)
-        R = a.shape[1]
-        a_layout = (R * K, 0, max(R, 1), K)
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
     if out is None:
         out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
     assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
@@ -500,10 +499,7 @@ def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=Non
         _ptr(bias), (bias.stride(0) if bias is not None else 0),
         _ptr(out), R * N, 0, max(R, 1), N,
         E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
-    if rc == _lib.ENOTSUP:
-        return None
-    _lib.check(rc, "tutel_amd_expert_gemm_w8")
-    return out
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8", out)
 
 
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
@@ -516,15 +512,8 @@ def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     assert w1.dim() == 3 and w2_kmajor.dim() == 3 and w1.is_contiguous() and w2_kmajor.is_contiguous() and w1.dtype == x.dtype == w2_kmajor.dtype
     E_loc, H, M = w1.shape
     M_out = w2_kmajor.shape[1]
-    assert w2_kmajor.shape == (E_loc, M_out, H) and x.is_contiguous()
-    x = _a16(x)
-    if smap is None:
-        assert x.dim() == 3 and x.shape[0] == E_loc and x.shape[2] == M
-        R = x.shape[1]
-        xs, ldx, T, z = R * M, M, 0, None
-    else:
-        assert x.dim() == 2 and x.shape[1] == M and smap.dtype == torch.int32 and smap.numel() == E_loc * R
-        xs, ldx, T, z = 0, x.stride(0), x.shape[0], zero_row(M, x.dtype, x.device)
+    assert w2_kmajor.shape == (E_loc, M_out, H)
+    x, R, (xs, _, _, ldx), T, z = _a_rows(x, E_loc, M, smap, R, None)
     if hid is None:
         hid = torch.empty([E_loc, R, H], dtype=x.dtype, device=x.device)
     out = torch.empty([E_loc, R, M_out], dtype=x.dtype, device=x.device)
@@ -532,10 +521,7 @@ def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
                                          (b1.stride(0) if b1 is not None else 0), _ptr(hid), R * H, H, _ptr(w2_kmajor), w2_kmajor.stride(0),
                                          w2_kmajor.stride(1), _ptr(b2), (b2.stride(0) if b2 is not None else 0), _ptr(out), R * M_out, M_out,
                                          E_loc, R, M, H, M_out, _code(x), ACT_CODES[act], _stream())
-    if rc == _lib.ENOTSUP:
-        return None
-    _lib.check(rc, "tutel_amd_expert_ffn")
-    return out
+    return _unless_notsup(rc, "tutel_amd_expert_ffn", out)
 
 
 _OPT_ENV = {_lib.OPT_GEMM_IMPL: "TUTEL_AMD_GEMM_IMPL", _lib.OPT_GEMM_TILE: "TUTEL_AMD_GEMM_BIG", _lib.OPT_DECODE: "TUTEL_AMD_DECODE",
