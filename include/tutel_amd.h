@@ -287,6 +287,33 @@ int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride
                              int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                              tutel_stream_t stream);
 
+/* W8A16 for SwiGLU experts (csrc/expert_gemm_w8.hip): the gate and up products of one expert in ONE launch over FP8 weights,
+ *     D[e, r, n] = act(A[e, r, :] . W_gate[e, n, :]) * (A[e, r, :] . W_up[e, n, :])          n < H, no bias
+ * -- tutel_amd_expert_gemm_gate_up with both weight matrices streamed as e4m3 codes; the token rows are read once and the gate is never
+ * written to memory.  Numeric contract (part of the interface; it mirrors tutel_amd_expert_gemm_gate_up: the gate is rounded before
+ * the product):
+ *     gacc, uacc = sum_k A[e, r, k] * dq(code)     in fp32 by v_mfma_f32_32x32x16_{bf16,f16}, dq as in tutel_amd_expert_gemm_w8; ONE
+ *                                                  accumulator per output and matrix: no split-K, no atomics
+ *     g = round_T( act( gacc * scale_gate[e, n] ) )     one fp32 multiply with its own rounding, the activation in fp32, one rounding
+ *     u = uacc * scale_up[e, n]                         one fp32 multiply with its own rounding
+ *     D[e, r, n] = round_T( float(g) * u )              one fp32 multiply with its own rounding, then one rounding to `dtype`
+ * The image Wq_gu is tutel_amd_expert_gemm_w8's layout over N = 2 H channels in which the two matrices are interleaved by 16: within
+ * every 32-channel group g, position p < 16 is gate channel 16 g + p and position 16 + p is up channel 16 g + p
+ * (tutel_amd/experts/w8.py::interleave_gate_up, then pack: no other byte layout).  scale_gu: fp32 [E_loc, 2 H] in the same order.
+ * Rows of A and D (D is [E_loc, R, H] with element strides), slot_map, T and zero_row as in tutel_amd_expert_gemm_w8.
+ * Covered (tutel_amd_expert_gemm_w8_glu_supported(dtype, H, K) == 1: a pure function, no HIP call): bf16 / fp16, K % 64 == 0,
+ * H % 16 == 0, H >= 16; the alignment and stride conditions of tutel_amd_expert_gemm_w8 with w_stride_e >= 2 * H * K; act one of
+ * TUTEL_ACT_*; any R >= 1 (tuned for R <= 128), E_loc * R and the tile count E_loc * ceil(R / 128) * ceil(2 H / 128) below 2^31.
+ * NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange layouts, peer stores.  Anything not covered returns
+ * TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  A, Wq_gu, scale_gu and zero_row 16-byte
+ * aligned, D 8-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w8_glu_supported(int dtype, int H, int K);
+int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq_gu,
+                                 int64_t w_stride_e, const float *scale_gu, void *D, int64_t d_stride_e, int64_t d_stride_w,
+                                 int d_rows_per_w, int ldd, int E_loc, int R, int H, int K, int dtype, int act,
+                                 const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                                 tutel_stream_t stream);
+
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert
  * -- what FusedExpertsNetwork.forward computes with two batched matmuls, two bias adds and the activation

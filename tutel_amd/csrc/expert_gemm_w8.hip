@@ -28,6 +28,13 @@
 //   * R > 128 runs as several row tiles that each stream the weights again: correct, not the design point.
 //   * ragged tiles: rows past R and channel groups past N clamp their loads (to the last row / the last 32-channel group) and mask
 //     their stores; nothing is read or written outside the operands.
+//
+// SwiGLU experts (tutel_amd_expert_gemm_w8_glu): D = round_T( round_T(act(gacc * scale_gate)) * (uacc * scale_up) ), the gate and up
+// products of one launch.  The image holds both matrices, interleaved by 16 channels (experts/w8.py::interleave_gate_up): in every
+// 32-channel group positions 0 .. 15 are gate channels 16 g .. 16 g + 15 and positions 16 .. 31 the up channels of the same indices.
+// A lane's accumulator registers rg = 0, 1 are then gate channels and rg + 2 the up channels of the SAME outputs, so the gating
+// product is register against register: same K loop over 2 H image channels (w8_tile), token rows read once, the gate never written
+// to memory, no LDS and no cross-lane move in the epilogue.  One workgroup is 128 image channels = 64 output channels x 128 rows.
 #include "gemm_dev.h"  // Mma<T>, activate<ACT>
 
 #define W8_BM 128
@@ -74,9 +81,10 @@ __device__ __forceinline__ u32x4 w8_wload(__amdgpu_buffer_rsrc_t rs, int voff, i
   return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 2));
 }
 
-template <typename T, int ACT>
-__global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8Args p) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
+// One (expert, 128 rows, 128 image channels) work item; both kernels below are this function.  GLU: the image holds a SwiGLU expert's
+// gate and up channels interleaved by 16 (experts/w8.py::interleave_gate_up), p.N = 2 H image channels, and only the epilogue differs.
+template <typename T, int ACT, bool GLU>
+__device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, kg = lane >> 5;
@@ -205,6 +213,39 @@ __global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8A
     sc[rg] = *reinterpret_cast<const float4 *>(p.scale + (long long)e * p.N + n);
     bi[rg] = p.bias != nullptr ? *reinterpret_cast<const uint2 *>(p.bias + (long long)e * p.bias_stride_e + n) : make_uint2(0u, 0u);
   }
+  if constexpr (GLU) {
+    // Registers rg = 0, 1 are gate channels 16 nt + 8 rg + 4 kg + r of the expert, registers rg + 2 the up channels of the same
+    // indices (the image's interleave): the gating product is register against register in this lane.  g = act(gacc * scale_gate)
+    // rounded to T, u = uacc * scale_up, D = round_T(float(g) * u) -- tutel_amd_expert_gemm_gate_up's order; no bias
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const int m = m0 + mi * 32 + l31;
+      if (m >= p.R) continue;
+      uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 16 + kg * 4;
+#pragma unroll
+      for (int rg = 0; rg < 2; ++rg) {
+        const float sg[4] = {sc[rg].x, sc[rg].y, sc[rg].z, sc[rg].w};
+        const float su[4] = {sc[rg + 2].x, sc[rg + 2].y, sc[rg + 2].z, sc[rg + 2].w};
+        uint16_t o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float a = activate<ACT>(__fmul_rn(acc[mi][rg * 4 + r], sg[r]));
+          asm("" : "+v"(a));  // the fp32 activation exists before it is rounded
+          const T g = Elem<T>::from_f32(a);
+          const float u = __fmul_rn(acc[mi][(rg + 2) * 4 + r], su[r]);
+          float v = __fmul_rn(Elem<T>::to_f32(g), u);
+          asm("" : "+v"(v));  // and so does the product
+          const T tv = Elem<T>::from_f32(v);
+          __builtin_memcpy(&o[r], &tv, 2);
+        }
+        uint2 ov;
+        ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
+        ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
+        *reinterpret_cast<uint2 *>(drow + rg * 8) = ov;
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
     const int m = m0 + mi * 32 + l31;
@@ -236,55 +277,77 @@ __global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8A
   }
 }
 
+template <typename T, int ACT>
+__global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8Args p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
+  w8_tile<T, ACT, false>(p, smem);
+}
+
+// SwiGLU gate and up products in one launch: 128 image channels = 64 output channels x 128 rows per workgroup
+template <typename T, int ACT>
+__global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_glu_kernel(const W8Args p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
+  w8_tile<T, ACT, true>(p, smem);
+}
+
 static bool w8_dtype_ok(int dtype) { return dtype == TUTEL_BF16 || dtype == TUTEL_F16; }
 static bool w8_shape_ok(int N, int K) { return N >= 32 && N % 32 == 0 && K >= W8_BK && K % W8_BK == 0; }
 
 extern "C" int tutel_amd_expert_gemm_w8_supported(int dtype, int N, int K) { return w8_dtype_ok(dtype) && w8_shape_ok(N, K) ? 1 : 0; }
+// the gate / up image has 2 H channels: H a multiple of 16
+extern "C" int tutel_amd_expert_gemm_w8_glu_supported(int dtype, int H, int K) {
+  return w8_dtype_ok(dtype) && H >= 16 && H % 16 == 0 && w8_shape_ok(2 * H, K) ? 1 : 0;
+}
 
-static const char W8_ENTRY[] = "tutel_amd_expert_gemm_w8";
-static int w8_bad_act() { return tutel_notsup(W8_ENTRY, "the activation must be none, relu, gelu or silu"); }
+// what differs between the two entry points on the host: the names in the messages, and the image's channels per output channel
+struct W8Entry { const char *name, *bad_n, *small_image; int per_out; };
+static const W8Entry W8_PLAIN = {"tutel_amd_expert_gemm_w8", "N must be a multiple of 32", "w_stride_e is smaller than one expert's image (N * K bytes)", 1};
+static const W8Entry W8_GLU = {"tutel_amd_expert_gemm_w8_glu", "H must be a multiple of 16",
+                               "w_stride_e is smaller than one expert's image (2 * H * K bytes)", 2};
 
 // (the activations last to first: the compiler instantiates the list's kernels from its end, and they keep their order in the code object)
-template <typename T> static int w8_launch(const W8Args &a, int act, unsigned grid, hipStream_t st) {
+template <typename T, bool GLU> static int w8_launch(const W8Entry &en, const W8Args &a, int act, unsigned grid, hipStream_t st) {
   return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
       act,
       [&](auto ac) {
-        hipLaunchKernelGGL((expert_gemm_w8_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W8_THREADS), 0, st, a);
-        TUTEL_CHECK_LAUNCH(W8_ENTRY);
+        if constexpr (GLU) hipLaunchKernelGGL((expert_gemm_w8_glu_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W8_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((expert_gemm_w8_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W8_THREADS), 0, st, a);
+        TUTEL_CHECK_LAUNCH(en.name);
         return 0;
       },
-      w8_bad_act);
+      [&] { return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu"); });
 }
 
-extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
-                                        int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
-                                        int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
-                                        int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T,
-                                        const void *zero_row, tutel_stream_t stream) {
-  // every check stands in front of the first HIP call
-  TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "tutel_amd_expert_gemm_w8: bad sizes E_loc=%d R=%d N=%d K=%d", E_loc, R, N, K);
-  if (!w8_dtype_ok(dtype)) return tutel_notsup(W8_ENTRY, "the activations must be bf16 or fp16");
-  if (K % W8_BK != 0) return tutel_notsup(W8_ENTRY, "K must be a multiple of 64");
-  if (N % 32 != 0) return tutel_notsup(W8_ENTRY, "N must be a multiple of 32");
+// Both entry points: N output channels per row of D, en.per_out * N image channels.  Every check stands in front of the first HIP call
+template <bool GLU>
+static int w8_run(const W8Entry &en, const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
+                  int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D, int64_t d_stride_e,
+                  int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
+                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row, tutel_stream_t stream) {
+  TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "%s: bad sizes E_loc=%d R=%d %s=%d K=%d", en.name, E_loc, R, GLU ? "H" : "N", N, K);
+  if (!w8_dtype_ok(dtype)) return tutel_notsup(en.name, "the activations must be bf16 or fp16");
+  if (K % W8_BK != 0) return tutel_notsup(en.name, "K must be a multiple of 64");
+  if (N % (32 / en.per_out) != 0) return tutel_notsup(en.name, en.bad_n);
   if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
-    return w8_bad_act();
-  if (row_counts != nullptr) return tutel_notsup(W8_ENTRY, "row_counts (megablocks) are not covered");
+    return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu");
+  if (row_counts != nullptr) return tutel_notsup(en.name, "row_counts (megablocks) are not covered");
   if ((slot_map == nullptr && (a_rows_per_w < R || a_stride_w != 0)) || d_rows_per_w < R || d_stride_w != 0)
-    return tutel_notsup(W8_ENTRY, "the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
+    return tutel_notsup(en.name, "the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
   if (lda % 8 != 0 || ldd % 4 != 0 || a_stride_e % 8 != 0 || d_stride_e % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0)
-    return tutel_notsup(W8_ENTRY, "rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
-  if (w_stride_e < (int64_t)N * K) return tutel_notsup(W8_ENTRY, "w_stride_e is smaller than one expert's image (N * K bytes)");
-  const long long ntm = (R + W8_BM - 1) / W8_BM, ntn = (N + W8_BN - 1) / W8_BN;
-  if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL)
-    return tutel_notsup(W8_ENTRY, "E_loc * R and the tile count must stay below 2^31");
+    return tutel_notsup(en.name, "rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
+  const long long NI = (long long)en.per_out * N;   // image channels
+  if (w_stride_e < NI * K) return tutel_notsup(en.name, en.small_image);
+  const long long ntm = (R + W8_BM - 1) / W8_BM, ntn = (NI + W8_BN - 1) / W8_BN;
+  if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL || NI > 0x7fffffffLL)
+    return tutel_notsup(en.name, "E_loc * R and the tile count must stay below 2^31");
   if (E_loc == 0 || R == 0) return 0;
-  TUTEL_REQUIRE(A && Wq && scale && D, "tutel_amd_expert_gemm_w8: null pointer");
+  TUTEL_REQUIRE(A && Wq && scale && D, "%s: null pointer", en.name);
   TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)D % 8) == 0 &&
                     ((uintptr_t)bias % 8) == 0,
-                "tutel_amd_expert_gemm_w8: A, Wq and scale must be 16-byte aligned, D and bias 8-byte aligned");
+                "%s: A, Wq and scale must be 16-byte aligned, D and bias 8-byte aligned", en.name);
   if (slot_map != nullptr)
     TUTEL_REQUIRE(T >= 1 && zero_row != nullptr && ((uintptr_t)zero_row % 16) == 0,
-                  "tutel_amd_expert_gemm_w8: a slot map needs T >= 1 and a 16-byte aligned zero row");
+                  "%s: a slot map needs T >= 1 and a 16-byte aligned zero row", en.name);
 
   W8Args a;
   a.A = (const unsigned char *)A; a.a_stride_e = a_stride_e; a.lda = lda;
@@ -292,10 +355,30 @@ extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64
   a.scale = scale;
   a.bias = (const uint16_t *)bias; a.bias_stride_e = bias_stride_e;
   a.D = (uint16_t *)D; a.d_stride_e = d_stride_e; a.ldd = ldd;
-  a.R = R; a.N = N; a.K = K; a.ntm = (int)ntm; a.ntn = (int)ntn;
+  a.R = R; a.N = (int)NI; a.K = K; a.ntm = (int)ntm; a.ntn = (int)ntn;
   a.slot_map = slot_map; a.T = T; a.zero_row = (const unsigned char *)zero_row;
   hipStream_t st = (hipStream_t)stream;
-  StageScope stage(act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  StageScope stage(GLU || act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
   const unsigned grid = (unsigned)((long long)E_loc * ntm * ntn);
-  return dtype == TUTEL_BF16 ? w8_launch<bf16_t>(a, act, grid, st) : w8_launch<f16_t>(a, act, grid, st);
+  return dtype == TUTEL_BF16 ? w8_launch<bf16_t, GLU>(en, a, act, grid, st) : w8_launch<f16_t, GLU>(en, a, act, grid, st);
 }
+
+extern "C" int tutel_amd_expert_gemm_w8(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
+                                        int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
+                                        int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                                        int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T,
+                                        const void *zero_row, tutel_stream_t stream) {
+  return w8_run<false>(W8_PLAIN, A, a_stride_e, a_stride_w, a_rows_per_w, lda, Wq, w_stride_e, scale, bias, bias_stride_e, D, d_stride_e,
+                       d_stride_w, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, row_counts, slot_map, T, zero_row, stream);
+}
+
+// SwiGLU gate and up products of FP8 weights in one launch (the contract: include/tutel_amd.h).  No bias: these experts have none
+extern "C" int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
+                                            const void *Wq_gu, int64_t w_stride_e, const float *scale_gu, void *D, int64_t d_stride_e,
+                                            int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int H, int K, int dtype, int act,
+                                            const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                                            tutel_stream_t stream) {
+  return w8_run<true>(W8_GLU, A, a_stride_e, a_stride_w, a_rows_per_w, lda, Wq_gu, w_stride_e, scale_gu, nullptr, 0, D, d_stride_e,
+                      d_stride_w, d_rows_per_w, ldd, E_loc, R, H, K, dtype, act, row_counts, slot_map, T, zero_row, stream);
+}
+

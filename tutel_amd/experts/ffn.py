@@ -229,9 +229,9 @@ def _params(net):
     return net.batched_fc1_w, net.batched_fc2_w, net.batched_fc1_bias, net.batched_fc2_bias
 
 
-def _dtypes(reason, allowed):
+def _dtypes(reason, allowed, params=_params):
     """the input in one of the `allowed` dtypes and every parameter in the input's"""
-    return _rung(reason, lambda net, x, ctx, mb: x.dtype not in allowed or any(p is not None and p.dtype != x.dtype for p in _params(net)))
+    return _rung(reason, lambda net, x, ctx, mb: x.dtype not in allowed or any(p is not None and p.dtype != x.dtype for p in params(net)))
 
 
 def _shape(reason, covers):
@@ -243,13 +243,20 @@ def _shape(reason, covers):
 _SKIP = _rung("SKIP_EXPERT is set", lambda net, x, ctx, mb: net.skip_expert)
 _DEVICE = _rung("the input is not on the HIP device", lambda net, x, ctx, mb: not x.is_cuda)
 _AUTOCAST = _rung("autocast is on", lambda net, x, ctx, mb: torch.is_autocast_enabled())
-_GATHERED = _rung("gathered-weight modes (sharded experts, adaptive_r = 0) are not covered",
+GATHERED_REASON = "gathered-weight modes (sharded experts, adaptive_r = 0) are not covered"
+_GATHERED = _rung(GATHERED_REASON,
                   lambda net, x, ctx, mb: getattr(ctx, "sharded_count", 1) != 1 or getattr(ctx, "adaptive_degree", 1) == 0)
 _MEGABLOCKS = _rung("megablocks row counts are not covered",   # mb: the value this forward will run with, where ctx does not hold it yet
                     lambda net, x, ctx, mb: (getattr(ctx, "megablocks_size", 0) if mb is None else mb) != 0)
 _AUTOGRAD_F32 = _rung("autograd is live (training stays on ATen)", lambda net, x, ctx, mb: not net._no_autograd(x))
 _AUTOGRAD_W8 = _rung("autograd is live (FP8 weights are inference only)", lambda net, x, ctx, mb: not net._no_autograd(x))
 _ACTIVATION = _rung("the activation is not one of the fused epilogues", lambda net, x, ctx, mb: net.fused_activation() is None)
+# the FP8 switch's own rungs, shared with SwiGLU experts (experts/llama_ffn.py walks a ladder of these)
+_SWITCH_W8 = _rung("fp8_weights is off (TUTEL_AMD_FP8_WEIGHTS)", lambda net, x, ctx, mb: not net.fp8_weights)
+_TRAINING_W8 = _rung("the module is in training mode (FP8 weights are inference only)", lambda net, x, ctx, mb: net.training)
+W8_DTYPE_REASON = "the input is not bf16 / fp16 in the experts' own dtype"
+# (quantising inside a capture would allocate the images in the graph's pool and redo the work at every replay)
+W8_CAPTURE_REASON = "the quantised weights are not cached yet: run one eager forward before capturing a graph"
 
 
 def _inference_params(net):
@@ -284,15 +291,12 @@ F32 = Engine(
 # bf16 / fp16 experts in inference reading FP8 weights
 W8 = Engine(
     ran="_fp8_weights_ran", entry="tutel_amd_expert_gemm_w8", run=_run_w8,
-    ladder=(_rung("fp8_weights is off (TUTEL_AMD_FP8_WEIGHTS)", lambda net, x, ctx, mb: not net.fp8_weights),
-            _SKIP, _DEVICE, _AUTOGRAD_W8,
-            _rung("the module is in training mode (FP8 weights are inference only)", lambda net, x, ctx, mb: net.training),
-            _AUTOCAST, _dtypes("the input is not bf16 / fp16 in the experts' own dtype", (torch.bfloat16, torch.float16)),
+    ladder=(_SWITCH_W8, _SKIP, _DEVICE, _AUTOGRAD_W8, _TRAINING_W8,
+            _AUTOCAST, _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16)),
             _GATHERED, _MEGABLOCKS, _ACTIVATION,
             _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
                    lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K)),
-            # (quantising inside a capture would allocate the images in the graph's pool and redo the work at every replay)
-            _rung("the quantised weights are not cached yet: run one eager forward before capturing a graph",
+            _rung(W8_CAPTURE_REASON,
                   lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not (
                       net._kmajor.holds("fc1.w8", net.batched_fc1_w, "w8") and net._kmajor.holds("fc2.w8", net.batched_fc2_w, "w8")))))
 ENGINES = (W8, F32)   # the order FusedExpertsNetwork.forward tries them in; their dtype checks exclude each other

@@ -11,6 +11,10 @@ Forward:
   * bf16 / fp16, no autograd, unsharded, recognised activation -> three launches of the MFMA
     grouped GEMM (tutel_amd_expert_gemm): the activation is fused into the W_fc1 launch and the
     gating product into the W_fc2 launch (its epilogue multiplies by the stored act(x @ W_fc1));
+  * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): the same experts in inference read e4m3 codes with
+    one fp32 scale per (expert, output channel) -- TWO launches: the gate and up products in one (tutel_amd_expert_gemm_w8_glu, both
+    weight matrices in one interleaved image, the gate never written to memory), then tutel_amd_expert_gemm_w8 on W_fc3; the images
+    are derived copies in the KMajorCache (experts/w8.py).  w8_refusal names why a forward keeps its 16-bit weights;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
 the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.
@@ -18,7 +22,28 @@ the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel),
 import torch
 
 from .. import net, ops
+from . import ffn as _ffn
+from . import w8
 from .ffn import KMajorCache, classify_activation, _PREPACK
+
+
+def _w8_params(net):
+    return net.W_fc1, net.W_fc2, net.W_fc3
+
+
+# why a forward of SwiGLU experts keeps its 16-bit weights: the shared rungs of experts/ffn.py, the switch first; the ORDER is behaviour
+W8_LADDER = (
+    _ffn._SWITCH_W8, _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST,
+    _ffn._dtypes(_ffn.W8_DTYPE_REASON, (torch.bfloat16, torch.float16), _w8_params),
+    _ffn._rung(_ffn.GATHERED_REASON,   # (these experts keep their own shard count: their parameters are stored flat and gathered)
+               lambda net, x, ctx, mb: net.sharded_count > 1 or _ffn._GATHERED(net, x, ctx, mb) is not None),
+    _ffn._ACTIVATION,
+    # fc3's K is H: stricter than the gate / up kernel's H % 16 == 0
+    _ffn._rung("the shape is not covered (M a multiple of 64, H a multiple of 64)",
+               lambda net, x, ctx, mb: not (ops.gemm_w8_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
+                                            and ops.gemm_w8_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1]))),
+    _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w8_cached()),
+)
 
 
 class LlamaFFNNetwork(torch.nn.Module):
@@ -44,6 +69,8 @@ class LlamaFFNNetwork(torch.nn.Module):
         self.activation_fn = activation_fn
         self._act_cache = {}
         self._kmajor = KMajorCache()
+        # FP8 (e4m3) weights in inference, W8A16; the 16-bit parameters stay as they are
+        self.fp8_weights = _ffn._FP8_WEIGHTS
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -89,6 +116,59 @@ class LlamaFFNNetwork(torch.nn.Module):
         h = ops.expert_gemm(x, w2, None, km, mul=g)
         return ops.expert_gemm(h, w3, None, km)
 
+    # -- FP8 weights (W8A16) --------------------------------------------------------------------
+    def _no_autograd(self, x):
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+
+    def w8_refusal(self, x, ctx):
+        """why this forward keeps its 16-bit weights (a string: the first failing check of W8_LADDER), or None when it reads FP8"""
+        reasons = (check(self, x, ctx, None) for check in W8_LADDER)
+        return next((why for why in reasons if why is not None), None)
+
+    def _w8_views(self):
+        return (self.W_fc1.view(self.W_fc1_full_shape), self.W_fc2.view(self.W_fc2_full_shape), self.W_fc3.view(self.W_fc3_full_shape))
+
+    def _w8_gate_up_key(self, w2):
+        """the gate / up entry is derived from BOTH parameters: W_fc2's key rides in the entry's `what`, W_fc1's is the entry's own"""
+        return ("w8.glu", KMajorCache._key(w2))
+
+    def w8_cached(self):
+        w1, w2, w3 = self._w8_views()
+        return self._kmajor.holds("fc12.w8", w1, self._w8_gate_up_key(w2)) and self._kmajor.holds("fc3.w8", w3, "w8")
+
+    def w8_params(self):
+        """((image_gu, scale_gu), (image3, scale3)): the interleaved gate / up image of (W_fc1, W_fc2) and the image of W_fc3, all
+        read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes (KMajorCache's rule)"""
+        w1, w2, w3 = self._w8_views()
+        gu = self._kmajor.derived("fc12.w8", w1, self._w8_gate_up_key(w2), lambda w: w8.prepare_gate_up(w, w2.detach(), False))
+        p3 = self._kmajor.derived("fc3.w8", w3, "w8", lambda w: w8.prepare(w, False))
+        return gu, p3
+
+    def forward_fused_w8(self, x):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M] in two launches: gate and up over one FP8 image, then W_fc3"""
+        (igu, sgu), (i3, s3) = self.w8_params()
+        _, M, H = self.W_fc1_full_shape
+        h = ops.expert_gemm_w8_glu(x, igu, sgu, H, M, act=self.fused_activation())
+        y = ops.expert_gemm_w8(h, i3, s3, None, M, H) if h is not None else None
+        if y is None:   # the ladder asked the library's own coverage queries: a refusal here is a bug, never a quiet forward elsewhere
+            from .. import _lib
+            raise _lib.TutelAmdError("the FP8 expert GEMMs refused a shape their own queries admit: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
+    def _forward_if_w8(self, x, ctx):
+        """forward()'s FP8 step: the output, or None where the switch is off or a check refuses -- the reason is kept for the caller"""
+        if not self.fp8_weights:
+            return None
+        why = self.w8_refusal(x, ctx)
+        if why is None and not (x.dim() == 3 and x.size(0) == self.W_fc1_full_shape[0] and x.size(2) == self.W_fc1_full_shape[1]):
+            why = "the input is not [E_loc, R, M]"
+        try:
+            setattr(ctx, "_fp8_weights_ran", True if why is None else why)
+        except AttributeError:
+            pass
+        return self.forward_fused_w8(x.contiguous()) if why is None else None
+
     def invalidate_prepacked(self):
         self._kmajor.invalidate()
 
@@ -106,6 +186,9 @@ class LlamaFFNNetwork(torch.nn.Module):
 
     # -- reference-equivalent ATen path -----------------------------------------------------
     def forward(self, x, ctx):
+        y = self._forward_if_w8(x, ctx)
+        if y is not None:
+            return y
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous())
         w1 = self._get_gathered_param(self.W_fc1, self.W_fc1_full_shape, ctx.group)

@@ -13,6 +13,9 @@ code.  Everything is elementwise or a max-reduction in fp32: deterministic.
 The image is the kernel's own layout (include/tutel_amd.h): per expert [N / 32][K / 32][64 lanes][16 bytes], byte b of lane l of
 block (g, t) = the code of channel 32 g + (l & 31) at k = 32 t + 16 (b >> 3) + 8 (l >> 5) + (b & 7); N and K padded up to multiples of
 32 with code 0x00.  pack / unpack are pure index operations.
+
+A SwiGLU expert's gate and up matrices share ONE image of 2 H channels (tutel_amd_expert_gemm_w8_glu): each is quantised on its own,
+the channels are interleaved by 16 (interleave_gate_up) and the result goes through the same pack.
 """
 import torch
 
@@ -75,3 +78,42 @@ def prepare(w, w_kmajor):
     """quantise and lay out one parameter: (image, scale) as the kernel reads them"""
     q, scale = quantize_e4m3(w, w_kmajor)
     return pack(q), scale.contiguous()
+
+
+# ---- SwiGLU experts: gate and up in one image (tutel_amd_expert_gemm_w8_glu) ------------------------------------------------------------
+# Register 4 rg + r of a lane's 32 x 32 accumulator is image channel 32 nt + 8 rg + 4 kg + r (kg = lane >> 5).  With the two matrices
+# interleaved by GLU_GROUP channels -- in every 32-channel group, position p < 16 gate channel 16 g + p, position 16 + p up channel
+# 16 g + p -- registers rg = 0, 1 of a lane are gate channels 16 g + 8 rg + 4 kg + r and registers rg + 2 the up channels of the same
+# indices: the gating product is register against register.  Only the channel order changes; the bytes below it are pack's.
+GLU_GROUP = 16
+
+
+def interleave_gate_up(gate, up):
+    """gate, up [E, H, ...] (codes [E, H, K] or scales [E, H]) -> [E, 2 H, ...]: blocks of 16 channels, gate then up; H % 16 == 0"""
+    assert gate.shape == up.shape and gate.dtype == up.dtype and gate.dim() >= 2
+    if gate.dtype == torch.float8_e4m3fn:   # codes move as bytes
+        return interleave_gate_up(gate.view(torch.uint8), up.view(torch.uint8)).view(torch.float8_e4m3fn)
+    E, H = gate.shape[:2]
+    assert H % GLU_GROUP == 0, "the gate / up image needs H % 16 == 0"
+    rest = tuple(gate.shape[2:])
+    both = torch.stack([gate.reshape(E, H // GLU_GROUP, GLU_GROUP, *rest), up.reshape(E, H // GLU_GROUP, GLU_GROUP, *rest)], dim=2)
+    return both.reshape(E, 2 * H, *rest)
+
+
+def deinterleave_gate_up(both):
+    """the inverse of interleave_gate_up: [E, 2 H, ...] -> (gate, up) [E, H, ...]"""
+    if both.dtype == torch.float8_e4m3fn:
+        return tuple(t.view(torch.float8_e4m3fn) for t in deinterleave_gate_up(both.view(torch.uint8)))
+    E, N = both.shape[:2]
+    assert N % (2 * GLU_GROUP) == 0
+    rest = tuple(both.shape[2:])
+    b = both.reshape(E, N // (2 * GLU_GROUP), 2, GLU_GROUP, *rest)
+    return b[:, :, 0].reshape(E, N // 2, *rest), b[:, :, 1].reshape(E, N // 2, *rest)
+
+
+def prepare_gate_up(w_gate, w_up, w_kmajor):
+    """quantise a SwiGLU expert's gate and up parameters, each on its own (its own per-channel scales), and lay them out as ONE image:
+    (pack(interleave(q_gate, q_up)), interleave(scale_gate, scale_up) [E, 2 H] fp32)"""
+    qg, sg = quantize_e4m3(w_gate, w_kmajor)
+    qu, su = quantize_e4m3(w_up, w_kmajor)
+    return pack(interleave_gate_up(qg, qu)), interleave_gate_up(sg, su).contiguous()

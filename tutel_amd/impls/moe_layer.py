@@ -348,6 +348,8 @@ class MOELayer(torch.nn.Module):
                                                                      alignment, gate_w=gate_w, plan=plan)
             self._dropless_packed_ran = True if res is not None else (why or "the packed layout does not cover this shape")
             if res is not None:
+                if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
+                    self._fp8_weights_ran = "the packed dropless forward has no FP8 GEMM"   # it keeps its 16-bit one-call path
                 y, l_aux, cnt, cap = res
                 self.megablocks_size = megablocks_size
                 self.dispatch_count = cnt
@@ -443,6 +445,9 @@ class MOELayer(torch.nn.Module):
             for engine in _ffn.ENGINES:
                 if engine.on(self.experts):
                     setattr(self, engine.ran, self.experts.engine_refusal(engine, x, self, megablocks_size))
+        elif isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
+            # SwiGLU experts: the same report (LlamaFFNNetwork.forward sets True, or a later reason)
+            self._fp8_weights_ran = self.experts.w8_refusal(x, self)
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega

@@ -502,6 +502,38 @@ def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=Non
     return _unless_notsup(rc, "tutel_amd_expert_gemm_w8", out)
 
 
+def gemm_w8_glu_supported(dtype, H, K):
+    """shapes the W8A16 gate / up GEMM (tutel_amd_expert_gemm_w8_glu) takes: bf16 / fp16 activations, K % 64 == 0, H % 16 == 0 -- the
+    library's own answer"""
+    if dtype not in _DT:
+        return False
+    return bool(_lib.lib().tutel_amd_expert_gemm_w8_glu_supported(_DT[dtype], int(H), int(K)))
+
+
+def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None, out=None, row_counts=None):
+    """W8A16 gate and up products of a SwiGLU expert in ONE launch: D[e,r,n] = round(round(act(gacc * scale_gate[e,n])) * (uacc *
+    scale_up[e,n])), gacc / uacc the fp32 sums over k of a[e,r,k] times the exact values of the gate / up e4m3 codes (the contract of
+    include/tutel_amd.h; expert_gemm_gate_up over FP8 weights).
+
+    a: [E_loc, R, K] contiguous bf16 / fp16, or -- with slot_map [E_loc * R] -- the token array [T, K] whose rows are gathered.  image,
+    scale: experts/w8.py::prepare_gate_up's uint8 image of the interleaved [E_loc, 2 H, K] codes and its [E_loc, 2 H] fp32 scales.
+    -> [E_loc, R, H].  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, image, scale, out, slot_map, row_counts)
+    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
+    E_loc = image.shape[0]
+    assert scale.shape == (E_loc, 2 * H) and image.numel() % max(E_loc, 1) == 0
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
+    if out is None:
+        out = torch.empty([E_loc, R, H], dtype=a.dtype, device=a.device)
+    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, H)
+    rc = _lib.lib().tutel_amd_expert_gemm_w8_glu(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        _ptr(image), image.numel() // max(E_loc, 1), _ptr(scale),
+        _ptr(out), R * H, 0, max(R, 1), H,
+        E_loc, R, H, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu", out)
+
+
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     """fc1 -> activation -> fc2 of every local expert in ONE persistent launch (tutel_amd_expert_ffn, csrc/expert_ffn.hip):
     x [E_loc, R, M] -- or the token array [T, M] with smap [E_loc * R] (fast_encode fused) -- w1 [E_loc, H, M], w2_kmajor
