@@ -314,6 +314,37 @@ int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_st
                                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                                  tutel_stream_t stream);
 
+/* The two W8A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w8.hip): the experts'
+ * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value
+ * and can be captured in a HIP graph.
+ *     expert e owns packed rows [offsets[e], offsets[e + 1]);  D[r, :] for each of them is what tutel_amd_expert_gemm_w8 /
+ *     tutel_amd_expert_gemm_w8_glu writes for the same input row and expert, BIT FOR BIT, wherever the row lies: the same kernel body
+ *     over a row window, one fp32 accumulator over all of K in the same order, the same epilogue.
+ * Rows: row r of A is A + r * lda elements, or, with a_rows (the packed slot map), token a_rows[r] % T of the token array A [T, lda]
+ * and zero_row (>= K zeros) for -1 -- tutel_amd_expert_gemm_packed's addressing.  D is [rows_bound, N] ([rows_bound, H] for the GLU
+ * form) with row stride ldd.  Every row in [0, offsets[E]) is written; rows at and past offsets[E] are neither read nor written.
+ * Wq / w_stride_e / scale / bias / bias_stride_e (Wq_gu / scale_gu), the image layout, the interleave of the GLU image and the
+ * epilogue arithmetic: exactly those of the padded entry points.  offsets [E + 1], tiles [2 * tiles_bound], ntiles [1] from
+ * tutel_amd_packed_layout with the same tiles_bound.
+ * Grid: tiles_bound * 2 * ceil(channels / 128) work items (rounded up to a multiple of 16 workgroups), sized on the host by the bound
+ * alone (channels = N, or 2 H); a 256-row table tile is two 128-row halves.  A workgroup whose table tile is not live (>= *ntiles) or
+ * whose half starts at or past the expert's end returns at once.  Rows of a 128-row window past offsets[e + 1] are the next expert's:
+ * their loads clamp to the window's last live row, their stores are masked and their 32-row groups skip the matrix instructions.  An
+ * expert above 128 rows streams its weights once per half (both halves of a table tile are work items of one XCD, which runs the
+ * first halves of its table tiles, then the second halves).
+ * Covered: the padded entry points' conditions -- bf16 / fp16, K % 64 == 0, N % 32 == 0 (H % 16 == 0), lda % 8 == 0, ldd and
+ * bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= one image, act one of TUTEL_ACT_*, the work item count below 2^31.  Anything
+ * else returns TUTEL_AMD_ENOTSUP with its reason and nothing enqueued; E == 0, rows_bound == 0 or tiles_bound == 0 is a successful
+ * no-op.  A, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w8_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq,
+                                    int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D, int ldd,
+                                    int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
+                                    const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+int tutel_amd_expert_gemm_w8_glu_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq_gu,
+                                        int64_t w_stride_e, const float *scale_gu, void *D, int ldd, int E, int rows_bound, int H,
+                                        int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
+                                        const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert
  * -- what FusedExpertsNetwork.forward computes with two batched matmuls, two bias adds and the activation
@@ -646,6 +677,8 @@ int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, 
                                  void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
                                  const int32_t *tiles, const int32_t *ntiles, const int32_t *capacity, int tiles_bound,
                                  tutel_stream_t stream);
+/* (FP8 expert weights over the same tables: tutel_amd_expert_gemm_w8_packed / tutel_amd_expert_gemm_w8_glu_packed, declared with
+ * the W8A16 contract above.) */
 /* tutel_amd_expert_wgrad_packed: the weight gradient D[e] = A[rows(e)]^T . B[rows(e)] -> [E, N_a, N_b] in dtype, rows(e) =
  * [offsets[e], offsets[e+1]), fp32 accumulation in a fixed order (deterministic, no atomics), one rounding.  A [*, N_a] row r at
  * A + r*lda, B [*, N_b] row r at B + r*ldb; gather = 1 (A) or 2 (B): that operand is the token array [T, *] read through

@@ -112,6 +112,8 @@ SIGNATURES.update({
     "tutel_amd_moe_forward_packed_glu": (_i, [_vp, ctypes.POINTER(MoeArgs), ctypes.POINTER(PackedArgs), _vp, _vp]),
     "tutel_amd_packed_layout": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 6),
     "tutel_amd_expert_gemm_packed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp] + [_i] * 7 + [_vp] * 4 + [_i, _vp]),
+    "tutel_amd_expert_gemm_w8_packed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
+    "tutel_amd_expert_gemm_w8_glu_packed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
     "tutel_amd_expert_wgrad_packed": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "tutel_amd_expert_bgrad_packed": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "tutel_amd_expert_wgrad_packed_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),

@@ -83,19 +83,21 @@ __device__ __forceinline__ u32x4 w8_wload(__amdgpu_buffer_rsrc_t rs, int voff, i
 
 // One (expert, 128 rows, 128 image channels) work item; both kernels below are this function.  GLU: the image holds a SwiGLU expert's
 // gate and up channels interleaved by 16 (experts/w8.py::interleave_gate_up), p.N = 2 H image channels, and only the epilogue differs.
+//
+// The work item is a ROW WINDOW: expert e (its weights, scale and bias), rows [m0, min(m0 + 128, rend)) and channel tile tn.  Rows are
+// numbered as the caller's layout numbers them -- within the expert's bucket for the padded kernels (row r of A at e * a_stride_e +
+// r * lda, its slot at slot0 + r with slot0 = e * R), absolute packed rows for the packed ones (a_stride_e = d_stride_e = 0, slot0 = 0,
+// rend = offsets[e + 1]: the rows from rend on are the NEXT expert's and are neither read nor written).
 template <typename T, int ACT, bool GLU>
-__device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
+__device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem, const int e, const int tn, const int m0, const int rend,
+                                        const long long slot0) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, kg = lane >> 5;
-  // the channel tiles of one (expert, row tile) are consecutive work items: on ONE XCD, so that its L2 fetches the tile's token rows
-  // once (placed round-robin, the eight XCDs each fetched them: 1.6 x the algorithmic bytes, measured with FETCH_SIZE)
-  const int b = xcd_work_item((int)gridDim.x);
-  const int tn = b % p.ntn, tm = (b / p.ntn) % p.ntm, e = b / (p.ntn * p.ntm);
-  const int m0 = tm * W8_BM, n0 = tn * W8_BN;
+  const int n0 = tn * W8_BN;
   const int nk = p.K / W8_BK;
   const int NT = p.N >> 5, KT32 = p.K >> 5;
-  const int nmi = min(4, (p.R - m0 + 31) >> 5);  // live 32-row groups of this tile
+  const int nmi = min(4, (rend - m0 + 31) >> 5);  // live 32-row groups of this tile
 
   // ---- token rows: thread `tid` moves chunk (tid & 7) of rows 32 i + (tid >> 3), i < 4, of every K-tile -------------------------------
   const unsigned char *rowp[4];
@@ -106,12 +108,12 @@ __device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
     for (int i = 0; i < 4; ++i) slot[i] = 0;
     if (p.slot_map != nullptr) {  // the slots first, so that their loads are in flight together
 #pragma unroll
-      for (int i = 0; i < 4; ++i) slot[i] = p.slot_map[(long long)e * p.R + min(m0 + 32 * i + (tid >> 3), p.R - 1)];
+      for (int i = 0; i < 4; ++i) slot[i] = p.slot_map[slot0 + min(m0 + 32 * i + (tid >> 3), rend - 1)];
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = 32 * i + (tid >> 3), c = tid & 7;
-      const int gr = min(m0 + r, p.R - 1);
+      const int gr = min(m0 + r, rend - 1);
       const unsigned char *row;
       if (p.slot_map != nullptr) row = slot[i] < 0 ? p.zero_row : p.A + (long long)(slot[i] % p.T) * p.lda * 2;
       else row = p.A + ((long long)e * p.a_stride_e + (long long)gr * p.lda) * 2;
@@ -220,7 +222,7 @@ __device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
       const int m = m0 + mi * 32 + l31;
-      if (m >= p.R) continue;
+      if (m >= rend) continue;
       uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 16 + kg * 4;
 #pragma unroll
       for (int rg = 0; rg < 2; ++rg) {
@@ -249,7 +251,7 @@ __device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
     const int m = m0 + mi * 32 + l31;
-    if (m >= p.R) continue;
+    if (m >= rend) continue;
     uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 32 + kg * 4;
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
@@ -277,17 +279,63 @@ __device__ __forceinline__ void w8_tile(const W8Args &p, unsigned char *smem) {
   }
 }
 
+// The padded window: (expert, row tile tm of the bucket [E_loc, R, *], channel tile).  The channel tiles of one (expert, row tile) are
+// consecutive work items: on ONE XCD, so that its L2 fetches the tile's token rows once (placed round-robin, the eight XCDs each
+// fetched them: 1.6 x the algorithmic bytes, measured with FETCH_SIZE)
+template <typename T, int ACT, bool GLU>
+__device__ __forceinline__ void w8_padded(const W8Args &p, unsigned char *smem) {
+  const int b = xcd_work_item((int)gridDim.x);
+  const int tn = b % p.ntn, tm = (b / p.ntn) % p.ntm, e = b / (p.ntn * p.ntm);
+  w8_tile<T, ACT, GLU>(p, smem, e, tn, tm * W8_BM, p.R, (long long)e * p.R);
+}
+
 template <typename T, int ACT>
 __global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_kernel(const W8Args p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
-  w8_tile<T, ACT, false>(p, smem);
+  w8_padded<T, ACT, false>(p, smem);
 }
 
 // SwiGLU gate and up products in one launch: 128 image channels = 64 output channels x 128 rows per workgroup
 template <typename T, int ACT>
 __global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_glu_kernel(const W8Args p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
-  w8_tile<T, ACT, true>(p, smem);
+  w8_padded<T, ACT, true>(p, smem);
+}
+
+// ---- the packed dropless layout (dropless.hip: tutel_amd_packed_layout) -------------------------------------------------------------------
+// The device tables give the windows: table tile t is rows [tiles[2t+1], +256) of expert tiles[2t], clipped by offsets[e + 1]; a
+// 256-row table tile is two 128-row halves of this kernel.  A work item is (table tile, channel tile, half); the grid is the host's
+// bound, tiles_bound x 2 x ntn of them (rounded up to a multiple of 16: every XCD gets the same number of blocks), the live ones belong
+// to the first *ntiles table tiles.
+//
+// Order.  The (table tile, channel tile) pairs, channel tile fastest, are cut into eight contiguous chunks, one per XCD (the channel
+// tiles of a table tile on ONE XCD: its L2 fetches the token rows once, as above); the blocks of an XCD run the FIRST halves of its chunk,
+// then the SECOND halves.  So the two halves of a table tile are work items of the same XCD, and the halves that are not live -- every
+// second half when no expert is above 128 rows -- sit at the end of the XCD's queue, where they return at once.  Measured
+// (tools/packed_w8_bench.py): with the halves as neighbouring work items instead, live and dead blocks alternate in the
+// dispatch order and a launch of 64 x 128 rows took 148 us against the padded kernel's 85 us for the same FETCH_SIZE.
+// live_map: the chunks are cut from the LIVE pairs (*ntiles x ntn, uniform per launch: one scalar load), so the live work is spread over
+// all eight XCDs; without it they are cut from the bound and the live tiles, which sit at the front of the table, land on the first XCDs.
+// A block returns in front of every barrier when its table tile is not live or its half starts at or past the expert's end.
+struct W8Tables { const int32_t *off, *tiles, *ntiles; int tiles_bound, live_map; };
+
+template <typename T, int ACT, bool GLU>
+__global__ __launch_bounds__(W8_THREADS, 2) void expert_gemm_w8_packed_kernel(const W8Args p, const W8Tables t) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W8_STAGE];
+  const int live = min(__builtin_amdgcn_readfirstlane(*t.ntiles), t.tiles_bound);
+  const int pairs = (t.live_map ? live : t.tiles_bound) * p.ntn;   // <= tiles_bound * ntn: the host sized the grid for it
+  const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3;
+  const int q = pairs >> 3, r = pairs & 7;
+  const int len = q + (xcd < r ? 1 : 0), start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  if (pos >= 2 * len) return;
+  const int half = pos >= len ? 1 : 0, it = start + pos - half * len;
+  const int tn = it % p.ntn, ti = it / p.ntn;
+  if (ti >= live) return;
+  const int e = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti]);
+  const int m0 = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti + 1]) + half * W8_BM;
+  const int rend = __builtin_amdgcn_readfirstlane(t.off[e + 1]);
+  if (m0 >= rend) return;
+  w8_tile<T, ACT, GLU>(p, smem, e, tn, m0, rend, 0);
 }
 
 static bool w8_dtype_ok(int dtype) { return dtype == TUTEL_BF16 || dtype == TUTEL_F16; }
@@ -316,6 +364,78 @@ template <typename T, bool GLU> static int w8_launch(const W8Entry &en, const W8
         return 0;
       },
       [&] { return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu"); });
+}
+
+static const W8Entry W8_PLAIN_PK = {"tutel_amd_expert_gemm_w8_packed", "N must be a multiple of 32",
+                                    "w_stride_e is smaller than one expert's image (N * K bytes)", 1};
+static const W8Entry W8_GLU_PK = {"tutel_amd_expert_gemm_w8_glu_packed", "H must be a multiple of 16",
+                                  "w_stride_e is smaller than one expert's image (2 * H * K bytes)", 2};
+
+template <typename T, bool GLU>
+static int w8_launch_packed(const W8Entry &en, const W8Args &a, const W8Tables &t, int act, unsigned grid, hipStream_t st) {
+  return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
+      act,
+      [&](auto ac) {
+        hipLaunchKernelGGL((expert_gemm_w8_packed_kernel<T, decltype(ac)::value, GLU>), dim3(grid), dim3(W8_THREADS), 0, st, a, t);
+        TUTEL_CHECK_LAUNCH(en.name);
+        return 0;
+      },
+      [&] { return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu"); });
+}
+
+// TUTEL_AMD_W8_PACKED_MAP=bound: cut the XCD chunks of the packed kernels from the grid, not from the live tile count (A/B runs only)
+static int w8_packed_live_map() {
+  static const int v = [] {
+    const char *s = getenv("TUTEL_AMD_W8_PACKED_MAP");
+    return s != nullptr && strcmp(s, "bound") == 0 ? 0 : 1;
+  }();
+  return v;
+}
+
+// The packed entry points: the padded ones' checks (minus the bucket strides the packed layout does not have), every one in front of
+// the first HIP call
+template <bool GLU>
+static int w8_run_packed(const W8Entry &en, const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq,
+                         int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D, int ldd, int E,
+                         int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
+                         const int32_t *ntiles, int tiles_bound, tutel_stream_t stream) {
+  TUTEL_REQUIRE(E >= 0 && rows_bound >= 0 && tiles_bound >= 0 && N >= 1 && K >= 1, "%s: bad sizes E=%d rows_bound=%d tiles_bound=%d %s=%d K=%d",
+                en.name, E, rows_bound, tiles_bound, GLU ? "H" : "N", N, K);
+  if (!w8_dtype_ok(dtype)) return tutel_notsup(en.name, "the activations must be bf16 or fp16");
+  if (K % W8_BK != 0) return tutel_notsup(en.name, "K must be a multiple of 64");
+  if (N % (32 / en.per_out) != 0) return tutel_notsup(en.name, en.bad_n);
+  if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
+    return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu");
+  if (lda % 8 != 0 || ldd % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0)
+    return tutel_notsup(en.name, "rows of A must stay 16-byte aligned (lda % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16");
+  const long long NI = (long long)en.per_out * N;   // image channels
+  if (w_stride_e < NI * K) return tutel_notsup(en.name, en.small_image);
+  const long long ntn = (NI + W8_BN - 1) / W8_BN;
+  const long long grid = ((long long)tiles_bound * ntn + 7) / 8 * 16;   // 2 halves x the pairs, a whole number of blocks per XCD
+  if (grid > 0x7fffffffLL || NI > 0x7fffffffLL)
+    return tutel_notsup(en.name, "the work item count tiles_bound * 2 * ceil(channels / 128) must stay below 2^31");
+  if (E == 0 || rows_bound == 0 || tiles_bound == 0) return 0;
+  TUTEL_REQUIRE(A && Wq && scale && D && offsets && tiles && ntiles, "%s: null pointer", en.name);
+  TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)D % 8) == 0 &&
+                    ((uintptr_t)bias % 8) == 0,
+                "%s: A, Wq and scale must be 16-byte aligned, D and bias 8-byte aligned", en.name);
+  if (a_rows != nullptr)
+    TUTEL_REQUIRE(T >= 1 && zero_row != nullptr && ((uintptr_t)zero_row % 16) == 0,
+                  "%s: a slot map needs T >= 1 and a 16-byte aligned zero row", en.name);
+
+  W8Args a;
+  a.A = (const unsigned char *)A; a.a_stride_e = 0; a.lda = lda;
+  a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
+  a.scale = scale;
+  a.bias = (const uint16_t *)bias; a.bias_stride_e = bias_stride_e;
+  a.D = (uint16_t *)D; a.d_stride_e = 0; a.ldd = ldd;
+  a.R = rows_bound; a.N = (int)NI; a.K = K; a.ntm = 0; a.ntn = (int)ntn;
+  a.slot_map = a_rows; a.T = T; a.zero_row = (const unsigned char *)zero_row;
+  const W8Tables t = {offsets, tiles, ntiles, tiles_bound, w8_packed_live_map()};
+  hipStream_t st = (hipStream_t)stream;
+  StageScope stage(GLU || act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
+  return dtype == TUTEL_BF16 ? w8_launch_packed<bf16_t, GLU>(en, a, t, act, (unsigned)grid, st)
+                             : w8_launch_packed<f16_t, GLU>(en, a, t, act, (unsigned)grid, st);
 }
 
 // Both entry points: N output channels per row of D, en.per_out * N image channels.  Every check stands in front of the first HIP call
@@ -382,3 +502,20 @@ extern "C" int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, i
                       d_stride_w, d_rows_per_w, ldd, E_loc, R, H, K, dtype, act, row_counts, slot_map, T, zero_row, stream);
 }
 
+
+// The two GEMMs above over the packed dropless layout (the contract: include/tutel_amd.h): the row ranges come from the device tables
+extern "C" int tutel_amd_expert_gemm_w8_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq,
+                                               int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
+                                               int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
+                                               const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream) {
+  return w8_run_packed<false>(W8_PLAIN_PK, A, lda, a_rows, T, zero_row, Wq, w_stride_e, scale, bias, bias_stride_e, D, ldd, E, rows_bound, N,
+                              K, dtype, act, offsets, tiles, ntiles, tiles_bound, stream);
+}
+
+extern "C" int tutel_amd_expert_gemm_w8_glu_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row,
+                                                   const void *Wq_gu, int64_t w_stride_e, const float *scale_gu, void *D, int ldd, int E,
+                                                   int rows_bound, int H, int K, int dtype, int act, const int32_t *offsets,
+                                                   const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream) {
+  return w8_run_packed<true>(W8_GLU_PK, A, lda, a_rows, T, zero_row, Wq_gu, w_stride_e, scale_gu, nullptr, 0, D, ldd, E, rows_bound, H, K,
+                             dtype, act, offsets, tiles, ntiles, tiles_bound, stream);
+}

@@ -18,7 +18,8 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     gathered from the tokens, fc2 read in its checkpoint layout.  No autograd, no megablocks row counts, local experts only;
   * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): bf16 / fp16 experts in inference read e4m3 codes
     with one fp32 scale per (expert, output channel) instead of the 16-bit weights (W8A16: activations are not quantised) -- two
-    launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py);
+    launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py).  A dropless
+    layer with `dropless_packed` and `dropless_packed_fp8` runs them over the packed layout instead (impls/packed_w8.py);
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """

@@ -17,7 +17,9 @@ Forward:
     are derived copies in the KMajorCache (experts/w8.py).  w8_refusal names why a forward keeps its 16-bit weights;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
-the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.
+the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.  With
+`layer.dropless_packed_fp8` as well, FP8 weights run on that layout too (impls/packed_w8.py: tutel_amd_expert_gemm_w8_glu_packed, then
+tutel_amd_expert_gemm_w8_packed on W_fc3), the bits of the padded FP8 forward.
 """
 import torch
 

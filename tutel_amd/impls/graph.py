@@ -16,7 +16,8 @@ host bound, the capacity kept on the device), and only when asked for:
     graphed = GraphedForward(layer, example_input, capacity_factor=0.0, dropless_packed=True)
 
 Replays then serve batches of any expert load, bit for bit what the eager padded dropless forward computes.  Both expert types
-take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM).
+take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM).  Experts with `fp8_weights` are captured reading FP8 when
+`layer.dropless_packed_fp8` is on (impls/packed_w8.py; the warm-up forwards cache the quantised images), else on their 16-bit weights.
 
 GraphedForward is forward-only.  A dropless TRAINING step of `ffn` experts (ReLU; bf16 / fp16 parameters, or fp32 masters under autocast) on the packed layout
 (`layer.dropless_packed = True`, impls/packed_train.py) needs no host synchronisation in its forward or backward either, so

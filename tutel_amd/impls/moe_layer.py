@@ -30,6 +30,7 @@ from .fast_dispatch import RoutingPlan, extract_critical, fast_decode, fast_enco
 from .overlap import a2a_ffn_overlap_forward, a2a_ffn_overlap_fused
 from . import ep_native
 from . import packed_train
+from . import packed_w8
 from .. import ops
 from ..experts import ffn as _ffn
 from ..experts.ffn import FusedExpertsNetwork
@@ -104,6 +105,9 @@ class MOELayer(torch.nn.Module):
         # a HIP graph; same bits as the padded layout.  The capacity then stays on the device: self.dropless_capacity (int32 [1])
         self.dropless_packed = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED", "0")) != 0
         self.dropless_capacity = None
+        # opt-in: experts with fp8_weights on that packed layout (impls/packed_w8.py: the W8A16 GEMMs over the packed tables, six
+        # launches, capturable).  Acts only with capacity_factor <= 0, dropless_packed and experts.fp8_weights; off: nothing changes
+        self.dropless_packed_fp8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_FP8", "0")) != 0
         # gradient accumulation over micro-batches: the packed training step adds the expert gradients into p.main_grad (fp32) inside
         # the gradient kernels and returns no autograd gradient for them (impls/packed_train.py).  A forward that cannot do so raises
         self.dropless_packed_main_grad = int(os.environ.get("TUTEL_AMD_PACKED_MAIN_GRAD", "0")) != 0
@@ -255,16 +259,19 @@ class MOELayer(torch.nn.Module):
         return self._route(*args, **kwargs)[0]
 
     def _route(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
-               original_dtype, crit=None, allow_native=True):
+               original_dtype, crit=None, allow_native=True, packed_fp8=False):
+        """packed_fp8 (before routing): the question of _packed_fp8_plan -- would this forward take the one-call path if its experts
+        ran on their 16-bit GEMMs?  The experts' own admission (engines, can_fuse) is then left to the FP8 ladder"""
         W = self.world_size
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
         # reason: ep_native.packed_cover, asked in _run_native_moe)
         swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
-        fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or isinstance(self.experts, FusedExpertsNetwork))
+        packed_fp8 = packed_fp8 and stage == "before_routing" and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))
+        fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or packed_fp8 or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
                    and (x.dtype == logits.dtype or (logits.dtype == torch.float32 and x.dtype == original_dtype)))
         engine = None
-        if fusable and not swiglu_packed:
+        if fusable and not swiglu_packed and not packed_fp8:
             engine = self.experts.admitted_engine(x, self, megablocks_size=megablocks_size)
             fusable = engine is not None or self.experts.can_fuse(x, self)
         if not fusable:
@@ -336,6 +343,36 @@ class MOELayer(torch.nn.Module):
             return None
         return w
 
+    def _packed_fp8_plan(self, x, logits, plan_args):
+        """The admission of the packed FP8 forward (impls/packed_w8.py), asked before routing; logits may be a meta tensor (shape and
+        dtype only).  -> the packed plan of this call when dropless_packed_fp8 acts and nothing refuses, else None: the forward is
+        then what it is without the switch, and where the switch acts the reason is kept -- the packed layout's or the routing's in _dropless_packed_ran,
+        the FP8 ladder's alone in _fp8_weights_ran (the forward is then the 16-bit packed one)."""
+        gate, top_k, cf, degree, alignment = plan_args[:5]
+        if not (self.dropless_packed_fp8 and cf <= 0 and self.dropless_packed and getattr(self.experts, "fp8_weights", False)
+                and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))):
+            return None
+        T, E = logits.shape[0], logits.shape[-1]
+        k = min(top_k, E)
+        plan, why = None, packed_w8.ROUTING_REASON
+        if x.is_cuda and logits.dim() == 2 and self._plan("before_routing", x, logits, *plan_args, packed_fp8=True) == "native_moe":
+            plan, why = ep_native.packed_cover(self, T, E, k, x.shape[1], x.dtype, ep_native.dropless_row_limit(T, E, k, cf), alignment)
+        if plan is None:
+            self._dropless_packed_ran = why or "the packed layout does not cover this shape"
+            return None
+        why = packed_w8.fp8_refusal(self, x)
+        if why is not None:
+            self._fp8_weights_ran = why
+            return None
+        return plan
+
+    def _run_packed_fp8(self, x, logits, plan, top_k, cf, alignment, megablocks_size):
+        y, l_aux = packed_w8.forward(self, x if x.is_contiguous() else x.contiguous(), logits.contiguous(), min(top_k, logits.shape[1]),
+                                     cf, alignment, plan)
+        self._dropless_packed_ran = self._fp8_weights_ran = True
+        self.megablocks_size = megablocks_size
+        return y, l_aux
+
     def _run_native_moe(self, x, logits, top_k, cf, degree, alignment, megablocks_size, gate_w=None):
         T, E = logits.shape
         k = min(top_k, E)
@@ -348,7 +385,8 @@ class MOELayer(torch.nn.Module):
                                                                      alignment, gate_w=gate_w, plan=plan)
             self._dropless_packed_ran = True if res is not None else (why or "the packed layout does not cover this shape")
             if res is not None:
-                if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
+                if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights and not (
+                        self.dropless_packed_fp8 and isinstance(self._fp8_weights_ran, str)):   # (the FP8 ladder's own reason stays)
                     self._fp8_weights_ran = "the packed dropless forward has no FP8 GEMM"   # it keeps its 16-bit one-call path
                 y, l_aux, cnt, cap = res
                 self.megablocks_size = megablocks_size
@@ -465,9 +503,11 @@ class MOELayer(torch.nn.Module):
         # (a meta tensor stands in for them); anything else -- hooks on the gate, a gradient, fp32_gate, an uncovered shape --
         # projects below as before.  (_NATIVE_GATE_FP32: an fp32 gate over 16-bit tokens too; the logits are then fp32.)
         gate_w = self._native_gate_weight(gate, x)
+        fp8_plan = None   # the packed FP8 forward's plan, once admitted (dropless_packed_fp8; it projects the gate below, once)
         if gate_w is not None:
             spec = torch.empty([x.shape[0], gate_w.shape[0]], dtype=gate_w.dtype, device="meta")
-            if self._plan("before_routing", x, spec, *plan_args) == "native_moe":
+            fp8_plan = self._packed_fp8_plan(x, spec, plan_args)
+            if fp8_plan is None and self._plan("before_routing", x, spec, *plan_args) == "native_moe":
                 res = self._run_native_moe(x, spec, top_k, cf, degree, alignment, megablocks_size, gate_w=gate_w)
                 if res is not None:
                     return finish(*res)
@@ -483,6 +523,10 @@ class MOELayer(torch.nn.Module):
                 logits = gate(x)
         else:
             logits = gate(x)
+        if fp8_plan is None and gate_w is None:
+            fp8_plan = self._packed_fp8_plan(x, logits, plan_args)
+        if fp8_plan is not None:
+            return finish(*self._run_packed_fp8(x, logits, fp8_plan, top_k, cf, alignment, megablocks_size))
         if self._plan("before_routing", x, logits, *plan_args) == "native_moe":
             res = self._run_native_moe(x, logits, top_k, cf, degree, alignment, megablocks_size)
             if res is not None:

@@ -189,6 +189,21 @@ class _PackedFFNTrain(torch.autograd.Function):
         return gx, gg, gw1, gb1, gw2, gb2, None, None, None, None, None
 
 
+def frozen_routing(logits, k, normalize_gate):
+    """The routing prologue of a packed forward whose router takes no gradient: logits [T, E] -> (idx [k, T], gates [k, T],
+    loc [k, T], dispatch_count [E], l_aux) -- the top-k launch and the location launch with the fused gshard loss, the kernel gates
+    and loss as extract_critical takes them then.  Two launches, no host read.  Shared by the packed training step (a frozen
+    router) and the packed FP8 forward (impls/packed_w8.py)."""
+    E = logits.shape[1]
+    work = logits if ops.routing_dtype(logits.dtype) else logits.float()
+    l_dt = logits.dtype if ops.supported_dtype(logits.dtype) else torch.float32
+    idx2d, gk, ws, _ = ops.gate_topk(work.detach(), k, apply_softmax=True, normalize_gate=normalize_gate)
+    loc2d, cnt, _, lk, _ = ops.compute_location(idx2d, E, ws=ws, capacity=0, want_l_aux=True, l_aux_dtype=l_dt)
+    gates2d = gk if gk.dtype == logits.dtype else gk.to(logits.dtype)
+    l_aux = lk[0] if lk.dtype == logits.dtype else lk[0].to(logits.dtype)
+    return idx2d, gates2d, loc2d, cnt, l_aux
+
+
 def forward(layer, gate, x, logits, k, cf, alignment, main_grad=False):
     """One dropless training forward of `layer` on the packed layout: x [T, M], logits [T, E] (with autograd) -> (y [T, M_out], l_aux).
     main_grad: the backward accumulates the expert gradients into the parameters' main_grad (main_grad_problem(layer) is None).
@@ -210,11 +225,7 @@ def forward(layer, gate, x, logits, k, cf, alignment, main_grad=False):
         gates2d = torch.stack(gates_from_scores(torch.softmax(logits, dim=1), idx2d, layer.normalize_gate))
         l_aux = losses.gshard_loss(torch.softmax(logits, dim=1), idx2d.t().long())
     else:
-        # a frozen router: the kernel gates and the fused gshard loss, as extract_critical takes them then
-        idx2d, gk, ws, _ = ops.gate_topk(work.detach(), k, apply_softmax=True, normalize_gate=layer.normalize_gate)
-        loc2d, cnt, _, lk, _ = ops.compute_location(idx2d, E, ws=ws, capacity=0, want_l_aux=True, l_aux_dtype=l_dt)
-        gates2d = gk if gk.dtype == logits.dtype else gk.to(logits.dtype)
-        l_aux = lk[0] if lk.dtype == logits.dtype else lk[0].to(logits.dtype)
+        idx2d, gates2d, loc2d, cnt, l_aux = frozen_routing(logits, k, layer.normalize_gate)
     lay = ops.packed_layout(cnt, idx2d, loc2d, limit, alignment, plan["rows_bound"], plan["tiles_bound"], plan["row_limit"])
     # (its own tensor per call, not ops.zero_row: this step may run inside a captured graph, and the process-wide cache must not
     # hold memory that belongs to a graph's pool)

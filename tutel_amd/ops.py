@@ -623,6 +623,53 @@ def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, ze
     return out
 
 
+def _w8_packed_operands(a, image, scale, channels, N, K, layout, gather, zero_row, out):
+    """the operand checks the two packed W8A16 wrappers share -> (a at a 16-byte aligned address, out [rows_bound, N], a_rows, T, zero row)"""
+    _dev(a, image, scale, out, zero_row)
+    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
+    E = image.shape[0]
+    assert E == layout.E and scale.shape == (E, channels) and image.numel() % max(E, 1) == 0
+    assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K
+    a = _a16(a)
+    if gather:
+        assert zero_row is not None and zero_row.dtype == a.dtype and zero_row.numel() >= K
+    else:
+        assert a.shape[0] >= layout.rows_bound
+    if out is None:
+        out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
+    assert out.shape == (layout.rows_bound, N) and out.is_contiguous() and out.dtype == a.dtype
+    return a, out, (_ptr(layout.slot_map) if gather else None), (a.shape[0] if gather else 0), (_ptr(zero_row) if gather else None)
+
+
+def expert_gemm_w8_packed(a, image, scale, bias, N, K, layout, act="none", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8 over the packed dropless layout: D[r] = act(acc * scale[e] + bias[e]) for the packed rows r of expert e
+    -> [rows_bound, N], bit for bit what expert_gemm_w8 writes for the same row and expert (the contract of include/tutel_amd.h).
+    a [rows_bound, K] bf16 / fp16, or with gather=True the token array [T, K] read through layout.slot_map (zero_row, >= K zeros,
+    for pad rows); image / scale / bias as expert_gemm_w8's.  Rows past layout.offsets[E] are left unwritten.  Returns None when
+    the library answers ENOTSUP (nothing was enqueued)."""
+    a, out, rows, T, z = _w8_packed_operands(a, image, scale, N, N, K, layout, gather, zero_row, out)
+    if bias is not None:
+        _dev(bias)
+        assert bias.dim() == 2 and bias.shape == (layout.E, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
+    rc = _lib.lib().tutel_amd_expert_gemm_w8_packed(
+        _ptr(a), K, rows, T, z, _ptr(image), image.numel() // max(layout.E, 1), _ptr(scale),
+        _ptr(bias), (bias.stride(0) if bias is not None else 0), _ptr(out), N, layout.E, layout.rows_bound, N, K,
+        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_packed", out)
+
+
+def expert_gemm_w8_glu_packed(a, image, scale, H, K, layout, act="silu", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w8_glu writes for the same
+    row and expert.  a, gather, zero_row as expert_gemm_w8_packed's; image / scale: the interleaved gate / up image and its
+    [E, 2 H] scales.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    a, out, rows, T, z = _w8_packed_operands(a, image, scale, 2 * H, H, K, layout, gather, zero_row, out)
+    rc = _lib.lib().tutel_amd_expert_gemm_w8_glu_packed(
+        _ptr(a), K, rows, T, z, _ptr(image), image.numel() // max(layout.E, 1), _ptr(scale),
+        _ptr(out), H, layout.E, layout.rows_bound, H, K,
+        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu_packed", out)
+
+
 def _grad_out_dtype(out_dtype, operand_dtype):
     """out_dtype of the packed gradients: None -> the operands' dtype (the 16-bit entry points), torch.float32 -> the *_f32 ones"""
     if out_dtype is None or out_dtype == operand_dtype:
