@@ -345,6 +345,38 @@ int tutel_amd_expert_gemm_w8_glu_packed(const void *A, int lda, const int32_t *a
                                         int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
                                         const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
 
+/* The quantiser of the W8A16 weights (csrc/quantize_w8.hip): reads a parameter as it is stored and writes the weight image of the
+ * GEMMs above and the per-channel scales directly -- no fp32 copy, no intermediate code tensor, no permuted copies.
+ * Source: expert e at W + e * w_stride_e ELEMENTS of `dtype` (TUTEL_BF16, TUTEL_F16 or TUTEL_F32), N channels of K weights:
+ *     w_kmajor = 1: element (n, k) at n * ldw + k   (batched_fc1_w);   w_kmajor = 0: element (n, k) at k * ldw + n   (batched_fc2_w and
+ *     the three SwiGLU matrices).  Both are read 16 bytes per lane along their contiguous dimension; nothing outside the N x K
+ *     elements of an expert is read (padding behind ldw or w_stride_e may hold anything).
+ * Image channel map: source channel n goes to image channel
+ *     c(n) = (n / group) * group_stride + group_offset + n % group
+ * of an image that is image_channels wide (the W8A16 layout above, unchanged: expert e at Wq + e * wq_stride_e BYTES).  A plain
+ * parameter: image_channels = group = group_stride = N, group_offset = 0.  A SwiGLU gate / up pair: two calls into ONE image of
+ * 2 H channels, both with group = 16 and group_stride = 32, the gate with group_offset = 0, the up with group_offset = 16 -- exactly
+ * tutel_amd/experts/w8.py::interleave_gate_up, then pack.  A call writes only the 16-byte lane chunks and the scales of its own
+ * channels: the other matrix's bytes, and every byte of a channel no source channel maps to, are left untouched.
+ * scale[e * scale_stride_e + c(n)] (fp32) receives channel n's scale.
+ * Numeric contract (part of the interface; the reference is w8.py::quantize_e4m3 on a CPU, whose bits these are):
+ *     scale = fp32(max_k |w|) / 448.0f          a correctly rounded IEEE fp32 division; an all-zero channel gets 1
+ *     q     = e4m3fn_rne(clamp(fp32(w) / scale, -448, 448))      again a correctly rounded division: no reciprocal, no contraction;
+ *                                                fp32 denormals (a quotient, a scale, a weight) are not flushed; -0 keeps its sign
+ * Non-finite weights: *status is ONE int32 the caller presets to INT32_MAX; a channel that holds an inf or a NaN does an atomicMin
+ * of e * N + n on it (so the word ends as the lowest expert's lowest such channel); that channel's codes and scale are unspecified.
+ * Wq == NULL and scale == NULL: the finiteness check alone -- pass 1 and the status word, nothing else is written.
+ * Covered (tutel_amd_quantize_w8_supported == 1: a pure function, no HIP call): dtype one of the three, K % 32 == 0,
+ * image_channels % 32 == 0, group % 16 == 0, N % group == 0, 0 <= group_offset and group_offset + group <= group_stride,
+ * (N / group) * group_stride <= image_channels; and, of the call: ldw >= K (k-major) or N (n-major), w_stride_e >= one expert's
+ * matrix, ldw and w_stride_e multiples of 16 bytes, wq_stride_e % 16 == 0 and >= image_channels * K, scale_stride_e >=
+ * image_channels, E * N < 2^31, W and Wq 16-byte aligned.  Anything else returns TUTEL_AMD_ENOTSUP with its reason and nothing
+ * enqueued; E == 0 is a successful no-op.  Every check precedes the first HIP call.  One launch, no workspace, capturable. */
+int tutel_amd_quantize_w8_supported(int dtype, int N, int K, int image_channels, int group, int group_stride, int group_offset);
+int tutel_amd_quantize_w8(const void *W, int dtype, int w_kmajor, int64_t w_stride_e, int ldw, int E, int N, int K, void *Wq,
+                          int64_t wq_stride_e, float *scale, int64_t scale_stride_e, int image_channels, int group, int group_stride,
+                          int group_offset, int32_t *status, tutel_stream_t stream);
+
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert
  * -- what FusedExpertsNetwork.forward computes with two batched matmuls, two bias adds and the activation

@@ -19,18 +19,21 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
   * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): bf16 / fp16 experts in inference read e4m3 codes
     with one fp32 scale per (expert, output channel) instead of the 16-bit weights (W8A16: activations are not quantised) -- two
     launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py).  A dropless
-    layer with `dropless_packed` and `dropless_packed_fp8` runs them over the packed layout instead (impls/packed_w8.py);
+    layer with `dropless_packed` and `dropless_packed_fp8` runs them over the packed layout instead (impls/packed_w8.py).
+    module.fp8_freeze() makes images and scales the module's own buffers, written by the HIP quantiser (csrc/quantize_w8.hip), and
+    frees the 16-bit weights: the same launches on the same bits, inference only, FP8 state dicts (experts/fp8_resident.py);
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
 import os
+import types
 from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
 
 from .. import net, ops
-from . import w8
+from . import fp8_resident, w8
 
 # eval-mode weight pre-layout: keep a [E, N, K] (k-major) copy of weights stored [E, K, N]; 0 disables
 _PREPACK = int(os.environ.get("TUTEL_AMD_PREPACK", "1")) != 0
@@ -280,6 +283,12 @@ def _run_w8(net, x, R, slot_map):
     return ops.expert_gemm_w8(h, i2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
 
 
+_W8_DTYPES = _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16))
+_W8_SHAPE = _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
+                   lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K))
+# the rungs of the W8 ladder that a module answers without a forward, in the ladder's order: what fp8_freeze() requires
+W8_STATIC = (_SKIP, _DEVICE, _TRAINING_W8, _W8_DTYPES, _GATHERED, _ACTIVATION, _W8_SHAPE)
+
 # fp32 experts on the native fp32 grouped GEMM (the switch is read from the module at call time)
 F32 = Engine(
     ran="_native_fp32_ran", entry="tutel_amd_expert_gemm_f32", run=_run_f32,
@@ -293,17 +302,16 @@ F32 = Engine(
 W8 = Engine(
     ran="_fp8_weights_ran", entry="tutel_amd_expert_gemm_w8", run=_run_w8,
     ladder=(_SWITCH_W8, _SKIP, _DEVICE, _AUTOGRAD_W8, _TRAINING_W8,
-            _AUTOCAST, _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16)),
-            _GATHERED, _MEGABLOCKS, _ACTIVATION,
-            _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
-                   lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K)),
-            _rung(W8_CAPTURE_REASON,
-                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not (
+            _AUTOCAST, _W8_DTYPES, _GATHERED, _MEGABLOCKS, _ACTIVATION, _W8_SHAPE,
+            _rung(W8_CAPTURE_REASON,   # (FP8-resident experts hold their images for good)
+                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.fp8_frozen and not (
                       net._kmajor.holds("fc1.w8", net.batched_fc1_w, "w8") and net._kmajor.holds("fc2.w8", net.batched_fc2_w, "w8")))))
 ENGINES = (W8, F32)   # the order FusedExpertsNetwork.forward tries them in; their dtype checks exclude each other
 
 
 class FusedExpertsNetwork(torch.nn.Module):
+    fp8_frozen = False   # True after fp8_freeze(): the FP8 images are the module's own buffers, the 16-bit weights are gone
+
     def __init__(self, model_dim, hidden_size_per_expert, num_experts_per_device, sharded_count,
                  activation_fn=None, activation_fn_with_self=None, output_dim=None,
                  has_fc1_bias=True, has_fc2_bias=True):
@@ -397,7 +405,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def can_fuse(self, x, ctx):
         """the plain fused route: this rank's own local experts (no weight gathering), no autograd, MFMA-able shapes.  (False does NOT
         mean ATen: adaptive_r = 0 / sharded experts gather their weights in forward() and run the same MFMA kernel on the result.)"""
-        if self.skip_expert or not x.is_cuda or not self._no_autograd(x):
+        if self.skip_expert or self.fp8_frozen or not x.is_cuda or not self._no_autograd(x):
             return False
         if getattr(ctx, "adaptive_degree", 1) == 0 or getattr(ctx, "sharded_count", 1) > 1:
             return False
@@ -409,7 +417,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def can_fuse_training(self, x, ctx):
         """the same local experts WITH autograd: bf16 / fp16 (or autocast over fp32 master weights), ReLU, all four GEMM
         products MFMA-able (forward K = M, H; backward K = M_out, H)"""
-        if (not _TRAIN_FUSED or self.skip_expert or not x.is_cuda or x.dim() != 3 or self._no_autograd(x)
+        if (not _TRAIN_FUSED or self.skip_expert or self.fp8_frozen or not x.is_cuda or x.dim() != 3 or self._no_autograd(x)
                 or getattr(ctx, "adaptive_degree", 1) == 0 or getattr(ctx, "sharded_count", 1) > 1):
             return False
         w1, w2 = self.batched_fc1_w, self.batched_fc2_w
@@ -429,7 +437,8 @@ class FusedExpertsNetwork(torch.nn.Module):
     def admitted_engine(self, x, ctx, megablocks_size=None):
         """the opt-in engine this forward's experts run on, or None: the default GEMMs.  An engine that is switched off costs its
         switch and nothing else"""
-        return next((e for e in ENGINES if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
+        engines = (W8,) if self.fp8_frozen else ENGINES
+        return next((e for e in engines if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
 
     def forward_engine(self, engine, x, R=None, slot_map=None):
         """x [E_loc, R, M] contiguous -> [E_loc, R, M_out] in two launches of engine.entry; slot_map given: x is the TOKEN array [T, M]
@@ -471,7 +480,10 @@ class FusedExpertsNetwork(torch.nn.Module):
 
     def w8_params(self):
         """((image1, scale1), (image2, scale2)): the FP8 images and scales of fc1 (read as stored, k-major) and fc2 (from its
-        [E, H, M_out] storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy"""
+        [E, H, M_out] storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy; after fp8_freeze()
+        the module's own buffers"""
+        if self.fp8_frozen:
+            return (self.fc1_w8, self.fc1_w8_scale), (self.fc2_w8, self.fc2_w8_scale)
         p1 = self._kmajor.derived("fc1.w8", self.batched_fc1_w, "w8", lambda w: w8.prepare(w, True))
         p2 = self._kmajor.derived("fc2.w8", self.batched_fc2_w, "w8", lambda w: w8.prepare(w, False))
         return p1, p2
@@ -479,6 +491,8 @@ class FusedExpertsNetwork(torch.nn.Module):
     def fused_params(self, dtype):
         """(w1, b1, w2, b2, w2_kmajor) of this rank's experts in the GEMM's compute dtype: the parameters themselves, or
         cached casts under autocast; fc2 as a k-major copy in eval mode."""
+        if self.fp8_frozen:
+            raise RuntimeError(fp8_resident.REFUSED + "the 16-bit grouped GEMM was asked for")
         w1, b1, w2, b2 = self.batched_fc1_w, self.batched_fc1_bias, self.batched_fc2_w, self.batched_fc2_bias
         cast = None if w1.dtype == dtype else dtype
         kmajor = self.w2_kmajor_now()
@@ -531,16 +545,40 @@ class FusedExpertsNetwork(torch.nn.Module):
         self._kmajor.invalidate()
 
     def train(self, mode=True):
+        if mode and self.fp8_frozen:
+            raise RuntimeError(fp8_resident.REFUSED + _TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
         self._kmajor.invalidate()
         return super().train(mode)
 
     def _apply(self, fn, *args, **kwargs):
+        fp8_resident.check_apply(self, fn)
         self._kmajor.invalidate()
         return super()._apply(fn, *args, **kwargs)
 
     def _load_from_state_dict(self, *args, **kwargs):
-        self._kmajor.invalidate()
-        return super()._load_from_state_dict(*args, **kwargs)
+        return fp8_resident.load_from_state_dict(self, super()._load_from_state_dict, *args, **kwargs)
+
+    # -- FP8-resident form (experts/fp8_resident.py) ----------------------------------------------------------------------
+    def _fp8_steps(self):
+        E, H, M = self.batched_fc1_w.shape
+        Mo = self.batched_fc2_w.size(2)
+        S = fp8_resident.Source
+        return (fp8_resident.Step("fc1_w8", (S("batched_fc1_w", (E, H, M), True, None),), H, M),
+                fp8_resident.Step("fc2_w8", (S("batched_fc2_w", (E, H, Mo), False, None),), Mo, H))
+
+    def _fp8_dtype(self):
+        return self.batched_fc1_w.dtype
+
+    def _fp8_static_refusal(self):
+        """the first static rung of the W8 ladder this module fails (None: fp8_freeze() may run)"""
+        x, ctx = fp8_resident.static_stand_ins(self.batched_fc1_w, self.sharded_count)
+        return fp8_resident.first_reason(self, W8_STATIC, x, ctx)
+
+    def fp8_freeze(self):
+        """Quantise fc1 and fc2 with the HIP quantiser, keep images and scales as buffers (fc1_w8, fc1_w8_scale, fc2_w8,
+        fc2_w8_scale) and free the 16-bit weights, one parameter at a time; the biases stay.  Inference only from then on, and no
+        way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP8 ladder refuses"""
+        return fp8_resident.freeze(self)
 
     # -- gathered-weight modes + the reference-equivalent ATen path ------------------------------
     def forward(self, x, ctx):
@@ -550,6 +588,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         y = self._forward_if_admitted(W8, x, ctx)
         if y is not None:
             return y
+        if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
+            raise RuntimeError(fp8_resident.REFUSED + (self.engine_refusal(W8, x, ctx) or "the input is not [E_loc, R, M]"))
 
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)

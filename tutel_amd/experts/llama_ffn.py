@@ -14,18 +14,22 @@ Forward:
   * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): the same experts in inference read e4m3 codes with
     one fp32 scale per (expert, output channel) -- TWO launches: the gate and up products in one (tutel_amd_expert_gemm_w8_glu, both
     weight matrices in one interleaved image, the gate never written to memory), then tutel_amd_expert_gemm_w8 on W_fc3; the images
-    are derived copies in the KMajorCache (experts/w8.py).  w8_refusal names why a forward keeps its 16-bit weights;
+    are derived copies in the KMajorCache (experts/w8.py).  w8_refusal names why a forward keeps its 16-bit weights.  module.fp8_freeze()
+    makes the images the module's own buffers and frees the 16-bit weights (experts/fp8_resident.py): a forward that w8_refusal
+    refuses then raises;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
 the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.  With
 `layer.dropless_packed_fp8` as well, FP8 weights run on that layout too (impls/packed_w8.py: tutel_amd_expert_gemm_w8_glu_packed, then
 tutel_amd_expert_gemm_w8_packed on W_fc3), the bits of the padded FP8 forward.
 """
+import types
+
 import torch
 
 from .. import net, ops
 from . import ffn as _ffn
-from . import w8
+from . import fp8_resident, w8
 from .ffn import KMajorCache, classify_activation, _PREPACK
 
 
@@ -33,22 +37,25 @@ def _w8_params(net):
     return net.W_fc1, net.W_fc2, net.W_fc3
 
 
+_W8_DTYPES = _ffn._dtypes(_ffn.W8_DTYPE_REASON, (torch.bfloat16, torch.float16), _w8_params)
+_W8_GATHERED = _ffn._rung(_ffn.GATHERED_REASON,   # (these experts keep their own shard count: their parameters are stored flat and gathered)
+                          lambda net, x, ctx, mb: net.sharded_count > 1 or _ffn._GATHERED(net, x, ctx, mb) is not None)
+# fc3's K is H: stricter than the gate / up kernel's H % 16 == 0
+_W8_SHAPE = _ffn._rung("the shape is not covered (M a multiple of 64, H a multiple of 64)",
+                       lambda net, x, ctx, mb: not (ops.gemm_w8_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
+                                                    and ops.gemm_w8_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1])))
 # why a forward of SwiGLU experts keeps its 16-bit weights: the shared rungs of experts/ffn.py, the switch first; the ORDER is behaviour
 W8_LADDER = (
-    _ffn._SWITCH_W8, _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST,
-    _ffn._dtypes(_ffn.W8_DTYPE_REASON, (torch.bfloat16, torch.float16), _w8_params),
-    _ffn._rung(_ffn.GATHERED_REASON,   # (these experts keep their own shard count: their parameters are stored flat and gathered)
-               lambda net, x, ctx, mb: net.sharded_count > 1 or _ffn._GATHERED(net, x, ctx, mb) is not None),
-    _ffn._ACTIVATION,
-    # fc3's K is H: stricter than the gate / up kernel's H % 16 == 0
-    _ffn._rung("the shape is not covered (M a multiple of 64, H a multiple of 64)",
-               lambda net, x, ctx, mb: not (ops.gemm_w8_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
-                                            and ops.gemm_w8_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1]))),
+    _ffn._SWITCH_W8, _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE,
     _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w8_cached()),
 )
+# the rungs a module answers without a forward, in the ladder's order: what fp8_freeze() requires
+W8_STATIC = (_ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE)
 
 
 class LlamaFFNNetwork(torch.nn.Module):
+    fp8_frozen = False   # True after fp8_freeze(): the FP8 images are the module's own buffers, the 16-bit weights are gone
+
     def _create_sharded_param(self, *full_shape, **kwargs):
         full_shape = torch.Size(full_shape)
         sharded = (full_shape.numel() + self.sharded_count - 1) // self.sharded_count
@@ -93,7 +100,7 @@ class LlamaFFNNetwork(torch.nn.Module):
         return self._act_cache[key]
 
     def can_fuse(self, x, ctx):
-        if not x.is_cuda or self.sharded_count > 1 or torch.is_autocast_enabled():
+        if self.fp8_frozen or not x.is_cuda or self.sharded_count > 1 or torch.is_autocast_enabled():
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
@@ -104,6 +111,8 @@ class LlamaFFNNetwork(torch.nn.Module):
     def kmajor_weights(self):
         """the eval-mode k-major copies (W_fc1 and W_fc2 [E, H, M], W_fc3 [E, M, H]) that forward_fused runs on: the operands of the
         packed dropless forward (impls/ep_native.py, tutel_amd_moe_forward_packed_glu)"""
+        if self.fp8_frozen:
+            raise RuntimeError(fp8_resident.REFUSED + "the 16-bit grouped GEMM was asked for")
         w1, w2, w3 = (self.W_fc1.view(self.W_fc1_full_shape), self.W_fc2.view(self.W_fc2_full_shape),
                       self.W_fc3.view(self.W_fc3_full_shape))
         return self._kmajor.get("fc1", w1), self._kmajor.get("fc2", w2), self._kmajor.get("fc3", w3)
@@ -135,12 +144,17 @@ class LlamaFFNNetwork(torch.nn.Module):
         return ("w8.glu", KMajorCache._key(w2))
 
     def w8_cached(self):
+        if self.fp8_frozen:
+            return True
         w1, w2, w3 = self._w8_views()
         return self._kmajor.holds("fc12.w8", w1, self._w8_gate_up_key(w2)) and self._kmajor.holds("fc3.w8", w3, "w8")
 
     def w8_params(self):
         """((image_gu, scale_gu), (image3, scale3)): the interleaved gate / up image of (W_fc1, W_fc2) and the image of W_fc3, all
-        read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes (KMajorCache's rule)"""
+        read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes (KMajorCache's rule);
+        after fp8_freeze() the module's own buffers"""
+        if self.fp8_frozen:
+            return (self.fc12_w8, self.fc12_w8_scale), (self.fc3_w8, self.fc3_w8_scale)
         w1, w2, w3 = self._w8_views()
         gu = self._kmajor.derived("fc12.w8", w1, self._w8_gate_up_key(w2), lambda w: w8.prepare_gate_up(w, w2.detach(), False))
         p3 = self._kmajor.derived("fc3.w8", w3, "w8", lambda w: w8.prepare(w, False))
@@ -175,22 +189,48 @@ class LlamaFFNNetwork(torch.nn.Module):
         self._kmajor.invalidate()
 
     def train(self, mode=True):
+        if mode and self.fp8_frozen:
+            raise RuntimeError(fp8_resident.REFUSED + _ffn._TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
         self._kmajor.invalidate()
         return super().train(mode)
 
     def _apply(self, fn, *args, **kwargs):
+        fp8_resident.check_apply(self, fn)
         self._kmajor.invalidate()
         return super()._apply(fn, *args, **kwargs)
 
     def _load_from_state_dict(self, *args, **kwargs):
-        self._kmajor.invalidate()
-        return super()._load_from_state_dict(*args, **kwargs)
+        return fp8_resident.load_from_state_dict(self, super()._load_from_state_dict, *args, **kwargs)
+
+    # -- FP8-resident form (experts/fp8_resident.py) ----------------------------------------------------------------------
+    def _fp8_steps(self):
+        _, M, H = self.W_fc1_full_shape
+        S = fp8_resident.Source
+        return (fp8_resident.Step("fc12_w8", (S("W_fc1", tuple(self.W_fc1_full_shape), False, w8.glu_channel_map(H, False)),
+                                              S("W_fc2", tuple(self.W_fc2_full_shape), False, w8.glu_channel_map(H, True))), 2 * H, M),
+                fp8_resident.Step("fc3_w8", (S("W_fc3", tuple(self.W_fc3_full_shape), False, None),), M, H))
+
+    def _fp8_dtype(self):
+        return self.W_fc1.dtype
+
+    def _fp8_static_refusal(self):
+        """the first static rung of the W8 ladder this module fails (None: fp8_freeze() may run)"""
+        x, ctx = fp8_resident.static_stand_ins(self.W_fc1)
+        return fp8_resident.first_reason(self, W8_STATIC, x, ctx)
+
+    def fp8_freeze(self):
+        """Quantise gate and up into one image, then W_fc3, with the HIP quantiser; keep images and scales as buffers (fc12_w8,
+        fc12_w8_scale, fc3_w8, fc3_w8_scale) and free the 16-bit weights, one parameter at a time.  Inference only from then on, and
+        no way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP8 ladder refuses"""
+        return fp8_resident.freeze(self)
 
     # -- reference-equivalent ATen path -----------------------------------------------------
     def forward(self, x, ctx):
         y = self._forward_if_w8(x, ctx)
         if y is not None:
             return y
+        if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
+            raise RuntimeError(fp8_resident.REFUSED + (self.w8_refusal(x, ctx) or "the input is not [E_loc, R, M]"))
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous())
         w1 = self._get_gathered_param(self.W_fc1, self.W_fc1_full_shape, ctx.group)

@@ -1,6 +1,7 @@
 """FP8 (OCP e4m3fn) expert weights for the W8A16 grouped GEMM (csrc/expert_gemm_w8.hip): the quantiser and the weight image.
 
-Cold path, plain torch, runs on CPU and GPU.  The kernel multiplies the 16-bit activations with the EXACT value of every e4m3 code
+Cold path, plain torch, runs on CPU and GPU (the reference of the HIP quantiser at the end of this file, which writes the same bits
+on the device without the intermediate copies).  The kernel multiplies the 16-bit activations with the EXACT value of every e4m3 code
 (widened to bf16 / fp16) and applies the per-channel scale once per output in fp32 (the contract of include/tutel_amd.h), so what
 is written here -- which code and which scale a weight gets -- is the whole of the quantisation's numerics.
 
@@ -117,3 +118,36 @@ def prepare_gate_up(w_gate, w_up, w_kmajor):
     qg, sg = quantize_e4m3(w_gate, w_kmajor)
     qu, su = quantize_e4m3(w_up, w_kmajor)
     return pack(interleave_gate_up(qg, qu)), interleave_gate_up(sg, su).contiguous()
+
+
+# ---- the HIP quantiser (csrc/quantize_w8.hip, tutel_amd_quantize_w8) ------------------------------------------------------------------------
+# The functions above hold an fp32 copy of the parameter, its codes and two permuted copies at once: several times the parameter's
+# size.  The kernel reads the parameter as stored and writes image and scales directly, the same bits.  Where the library does not
+# cover the call (a CPU tensor, K or the channel count no multiple of 32) the torch functions answer, with the same return types.
+def glu_channel_map(H, up):
+    """the channel map of one half of a gate / up image of 2 H channels: (image_channels, group, group_stride, group_offset) --
+    interleave_gate_up's order, c(n) = (n / 16) * 32 + 16 * up + n % 16"""
+    return (2 * H, GLU_GROUP, 2 * GLU_GROUP, GLU_GROUP if up else 0)
+
+
+def prepare_native(w, w_kmajor):
+    """prepare(w, w_kmajor) by the HIP quantiser where it covers the call"""
+    if w.is_cuda:
+        from .. import ops
+        res = ops.quantize_w8(w.detach(), w_kmajor)
+        if res is not None:
+            return res
+    return prepare(w, w_kmajor)
+
+
+def prepare_gate_up_native(w_gate, w_up, w_kmajor):
+    """prepare_gate_up(w_gate, w_up, w_kmajor) by the HIP quantiser where it covers the call: two launches into one image"""
+    if w_gate.is_cuda and w_up.is_cuda and w_gate.shape == w_up.shape and w_gate.dtype == w_up.dtype:
+        from .. import ops
+        H = w_gate.shape[1] if w_kmajor else w_gate.shape[2]
+        res = ops.quantize_w8(w_gate.detach(), w_kmajor, channel_map=glu_channel_map(H, False))
+        if res is not None:
+            res = ops.quantize_w8(w_up.detach(), w_kmajor, image=res[0], scale=res[1], channel_map=glu_channel_map(H, True))
+            if res is not None:
+                return res
+    return prepare_gate_up(w_gate, w_up, w_kmajor)

@@ -33,6 +33,7 @@ from . import packed_train
 from . import packed_w8
 from .. import ops
 from ..experts import ffn as _ffn
+from ..experts import fp8_resident as _fp8_resident
 from ..experts.ffn import FusedExpertsNetwork
 from ..experts.llama_ffn import LlamaFFNNetwork
 from ..gates.top import LinearTopKGate
@@ -200,14 +201,24 @@ class MOELayer(torch.nn.Module):
         else:
             have, want = int(state_dict[key]), self.num_global_experts
             assert have == want, "Failed to load state from checkpoint: the number of global experts mismatch (%s <- %s)" % (want, have)
+        # an FP8-resident state dict (experts/fp8_resident.py) holds images instead of the 16-bit weights: those are not missing
+        steps = self.experts._fp8_steps() if hasattr(self.experts, "_fp8_steps") else ()
+        as_fp8 = {src.name for step in steps if prefix + "experts." + step.buffer in state_dict for src in step.sources}
         for name, param in self.experts.named_parameters():
             k = prefix + "experts." + name
+            if name in as_fp8:
+                continue
             if k not in state_dict:
                 logging.warning("Could not find parameter `%s` in state_dict, zero values will be filled into this parameter." % k)
                 state_dict[k] = torch.zeros_like(param)
             if state_dict[k].numel() == param.numel():
                 state_dict[k] = state_dict[k].view(param.shape)
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def train(self, mode=True):
+        if mode and getattr(getattr(self, "experts", None), "fp8_frozen", False):
+            self.experts.train(True)   # raises (FP8-resident experts are inference only) before any module has changed its mode
+        return super().train(mode)
 
     def extra_repr(self):
         return "Top-K(s) = %s, Total-Experts = %d [managed by %d device(s)]," % (
@@ -266,6 +277,8 @@ class MOELayer(torch.nn.Module):
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
         # reason: ep_native.packed_cover, asked in _run_native_moe)
         swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
+        if getattr(self.experts, "fp8_frozen", False) and not packed_fp8:
+            swiglu_packed = False   # FP8-resident experts: the one-call pipelines have no FP8 GEMM and there are no 16-bit weights
         packed_fp8 = packed_fp8 and stage == "before_routing" and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))
         fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or packed_fp8 or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
@@ -354,15 +367,20 @@ class MOELayer(torch.nn.Module):
             return None
         T, E = logits.shape[0], logits.shape[-1]
         k = min(top_k, E)
+        frozen = getattr(self.experts, "fp8_frozen", False)   # no 16-bit packed forward to fall back to: a refusal raises
         plan, why = None, packed_w8.ROUTING_REASON
         if x.is_cuda and logits.dim() == 2 and self._plan("before_routing", x, logits, *plan_args, packed_fp8=True) == "native_moe":
             plan, why = ep_native.packed_cover(self, T, E, k, x.shape[1], x.dtype, ep_native.dropless_row_limit(T, E, k, cf), alignment)
         if plan is None:
             self._dropless_packed_ran = why or "the packed layout does not cover this shape"
+            if frozen:
+                raise RuntimeError(_fp8_resident.REFUSED + "dropless_packed_fp8 is on and " + self._dropless_packed_ran)
             return None
         why = packed_w8.fp8_refusal(self, x)
         if why is not None:
             self._fp8_weights_ran = why
+            if frozen:
+                raise RuntimeError(_fp8_resident.REFUSED + why)
             return None
         return plan
 
@@ -465,6 +483,9 @@ class MOELayer(torch.nn.Module):
             for p in self.experts.parameters():
                 x = x.to(p.dtype)
                 break
+            else:
+                if getattr(self.experts, "fp8_frozen", False):   # no parameter left to ask: the dtype the experts were frozen from
+                    x = x.to(self.experts._fp8_dtype())
         if x.is_cuda and x.data_ptr() % 16:
             x = x.clone()   # an offset view of a larger buffer: the kernels fetch 16-byte vectors, upstream takes any tensor (ops._a16)
         gate = self.gates[gate_index]
@@ -486,6 +507,14 @@ class MOELayer(torch.nn.Module):
         elif isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
             # SwiGLU experts: the same report (LlamaFFNNetwork.forward sets True, or a later reason)
             self._fp8_weights_ran = self.experts.w8_refusal(x, self)
+        if getattr(self.experts, "fp8_frozen", False):
+            # FP8-resident experts: what the ladder knows before routing decides here, in front of every launch -- no path below
+            # may reach for 16-bit weights that are gone.  (Walked with megablocks_size 0: the packed FP8 forward takes any; the
+            # padded paths meet that rung with their own value, in the experts' forward.)
+            why = packed_w8.fp8_refusal(self, x)
+            if why is not None:
+                self._fp8_weights_ran = why
+                raise RuntimeError(_fp8_resident.REFUSED + why)
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega

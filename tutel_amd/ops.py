@@ -534,6 +534,57 @@ def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None,
     return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu", out)
 
 
+INT32_MAX = 2 ** 31 - 1
+
+
+def quantize_w8_supported(dtype, N, K, channel_map=None):
+    """shapes the HIP quantiser (tutel_amd_quantize_w8) takes -- the library's own answer.  channel_map: (image_channels, group,
+    group_stride, group_offset), default the plain map (N, N, N, 0)"""
+    if dtype not in _DT:
+        return False
+    C, g, gs, go = (N, N, N, 0) if channel_map is None else channel_map
+    return bool(_lib.lib().tutel_amd_quantize_w8_supported(_DT[dtype], int(N), int(K), int(C), int(g), int(gs), int(go)))
+
+
+def quantize_w8(w, w_kmajor, image=None, scale=None, channel_map=None, check_only=False):
+    """The FP8 weight image and scales of one parameter, written by the HIP quantiser straight from the parameter as stored: bit for
+    bit experts/w8.py::prepare (the contract of include/tutel_amd.h).
+
+    w: [E, N, K] (w_kmajor) or [E, K, N], bf16 / fp16 / fp32; the last dimension contiguous, rows and experts may be strided.
+    channel_map = (image_channels, group, group_stride, group_offset): source channel n goes to image channel
+    (n / group) * group_stride + group_offset + n % group; default the plain map.  A SwiGLU gate / up pair is two calls into one
+    image [E, 2 H / 32, K / 32, 64, 16]: (2 H, 16, 32, 0) for the gate, (2 H, 16, 32, 16) with image= and scale= for the up.
+    image / scale: written in place when given (uint8 with image_channels * K bytes per expert, fp32 [E, image_channels]), else
+    allocated.  check_only: nothing is written but the finiteness check runs.
+    -> (image, scale); None where the library does not cover the call (nothing was enqueued).  A non-finite weight raises the torch
+    quantiser's ValueError, naming the same channel (this reads one word back: a synchronisation, the quantiser is a cold path)."""
+    _dev(w, image, scale)
+    assert w.dim() == 3 and w.stride(2) == 1
+    E = w.shape[0]
+    N, K = (w.shape[1], w.shape[2]) if w_kmajor else (w.shape[2], w.shape[1])
+    C, g, gs, go = (N, N, N, 0) if channel_map is None else (int(v) for v in channel_map)
+    if w.dtype not in _DT or not quantize_w8_supported(w.dtype, N, K, (C, g, gs, go)):
+        return None
+    if not check_only:
+        if image is None:
+            image = torch.empty([E, C // 32, K // 32, 64, 16], dtype=torch.uint8, device=w.device)
+        if scale is None:
+            scale = torch.empty([E, C], dtype=torch.float32, device=w.device)
+        assert image.dtype == torch.uint8 and image.is_contiguous() and image.numel() == E * C * K
+        assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.shape == (E, C)
+    status = torch.full([1], INT32_MAX, dtype=torch.int32, device=w.device)
+    rc = _lib.lib().tutel_amd_quantize_w8(
+        _ptr(w), _DT[w.dtype], int(bool(w_kmajor)), w.stride(0) if E > 1 else max(w.stride(0), w.shape[1] * w.stride(1)), w.stride(1),
+        E, N, K, None if check_only else _ptr(image), C * K, None if check_only else _ptr(scale), C, C, g, gs, go,
+        _ptr(status), _stream())
+    if _unless_notsup(rc, "tutel_amd_quantize_w8", True) is None:
+        return None
+    bad = int(status.item())
+    if bad != INT32_MAX:
+        raise ValueError(f"quantize_e4m3: channel (expert {bad // N}, output {bad % N}) holds a non-finite weight")
+    return image, scale
+
+
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     """fc1 -> activation -> fc2 of every local expert in ONE persistent launch (tutel_amd_expert_ffn, csrc/expert_ffn.hip):
     x [E_loc, R, M] -- or the token array [T, M] with smap [E_loc * R] (fast_encode fused) -- w1 [E_loc, H, M], w2_kmajor
