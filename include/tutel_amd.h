@@ -869,6 +869,24 @@ typedef struct {
 } tutel_amd_gemm_plan_t;
 int tutel_amd_expert_gemm_plan_next(tutel_amd_gemm_plan_t *out, int corun);
 
+/* The PLAIN form of the 128 x 256 ring kernel (TUTEL_GEMM_RING with bm 128): a lean instantiation for launches whose rows are plain --
+ * every row of A and D in one source rank (rows_per_w >= R), no row counts, gating operand or peer rows, 32-bit offsets, 16-byte
+ * output rows, write-through stores, N a multiple of 256.  It fetches a compact argument block in one batch, contains no integer
+ * division by a run-time divisor, requests the bias words ahead of the K loop and has one epilogue path; the K loop and the bits are
+ * the general kernel's, and the plan record above is the same for both forms.
+ *   tutel_amd_gemm_plain(value): -1 automatic / 1 = the PLAIN kernel wherever a launch admits it, 0 = never; -2 = leave as it is.
+ *     Returns the previous value.  Seeded once from the environment variable TUTEL_AMD_GEMM_PLAIN.  (An entry point of its own, not
+ *     a numbered TUTEL_OPT_* key.)
+ *   tutel_amd_expert_gemm_last_form(launches): the form of the last grouped GEMM this thread launched through tutel_amd_expert_gemm,
+ *     _glu, _gather, _packed, _gate_up or a pipeline -- or, for a call armed by tutel_amd_expert_gemm_plan_next, would have launched.
+ *     launches (optional, two ints): how many such GEMMs this thread has launched so far in the GENERAL [0] and the PLAIN [1] form
+ *     (armed calls not counted) -- for the GEMMs inside a pipeline, where "the last" is only the last. */
+#define TUTEL_GEMM_FORM_NONE (-1)   /* no grouped GEMM yet on this thread */
+#define TUTEL_GEMM_FORM_GENERAL 0
+#define TUTEL_GEMM_FORM_PLAIN 1
+int tutel_amd_gemm_plain(int value);
+int tutel_amd_expert_gemm_last_form(int *launches);
+
 /* ---- self-test helpers (used by tests / smoke only) ---------------------------------------
  * Dumps the lane->element permutation of ds_read_b64_tr_b16 (the transposing LDS read the
  * [K,N]-weight GEMM relies on): out[64*4] uint16, LDS pre-filled with lds[i] = i, lane l

@@ -13,6 +13,7 @@ int tutel_get_option(int) { return -1; }
 template <int MINW>
 __global__ __launch_bounds__(256, MINW) void k_one(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  GEMM_PROBE(6);  // kernel entry (probe 0 sits inside the tile, behind the wrapper's work-item arithmetic)
   const int nb = gridDim.x;
   int w;
   {
@@ -20,6 +21,15 @@ __global__ __launch_bounds__(256, MINW) void k_one(GemmArgs p) {
     w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
   }
   gemm_big_tile<bf16_t, true, TUTEL_ACT_RELU, 4, 3, true, 128, false>(p, w / p.ntn, 0, w % p.ntn, smem);
+  GEMM_PROBE(5);
+}
+// the PLAIN form (csrc/expert_gemm_plain.hip: the same entry sequence -- the argument block in one batch -- and the same tile call)
+__global__ __launch_bounds__(256, 2) void k_plain(GemmPlainArgs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  GEMM_PROBE(6);
+  const GemmPlainArgs p = gemm_plain_fetch_args();
+  const uint32_t w = (uint32_t)xcd_work_item(p.grid), e = gemm_plain_div(w, (uint32_t)p.ntn, p.rcp_ntn);
+  gemm_big_tile<bf16_t, true, TUTEL_ACT_RELU, 4, 3, true, 128, false, GemmNoHook, true>(p, (int)e, 0, (int)(w - e * (uint32_t)p.ntn), smem);
   GEMM_PROBE(5);
 }
 // persistent, static assignment: workgroup b (XCD b & 7, slot b >> 3) runs items slot, slot + 32, ... of its XCD's list
@@ -52,7 +62,7 @@ int main(int argc, char **argv) {
   const size_t lds = (size_t)3 * 3 * GL_STAGE * 2 + 16;
   auto opt = [&](const void *k) { CK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); };
   opt((const void *)k_one<2>); opt((const void *)k_one<1>); opt((const void *)k_loop<2, TUTEL_ACT_RELU>); opt((const void *)k_loop<1, TUTEL_ACT_RELU>);
-  opt((const void *)k_loop<1, GEMM_ACT_RUNTIME>); opt((const void *)k_loop<2, GEMM_ACT_RUNTIME>);
+  opt((const void *)k_loop<1, GEMM_ACT_RUNTIME>); opt((const void *)k_loop<2, GEMM_ACT_RUNTIME>); opt((const void *)k_plain);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const int tiles = E * (N / 256);
   auto run = [&](int v, int wi) {
@@ -64,12 +74,14 @@ int main(int argc, char **argv) {
       case 3: hipLaunchKernelGGL((k_loop<1, TUTEL_ACT_RELU>), dim3(256), dim3(256), lds, 0, p, tiles / 8); break;
       case 4: hipLaunchKernelGGL((k_loop<1, GEMM_ACT_RUNTIME>), dim3(256), dim3(256), lds, 0, p, tiles / 8); break;
       case 5: hipLaunchKernelGGL((k_loop<2, GEMM_ACT_RUNTIME>), dim3(256), dim3(256), lds, 0, p, tiles / 8); break;
+      case 6: hipLaunchKernelGGL(k_plain, dim3(tiles), dim3(256), lds, 0, gemm_plain_pack(p, p.ntn, tiles)); break;
     }
   };
   const char *names[] = {"one tile per WG, bounds(256,2) [production]", "one tile per WG, bounds(256,1)", "persistent static loop, bounds(256,2)",
-                         "persistent static loop, bounds(256,1)", "persistent static loop, runtime act, bounds(256,1)", "persistent static loop, runtime act, bounds(256,2)"};
+                         "persistent static loop, bounds(256,1)", "persistent static loop, runtime act, bounds(256,1)", "persistent static loop, runtime act, bounds(256,2)",
+                         "one tile per WG, PLAIN form"};
   for (int rep = 0; rep < 3; ++rep)
-    for (int v = 0; v < 6; ++v) {
+    for (int v = 0; v < 7; ++v) {
       for (int i = 0; i < 4; ++i) run(v, i & 1);
       CK(hipDeviceSynchronize());
       CK(hipEventRecord(e0, 0));
@@ -78,12 +90,17 @@ int main(int argc, char **argv) {
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       printf("rep %d  %-55s %8.2f us per GEMM  %6.0f GB/s (weights + rows in + rows out)\n", rep, names[v], ms * 1000 / 20, ((double)E * N * K + (double)E * R * (K + N)) * 2 / (ms / 20 * 1e-3) * 1e-9);
     }
-  // phase timeline of one workgroup (block 17) of the production wrapper
-  for (int i = 0; i < 3; ++i) { run(0, i & 1); }
-  CK(hipDeviceSynchronize());
-  long long pr[8];
-  CK(hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_probe), sizeof(pr)));
-  printf("tile phases of one workgroup (us from entry): prologue issued %.2f, first K-tile landed %.2f, last DMA issued %.2f, K loop done %.2f, epilogue done %.2f\n",
-         (pr[1] - pr[0]) / 100.0, (pr[2] - pr[0]) / 100.0, (pr[3] - pr[0]) / 100.0, (pr[4] - pr[0]) / 100.0, (pr[5] - pr[0]) / 100.0);
+  // phase timeline of one workgroup (block 17) of the production wrapper and of the PLAIN form, three launches each (the last one's marks)
+  for (int v : {0, 6})
+    for (int rep = 0; rep < 3; ++rep) {
+      for (int i = 0; i < 3; ++i) { run(v, i & 1); }
+      CK(hipDeviceSynchronize());
+      long long pr[8];
+      CK(hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_probe), sizeof(pr)));
+      printf("%s: tile phases of one workgroup (us from tile entry): prologue issued %.2f, first K-tile landed %.2f, last DMA issued %.2f, K loop done %.2f, "
+             "epilogue done %.2f | kernel entry to tile entry %.2f, K loop done to epilogue done %.2f\n", v == 0 ? "general" : "PLAIN",
+             (pr[1] - pr[0]) / 100.0, (pr[2] - pr[0]) / 100.0, (pr[3] - pr[0]) / 100.0, (pr[4] - pr[0]) / 100.0, (pr[5] - pr[0]) / 100.0,
+             (pr[0] - pr[6]) / 100.0, (pr[5] - pr[4]) / 100.0);
+    }
   return 0;
 }

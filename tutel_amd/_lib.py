@@ -104,9 +104,13 @@ class GemmPlan(ctypes.Structure):
                                   "d_store", "covered")]
 
 
+GEMM_FORM_NONE, GEMM_FORM_GENERAL, GEMM_FORM_PLAIN = -1, 0, 1                        # TUTEL_GEMM_FORM_*
+GEMM_PLAIN_ENV = "TUTEL_AMD_GEMM_PLAIN"                                              # seeds tutel_amd_gemm_plain
 GEMM_FAMILIES = ("STAGED_128", "GLDS_128", "RING", "PINGPONG", "PACKED_NMAJOR")     # TUTEL_GEMM_*
 SIGNATURES.update({
     "tutel_amd_expert_gemm_plan_next": (_i, [ctypes.POINTER(GemmPlan * 2), _i]),
+    "tutel_amd_gemm_plain": (_i, [_i]),
+    "tutel_amd_expert_gemm_last_form": (_i, [ctypes.POINTER(_i * 2)]),
     "tutel_amd_moe_forward": (_i, [_vp, ctypes.POINTER(MoeArgs), _vp]),
     "tutel_amd_packed_plan": (_i, [_i] * 9 + [ctypes.POINTER(PackedPlan)]),
     "tutel_amd_moe_packed_workspace_bytes": (_sz, [_i] * 9),

@@ -979,7 +979,12 @@ static int run_plan(const GemmPlan &pl, const GemmArgs &a, int dtype, int act, i
         dtype, act,
         [&](auto t, auto ac) {
           if (pl.status != GEMM_PLAN_LAUNCH && pl.status != GEMM_PLAN_FL_QUERY) return plan_refusal(pl, a);
+          // the 128-row ring with plain rows: the lean instantiation (expert_gemm_plain.hip) -- same plan, same bits.  An armed call notes
+          // the form it would have launched
+          const bool plain = pl.status == GEMM_PLAN_LAUNCH && gemm_plain_mode() != 0 && gemm_plain_admits(pl, a);
+          if (pl.status == GEMM_PLAN_LAUNCH) gemm_form_note(plain ? TUTEL_GEMM_FORM_PLAIN : TUTEL_GEMM_FORM_GENERAL);
           if (gemm_plan_report(pl, a) || pl.status == GEMM_PLAN_FL_QUERY) return 0;
+          if (plain) return tutel_gemm_plain_launch(pl, a, dtype, act, st);
           return launch_plan<typename decltype(t)::type, decltype(ac)::value>(pl, a, st);
         },
         other);

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_plain.h"
 
 // probe points of the ring tile (tools/scratch/tile_bench.hip defines this to timestamp them; empty in the library)
 #ifndef GEMM_PROBE
@@ -32,6 +33,15 @@ struct GemmPlan : tutel_amd_gemm_plan_t {                       // the fields tu
 GemmPlan gemm_plan(const GemmArgs &a, bool w_kmajor, bool gate_up, int tiles_bound, const GemmKnobs &k);
 // to a waiting tutel_amd_expert_gemm_plan_next (GemmPlanScope, common.h): the plan; true = "return now", false = nobody asked: launch
 bool gemm_plan_report(const GemmPlan &pl, const GemmArgs &a, int covered = 0);
+
+// The PLAIN form of the 128 x 256 ring kernel (gemm_plain.h, expert_gemm_plain.hip).  gemm_plain_admits (gemm_plan.hip): a pure
+// predicate of the plan and the argument block -- does this launch have the one layout the lean kernel serves?  gemm_plain_mode:
+// TUTEL_AMD_GEMM_PLAIN / tutel_amd_gemm_plain (-1 automatic, 0 never, 1 wherever admitted).  gemm_form_note: what
+// tutel_amd_expert_gemm_last_form answers (TUTEL_GEMM_FORM_*).
+bool gemm_plain_admits(const GemmPlan &pl, const GemmArgs &a);
+int gemm_plain_mode();
+void gemm_form_note(int form);
+int tutel_gemm_plain_launch(const GemmPlan &pl, const GemmArgs &a, int dtype, int act, hipStream_t st);
 
 // one launch with `lds` bytes of dynamic LDS: the opt-in (needed above 64 KB only), the launch, the launch check
 template <typename Kern, typename Args>
@@ -103,6 +113,8 @@ template <int ACT> __device__ __forceinline__ float activate(float v) {
 #define GM_PRELOAD_BIAS() GM_PRELOAD_BIAS_N(2)
 #define GM_PRELOAD_BIAS_N(NI_)                                                                    \
   uint2 bias_r[NI_][4];                                                                           \
+  GM_LOAD_BIAS_N(NI_)
+#define GM_LOAD_BIAS_N(NI_)                                                                       \
   {                                                                                               \
     const uint16_t *be_ = p.bias ? reinterpret_cast<const uint16_t *>(p.bias) + (size_t)e * p.bias_stride_e : nullptr; \
     _Pragma("unroll") for (int ni_ = 0; ni_ < NI_; ++ni_)                                         \
@@ -145,6 +157,32 @@ struct GemmArgs {
 __host__ __device__ __forceinline__ bool gemm_out_rows16(const GemmArgs &p) {
   return !((p.ldd & 7) || (p.d_stride_e & 7) || (p.d_stride_w & 7) || (reinterpret_cast<uintptr_t>(p.D) & 15));
 }
+
+// The ring tile and its LDS epilogue take either block: GemmArgs, or (PLAIN) the compact GemmPlainArgs of the one layout the lean
+// instantiation admits (gemm_plain.h; the host packs it, gemm_plain_pack).  What the two compute differently is behind these overloads:
+// the general forms are the expressions the tile has always had, the PLAIN forms have no division by a run-time divisor.
+template <bool PLAIN> using GemmTileArgs = std::conditional_t<PLAIN, GemmPlainArgs, GemmArgs>;
+__host__ __device__ __forceinline__ bool gemm_out_rows16(const GemmPlainArgs &) { return true; }  // (admitted only with 16-byte rows)
+__device__ __forceinline__ const uint16_t *gemm_a_row(const GemmArgs &p, const uint16_t *Ae, int gr) {
+  return Ae + (size_t)(gr / p.a_rpw) * p.a_stride_w + (size_t)(gr % p.a_rpw) * p.lda;
+}
+__device__ __forceinline__ const uint16_t *gemm_a_row(const GemmPlainArgs &p, const uint16_t *Ae, int gr) { return Ae + gemm_plain_row_off(gr, p.lda); }
+__device__ __forceinline__ int gemm_slot_token(const GemmArgs &p, int q) { return q % p.a_rows_mod; }
+__device__ __forceinline__ int gemm_slot_token(const GemmPlainArgs &p, int q) { return gemm_plain_slot_token(q, p.a_rows_mod, p.rcp_rows_mod); }
+__device__ __forceinline__ int gemm_rot(const GemmArgs &p, int pair, int e, int nk, int npair) {
+  return p.rot_on ? (int)(((long long)(pair + 3 * e) * nk / npair) % nk) : 0;
+}
+__device__ __forceinline__ int gemm_rot(const GemmPlainArgs &p, int pair, int e, int nk, int npair) {  // R <= 128: the rotation is always on
+  return gemm_plain_rot(pair, e, nk, npair, p.rcp_ntn, p.rcp_nk);
+}
+__device__ __forceinline__ unsigned gemm_grid(const GemmArgs &) { return gridDim.x; }
+__device__ __forceinline__ unsigned gemm_grid(const GemmPlainArgs &p) { return (unsigned)p.grid; }
+__device__ __forceinline__ int gemm_ntm(const GemmArgs &p) { return p.ntm; }
+__device__ __forceinline__ int gemm_ntm(const GemmPlainArgs &) { return 1; }
+__device__ __forceinline__ const uint16_t *gemm_mul_base(const GemmArgs &p, int e) {
+  return p.mul ? reinterpret_cast<const uint16_t *>(p.mul) + (size_t)e * p.d_stride_e : nullptr;
+}
+__device__ __forceinline__ const uint16_t *gemm_mul_base(const GemmPlainArgs &, int) { return nullptr; }
 
 // address of output row m of expert e (elements of 2 bytes).  Plain: D + e*stride_e + (m / rpw)*stride_w + (m % rpw)*ldd.
 // Peer stores (IPC transport of the expert-parallel pipeline, ep.hip): the rows that came from source rank w = m / rpw are
@@ -223,7 +261,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &p, f32x16 (&acc)[N
 // per piece inside `if (p.a_rows)` branches, hipcc emitted one global load + s_waitcnt vmcnt(0) per piece (and again for the
 // out-of-range test of the buffer-descriptor path): eight dependent L2 round trips in front of the first DMA of every block --
 // about 2 us per block with one block per CU, the 4 us by which fc1 (gather) trailed fc2 at the headline shape.
-__device__ __forceinline__ void gather_rows4(const GemmArgs &p, int e, const int (&gr)[4], int (&q)[4]) {
+template <typename Args>
+__device__ __forceinline__ void gather_rows4(const Args &p, int e, const int (&gr)[4], int (&q)[4]) {
   q[0] = q[1] = q[2] = q[3] = 0;
   if (p.a_rows != nullptr) {
     const int32_t *m = p.a_rows + (size_t)e * p.R;
@@ -249,6 +288,7 @@ __device__ __forceinline__ int padded_row_limit(const GemmArgs &p, int e) {
   }
   return row_limit;
 }
+__device__ __forceinline__ int padded_row_limit(const GemmPlainArgs &p, int) { return p.R; }  // (no row counts)
 
 // streamed-once weight loads may bypass cache allocation (each W byte is read by exactly one CU)
 template <bool NT> __device__ __forceinline__ u32x4 ld16(const uint16_t *p) {
@@ -287,22 +327,25 @@ __device__ __forceinline__ void bdma16(__amdgpu_buffer_rsrc_t rs, int voff, int 
 // up products of the same features in [NI, 2 * NI); the value of column tile ni is up * g, g = act(gate) rounded to T -- what the
 // act launch stores and the gated launch multiplies by (`v *= mul` below) -- with no bias and no gating operand.
 #define EP_PITCH 272   // NI = 4 (128 columns per wave); NI = 2: 144
-template <typename T, int ACT, int NI = 4, bool GATE_UP = false>
-__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&acc)[GATE_UP ? 2 * NI : NI][2], uint2 (&bias_r)[NI][4],
+// PLAIN (gemm_plain.h): one way out -- no gating operand, no peer rows, write-through stores whose offsets are built by additions.
+template <typename T, int ACT, int NI = 4, bool GATE_UP = false, bool PLAIN = false>
+__device__ __forceinline__ void gemm_epilogue_lds(const GemmTileArgs<PLAIN> &p, f32x16 (&acc)[GATE_UP ? 2 * NI : NI][2], uint2 (&bias_r)[NI][4],
                                                   unsigned char *stage, int e, int m0, int n0, int wm, int wn,
                                                   int lane, int row_limit) {
   constexpr int PITCH = NI * 64 + 16;  // bytes per staged row (NI*32 features + 16 B: see EP_PITCH)
   const int l31 = lane & 31, kg = lane >> 5;
   uint16_t *De = reinterpret_cast<uint16_t *>(p.D) + (size_t)e * p.d_stride_e;
-  const uint16_t *Me = p.mul ? reinterpret_cast<const uint16_t *>(p.mul) + (size_t)e * p.d_stride_e : nullptr;
+  const uint16_t *Me = gemm_mul_base(p, e);
   const bool has_bias = p.bias != nullptr;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
     const int m = m0 + wm * 64 + mi * 32 + l31;
     size_t roff = 0;
+    if constexpr (!PLAIN) {
     if (Me) {
       const int mc = min(m, p.R - 1);
       roff = (size_t)(mc / p.d_rpw) * p.d_stride_w + (size_t)(mc % p.d_rpw) * p.ldd;
+    }
     }
     unsigned char *srow = stage + (mi * 32 + l31) * PITCH + kg * 8;
 #pragma unroll
@@ -337,7 +380,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = activate<ACT>(v[r]);
         }
-        if (Me) {
+        if (!PLAIN && Me) {
           const int n = min(n0 + wn * (NI * 32) + ni * 32 + rg * 8 + kg * 4, p.N - 4);
           const uint2 mm = *reinterpret_cast<const uint2 *>(Me + roff + n);
           uint16_t m4[4] = {(uint16_t)(mm.x & 0xffff), (uint16_t)(mm.x >> 16), (uint16_t)(mm.y & 0xffff), (uint16_t)(mm.y >> 16)};
@@ -365,6 +408,21 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
   constexpr int LPR = NI * 4, RPI = 64 / LPR;  // lanes per row (16 bytes each), rows per store instruction
   const int c16 = lane % LPR, r4 = lane / LPR;
   const int n = n0 + wn * (NI * 32) + c16 * 8;
+  if constexpr (PLAIN) {
+    // the wave's 64 rows, RPI per instruction: lane offset (r4 * ldd + n) * 2 once, the instruction's first row as the scalar offset, stepped
+    // by additions (N % 256 == 0: every column of the tile exists; rows past R are not stored)
+    const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(De, 0, -1, 0x00020000);
+    const int voff = (gemm_plain_row_off(r4, p.ldd) + n) * 2, sstep = gemm_plain_row_off(RPI, p.ldd) * 2;
+    int soff = gemm_plain_row_off(__builtin_amdgcn_readfirstlane(m0 + wm * 64), p.ldd) * 2;
+#pragma unroll 4
+    for (int it = 0; it < 64 / RPI; ++it) {
+      const int row = it * RPI + r4;
+      const u32x4 val = *reinterpret_cast<const u32x4 *>(stage + row * PITCH + c16 * 16);
+      if (m0 + wm * 64 + row < row_limit) __builtin_amdgcn_raw_buffer_store_b128(val, rs_d, voff, soff, 17);
+      soff += sstep;
+    }
+    return;
+  } else {
   if (p.d_store != 0 && p.d_peer != nullptr) {
     // peer rows (IPC transport), write-through: the rows of ONE store instruction -- RPI consecutive rows starting at a multiple of RPI --
     // belong to one source rank (the host sets d_store for peer stores only when d_rpw % 8 == 0), so the descriptor over that rank's
@@ -419,6 +477,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
     }
   }
   if (p.d_peer != nullptr) peer_canary_store(p.d_peer, p.d_can);
+  }
 }
 
 // -------------------------------------------------------------------------------------------
@@ -457,10 +516,15 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs &p, f32x16 (&ac
 struct GemmNoHook { __device__ __forceinline__ void operator()() const {} };
 // `tail`: called by every thread between the K loop and the epilogue (the persistent kernel asks for its next ticket there, so that the
 // atomic's round trip hides behind the epilogue's LDS staging and stores); a tile without rows calls it too.
-template <typename T, bool W_KMAJOR, int ACT, int NI, int NS, bool BUF = false, int BM = GB_BM, bool FL = false, typename Tail = GemmNoHook>
-__device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, const int mt, const int nt, unsigned char *smem,
+// PLAIN (expert_gemm_plain.hip; the 128 x 256 ring only): the lean instantiation for launches whose rows are plain -- argument block
+// GemmPlainArgs, no division by a run-time divisor, the bias words requested in front of the first DMA, one epilogue path.  The K loop,
+// the ring counting, the swizzles, the rotation VALUE and the fused location scan are the lines below, shared: the same bits.
+template <typename T, bool W_KMAJOR, int ACT, int NI, int NS, bool BUF = false, int BM = GB_BM, bool FL = false, typename Tail = GemmNoHook,
+          bool PLAIN = false>
+__device__ __forceinline__ void gemm_big_tile(const GemmTileArgs<PLAIN> &p, const int e, const int mt, const int nt, unsigned char *smem,
                                               Tail tail = Tail()) {
   static_assert(!FL || (BUF && NS == 3 && BM == 128 && W_KMAJOR), "FL: the 128 x 256 ring kernel only");
+  static_assert(!PLAIN || (BUF && NS == 3 && BM == 128 && NI == 4 && W_KMAJOR && ACT != GEMM_ACT_RUNTIME), "PLAIN: the 128 x 256 ring kernel only");
   constexpr int NW = BM / 32;               // waves: (BM / 64) row groups x 2 column groups
   constexpr int NSUB = NI / 2;              // 128-column weight sub-tiles per stage
   constexpr int WPW = 16 * NSUB / NW;       // weight DMA pieces per wave and stage
@@ -513,10 +577,10 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
     const int r = 8 * (wid * 4 + i) + (lane >> 3);                                                             \
     const int c = (lane & 7) ^ ((r >> 1) & 7);                                                                 \
     const int gr = gr4[i];                                                                                     \
-    a_src[i] = Ae + (size_t)(gr / p.a_rpw) * p.a_stride_w + (size_t)(gr % p.a_rpw) * p.lda + c * 8;            \
+    a_src[i] = gemm_a_row(p, Ae, gr) + c * 8;                                                                  \
     if (p.a_rows != nullptr) {                                                                                 \
       const int q = slot4[i];                                                                                  \
-      a_src[i] = (q >= 0 ? reinterpret_cast<const uint16_t *>(p.A) + (size_t)(q % p.a_rows_mod) * p.lda        \
+      a_src[i] = (q >= 0 ? reinterpret_cast<const uint16_t *>(p.A) + (size_t)gemm_slot_token(p, q) * p.lda     \
                          : reinterpret_cast<const uint16_t *>(p.a_zero)) + c * 8;                              \
     }                                                                                                          \
   }
@@ -559,7 +623,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
   // 256 x 256 tile with the chip covered (32 x 256 rows: 720 -> 758 TFLOP/s, dropless 64 x 157: 171 -> 156 us).
   // With several M-tiles the blocks re-read each other's weight tiles from L2 and the hint costs 6-15 %; it also
   // costs on the 256 x 128 tile and on half-empty grids (measured), so it is limited to the case that gains.
-  const bool w_once = NI == 4 && p.ntm == 1 && gridDim.x >= 256;
+  const bool w_once = NI == 4 && gemm_ntm(p) == 1 && gemm_grid(p) >= 256;
 
   f32x16 acc[NI][2];
 #pragma unroll
@@ -570,6 +634,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int l31 = lane & 31, kg = lane >> 5;
+  uint2 bias_r[NI][4];  // filled after the K loop (GM_LOAD_BIAS_N), PLAIN: in front of the ring's first DMA
   const int sw = (l31 >> 1) & 7;
   int frag_k[4];
 #pragma unroll
@@ -586,7 +651,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
   const int nk = p.K / GL_BK;
   // the same k order as the 128-tile kernels (rotation per PAIR of 128-column tiles)
   const int npair = NI == 4 ? p.ntn : (p.ntn + 1) >> 1, pair = NI == 4 ? nt : nt >> 1;
-  const int rot = p.rot_on ? (int)(((long long)(pair + 3 * e) * nk / npair) % nk) : 0;
+  const int rot = gemm_rot(p, pair, e, nk, npair);
 
 #define GB_ISSUE_A(KT, STG)                                                            \
   do {                                                                                 \
@@ -684,6 +749,10 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
     // the weight DMA is what lets `s_waitcnt vmcnt(16)` below wait for it WITHOUT waiting for the weights (16 = the 2 x WPW weight
     // ops every wave issues after it; as register loads hipcc placed a vmcnt(0) at their first use).  1 KB per wave instruction
     // through a descriptor whose range is the buffer: the tail reads zeros.
+    // PLAIN: the lane's bias words are requested HERE, ahead of every DMA, as the ping-pong kernel does (GM_PRELOAD_BIAS) -- after the
+    // K loop their round trip stands exposed in front of the staging.  Older than all the DMA, they leave the hand-counted waits below
+    // as they are: vmcnt retires in order and every count names the YOUNGEST ops that may still be in flight.
+    if constexpr (PLAIN) { GM_LOAD_BIAS_N(NI); }
     constexpr int FL_CH = 4;  // 16-byte chunks per thread: k*T <= 15 KB of entries
     unsigned char *s_fl = smem + (size_t)NS * (A_STAGE + NSUB * GL_STAGE) * 2;  // [15360] idx bytes, [128] slots, [4] wave totals
     if (FL && fl_on) {
@@ -838,21 +907,61 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &p, const int e, co
 #undef GB_MMA
 
   tail();
-  GM_PRELOAD_BIAS_N(NI);
+  if constexpr (!PLAIN) { GM_LOAD_BIAS_N(NI); }
   if (BUF && gemm_out_rows16(p)) {
     __syncthreads();  // every wave is done with the K-tile stages: LDS is free for the staging regions
     unsigned char *stage = smem + wid * (64 * (NI * 64 + 16));
-    if (ACT == GEMM_ACT_RUNTIME) {  // one copy of everything above for all activations; the same epilogue code (and bits) per activation
+    if constexpr (ACT == GEMM_ACT_RUNTIME) {  // one copy of everything above for all activations; the same epilogue code (and bits) per activation
       if (p.act_rt == TUTEL_ACT_NONE) gemm_epilogue_lds<T, TUTEL_ACT_NONE, NI>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
       else if (p.act_rt == TUTEL_ACT_RELU) gemm_epilogue_lds<T, TUTEL_ACT_RELU, NI>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
       else if (p.act_rt == TUTEL_ACT_GELU) gemm_epilogue_lds<T, TUTEL_ACT_GELU, NI>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
       else gemm_epilogue_lds<T, TUTEL_ACT_SILU, NI>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
       return;
     }
-    gemm_epilogue_lds<T, ACT == GEMM_ACT_RUNTIME ? TUTEL_ACT_NONE : ACT, NI>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
+    gemm_epilogue_lds<T, ACT == GEMM_ACT_RUNTIME ? TUTEL_ACT_NONE : ACT, NI, false, PLAIN>(p, acc, bias_r, stage, e, m0, n0, wm, wn, lane, row_limit);
     return;
   }
   static_assert(ACT != GEMM_ACT_RUNTIME || BUF, "the run-time activation switch lives in the LDS epilogue");
-  gemm_epilogue<T, ACT == GEMM_ACT_RUNTIME ? TUTEL_ACT_NONE : ACT, NI>(p, acc, bias_r, e, m0, n0, wm, wn, l31, kg, row_limit);
+  if constexpr (!PLAIN) gemm_epilogue<T, ACT == GEMM_ACT_RUNTIME ? TUTEL_ACT_NONE : ACT, NI>(p, acc, bias_r, e, m0, n0, wm, wn, l31, kg, row_limit);
 }
 
+// GemmArgs -> the compact block (the launch was admitted: gemm_plain_admits)
+static inline GemmPlainArgs gemm_plain_pack(const GemmArgs &a, int ntn, int grid) {
+  GemmPlainArgs p = {};
+  p.W = a.W; p.w_stride_e = a.w_stride_e; p.ldw = a.ldw; p.K = a.K; p.N = a.N; p.ntn = ntn;
+  p.rcp_ntn = gemm_plain_rcp((uint32_t)ntn); p.rcp_nk = gemm_plain_rcp((uint32_t)(a.K / GL_BK));
+  p.R = a.R; p.E_loc = a.E_loc; p.sgather = a.sgather; p.a_rows = a.a_rows; p.fl_idx8 = a.fl_idx8;
+  p.A = a.A; p.a_stride_e = a.a_stride_e; p.lda = a.lda; p.a_span_bytes = a.a_span_bytes;
+  p.a_zero = a.a_zero; p.a_rows_mod = a.a_rows_mod; p.rcp_rows_mod = a.a_rows != nullptr ? gemm_plain_rcp((uint32_t)a.a_rows_mod) : 0u;
+  p.fl_loc = a.fl_loc; p.fl_n = a.fl_n; p.ldd = a.ldd;
+  p.bias = a.bias; p.bias_stride_e = a.bias_stride_e; p.D = a.D; p.d_stride_e = a.d_stride_e; p.grid = grid;
+  return p;
+}
+
+// Device side: the block of a kernel whose FIRST (and only) argument is a GemmPlainArgs, fetched in ONE batch -- five 8-dword scalar
+// loads from the kernel-argument segment at entry and one wait.  (Read field by field, hipcc fetches each argument where it is first
+// used: in the general kernel the straight-line path to the first weight DMA crosses seven dependent waits on such fetches.)  The
+// empty asm statement takes the forty dwords as in-out operands, so they are all in registers there and nothing after it can go
+// back to the segment.
+__device__ __forceinline__ GemmPlainArgs gemm_plain_fetch_args() {
+  typedef int sgv8a __attribute__((ext_vector_type(8), aligned(4)));
+  struct Raw { sgv8 v[5]; };
+  static_assert(sizeof(Raw) == sizeof(GemmPlainArgs), "the five loads cover the block");
+  const __attribute__((address_space(4))) sgv8a *kp = (const __attribute__((address_space(4))) sgv8a *)__builtin_amdgcn_kernarg_segment_ptr();
+  sgv8 k0 = kp[0], k1 = kp[1], k2 = kp[2], k3 = kp[3], k4 = kp[4];
+  asm volatile("" : "+s"(k0), "+s"(k1), "+s"(k2), "+s"(k3), "+s"(k4));
+  const Raw raw = {{k0, k1, k2, k3, k4}};
+  GemmPlainArgs p = __builtin_bit_cast(GemmPlainArgs, raw);
+  // pointers rebuilt from integers have no address space: say "global", as a kernel's pointer arguments are, or every access through
+  // them is a FLAT instruction (which counts on lgkmcnt as well as vmcnt)
+#define GM_GLOBAL_PTR(F)                                                                        \
+  {                                                                                             \
+    __attribute__((address_space(1))) void *g_ = (__attribute__((address_space(1))) void *)(p.F); \
+    asm volatile("" : "+s"(g_));  /* (an opaque global pointer: a cast of an integer would fold back to "no address space") */ \
+    p.F = (decltype(p.F))g_;                                                                     \
+  }
+  GM_GLOBAL_PTR(W) GM_GLOBAL_PTR(a_rows) GM_GLOBAL_PTR(fl_idx8) GM_GLOBAL_PTR(A) GM_GLOBAL_PTR(a_zero) GM_GLOBAL_PTR(fl_loc)
+  GM_GLOBAL_PTR(bias) GM_GLOBAL_PTR(D)
+#undef GM_GLOBAL_PTR
+  return p;
+}

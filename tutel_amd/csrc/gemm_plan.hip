@@ -47,6 +47,42 @@ GemmKnobs gemm_knobs() {
                    tutel_get_option(TUTEL_OPT_GEMM_SPLITK), g_plan_out != nullptr ? g_plan_corun : tutel_gemm_corun()};
 }
 
+// ---- the PLAIN form of the 128 x 256 ring kernel: who takes it -------------------------------------------------------------------------
+// Yes only for the one layout the lean instantiation serves (gemm_plain.h): the 128-row ring plan; every row of an operand in one
+// source rank (so row m sits m * ld past the expert's base); no peer rows, gating operand or row counts; 32-bit offsets, 16-byte output
+// rows, write-through stores; whole 256-column tiles; the rotation computable in 32 bits.  Everything else takes the general kernel.
+// The plan record (tutel_amd_gemm_plan_t) is the same either way: the form is a property of the launch, not of the plan.
+bool gemm_plain_admits(const GemmPlan &pl, const GemmArgs &a) {
+  const bool ring128 = pl.status == GEMM_PLAN_LAUNCH && pl.family == TUTEL_GEMM_RING && pl.bm == 128 && pl.ni == 4 && pl.ns == 3 && pl.buf && pl.w_kmajor;
+  return ring128 && a.a_rpw >= a.R && a.d_rpw >= a.R && a.d_peer == nullptr && a.mul == nullptr && a.row_counts == nullptr && a.fits32 &&
+         gemm_out_rows16(a) && a.d_store == 1 && a.N % 256 == 0 && a.K % GL_BK == 0 && gemm_plain_rot_fits(pl.ntn, a.E_loc, a.K / GL_BK);
+}
+// Not one of the numbered TUTEL_OPT_* knobs: an entry point of its own (tutel_amd_gemm_plain), seeded once from TUTEL_AMD_GEMM_PLAIN.
+// -1 (automatic) and 1: the PLAIN kernel wherever the predicate holds; 0: never.
+static int g_plain_mode = -2;
+int gemm_plain_mode() {
+  if (g_plain_mode == -2) {
+    const char *s = getenv("TUTEL_AMD_GEMM_PLAIN");
+    g_plain_mode = s ? atoi(s) : -1;
+  }
+  return g_plain_mode;
+}
+extern "C" int tutel_amd_gemm_plain(int value) {
+  TUTEL_REQUIRE(value >= -2 && value <= 1, "tutel_amd_gemm_plain: value %d out of range", value);
+  const int was = gemm_plain_mode();
+  if (value != -2) g_plain_mode = value;
+  return was;
+}
+static thread_local int g_last_form = TUTEL_GEMM_FORM_NONE, g_form_launches[2] = {0, 0};
+void gemm_form_note(int form) {
+  g_last_form = form;
+  if (g_plan_out == nullptr) ++g_form_launches[form == TUTEL_GEMM_FORM_PLAIN];   // (an armed call launches nothing)
+}
+extern "C" int tutel_amd_expert_gemm_last_form(int *launches) {
+  if (launches != nullptr) { launches[0] = g_form_launches[0]; launches[1] = g_form_launches[1]; }
+  return g_last_form;
+}
+
 static GemmPlan plan_refused(int status, const char *error) {
   GemmPlan p = {};
   p.status = status; p.family = -1; p.error = error;

@@ -4,6 +4,8 @@ PyTorch is plumbing here: it owns the HBM allocations and the current HIP stream
 below hands raw device pointers + sizes + that stream to libtutel_amd.so.  All ops require HIP
 device tensors and raise otherwise -- there is no CPU or eager implementation behind them.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -830,6 +832,20 @@ def get_option(key):
         return int(os.environ.get(_OPT_ENV[int(key)], "-1"))
     except ValueError:
         return -1
+
+
+def gemm_plain(value=-2):
+    """The PLAIN form of the 128 x 256 ring GEMM kernel (include/tutel_amd.h): -1 automatic / 1 = wherever a launch admits it, 0 = never;
+    -2 only asks.  Returns the previous value (seeded from TUTEL_AMD_GEMM_PLAIN)."""
+    return _lib.lib().tutel_amd_gemm_plain(int(value))
+
+
+def expert_gemm_last_form():
+    """(_lib.GEMM_FORM_* of the last grouped GEMM this thread launched -- NONE before the first --, [launches so far in the GENERAL form,
+    in the PLAIN form])"""
+    n = (ctypes.c_int * 2)()
+    form = _lib.lib().tutel_amd_expert_gemm_last_form(ctypes.byref(n))
+    return form, [n[0], n[1]]
 
 
 def probe_tr16():
