@@ -314,6 +314,73 @@ int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_st
                                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                                  tutel_stream_t stream);
 
+/* W4A16 (csrc/expert_gemm_w4.hip): the grouped GEMM of bf16 / fp16 experts whose weights are stored as OCP MXFP4 -- e2m1 codes, two
+ * per byte, with one e8m0 scale byte per block of 32 values along K.  Activations, bias and output stay in `dtype` (TUTEL_BF16 or
+ * TUTEL_F16).  Numeric contract (part of the interface):
+ *     w[e, n, k]   = val(code[e, n, k]) * 2^(s[e, n, k / 32] - 127)
+ *     val(code)    in +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}      (e2m1: sign, 2 exponent bits, 1 mantissa bit)
+ *                  exactly representable in `dtype` -- see the admitted scale bytes below
+ *     acc[e, r, n] = sum_k A[e, r, k] * w[e, n, k]        fp32, by v_mfma_f32_32x32x16_{bf16,f16}, ONE accumulator per output,
+ *                                                         K ascending, no split-K, no atomics
+ *     v            = acc (+ float(bias[e, n]))            one fp32 add, skipped when bias is NULL
+ *     v            = act(v)                               tutel_amd_expert_gemm_w8's epilogue formulas
+ *     D[e, r, n]   = v rounded once to `dtype`
+ *   The widen is v_cvt_scalef32_pk_{bf16,f16}_fp4; the scale reaches it as the fp32 with bits s << 23, a power of two, so the
+ *   contract does not depend on whether the instruction reads the mantissa.  The scale folds into the widened operand exactly: there
+ *   is no multiply in the epilogue and no second rounding.  The activations are not quantised: neither the fp8 / fp4 matrix
+ *   instruction nor the block-scaled MFMA is used.
+ * Admitted scale bytes -- those for which every product val * 2^(s - 127) is a NORMAL number of the dtype (0.5 * 2^e at least the
+ * smallest normal, 6 * 2^e = 1.5 * 2^(e + 2) at most the largest finite):
+ *     bf16: s = 2 .. 252   (exponents -125 .. 125)          fp16: s = 114 .. 140   (exponents -13 .. 13)
+ *   Within these ranges the convert has nothing to round.  A byte outside the range, 0xFF (the e8m0 NaN) included, is refused on the
+ *   host when an image is built (tutel_amd/experts/w4.py::check_scales, the quantiser's clamp); the kernel given such a byte stays
+ *   memory-safe and its output for that channel is unspecified.
+ * The weight image (the kernel's own layout; tutel_amd/experts/w4.py::pack / unpack from the standard MX layout, in which element
+ * 2 j of a row is the low nibble of byte j and element 2 j + 1 the high nibble):
+ *   codes Wq -- expert e at Wq + e * w_stride_e BYTES, then [N / 32 channel groups][K / 64][64 lanes][16 bytes]:
+ *     lane l of block (g, t) holds channel n = 32 g + (l & 31); nibble j (0 = the low nibble of the lowest byte) of dword q of its
+ *     16 bytes is the code of k = 64 t + 16 q + 8 (l >> 5) + j
+ *     -- one 16-byte load per lane is 1 KB contiguous per wave and is the lane's matrix-instruction operand of four K-steps of 16; a
+ *     channel group's whole K extent is one contiguous run of 16 K bytes; an expert's image is N * K / 2 bytes.
+ *   scales Ws -- expert e at Ws + e * s_stride_e BYTES, then [N / 32][ceil(K / 128)][32 channels][4 bytes]:
+ *     byte i of channel c of block (g, t128) is the scale byte of channel 32 g + c for k in [128 t128 + 32 i, + 32); bytes past K / 32
+ *     blocks are padded with 127 -- one dword per lane per 128 k, 128 B contiguous per 32 lanes; an expert's image is
+ *     N * ceil(K / 128) * 4 bytes.
+ * bias: `dtype`, row e at bias + e * bias_stride_e elements, or NULL.  Rows of A and D, slot_map, T and zero_row: exactly
+ * tutel_amd_expert_gemm_w8's.
+ * Covered (tutel_amd_expert_gemm_w4_supported(dtype, N, K) == 1: a pure function, no HIP call): bf16 / fp16, K % 64 == 0,
+ * N % 32 == 0; lda and a_stride_e % 8 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K / 2,
+ * s_stride_e % 4 == 0 and >= N * ceil(K / 128) * 4; any R >= 1 (tuned for R <= 128; more rows stream the weights once per 128),
+ * E_loc * R, the tile count E_loc * ceil(R / 128) * ceil(N / 128) and 16 K below 2^31.  Ragged last tiles clamp their loads and mask
+ * their stores: nothing is read or written outside the operands.  NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange
+ * layouts (rows_per_w < R or a stride_w), peer stores.  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued;
+ * E_loc == 0 or R == 0 is a successful no-op.  A, Wq and zero_row 16-byte aligned, D and bias 8-byte aligned, Ws 4-byte aligned.
+ * Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w4_supported(int dtype, int N, int K);
+int tutel_amd_expert_gemm_w4(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
+                             int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e, void *D,
+                             int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                             int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                             tutel_stream_t stream);
+
+/* W4A16 for SwiGLU experts (csrc/expert_gemm_w4.hip): the gate and up products of one expert in ONE launch over MXFP4 weights, no
+ * bias -- tutel_amd_expert_gemm_w8_glu's order without its two scale multiplies:
+ *     gacc, uacc = sum_k A[e, r, k] * w[e, n, k]          as in tutel_amd_expert_gemm_w4, ONE accumulator per output and matrix
+ *     D[e, r, n] = round_T( float(round_T(act(gacc))) * uacc )          n < H; one fp32 multiply with its own rounding
+ * The image is tutel_amd_expert_gemm_w4's layout over N = 2 H channels in which the two matrices are interleaved by 16: within every
+ * 32-channel group g, position p < 16 is gate channel 16 g + p and position 16 + p is up channel 16 g + p, codes and scale bytes
+ * alike (tutel_amd/experts/w8.py::interleave_gate_up, then w4.py::pack).  D is [E_loc, R, H] with element strides.
+ * Covered (tutel_amd_expert_gemm_w4_glu_supported(dtype, H, K) == 1: a pure function, no HIP call): bf16 / fp16, K % 64 == 0,
+ * H % 16 == 0, H >= 16; the alignment and stride conditions of tutel_amd_expert_gemm_w4 with w_stride_e >= H * K and
+ * s_stride_e >= 2 * H * ceil(K / 128) * 4.  NOT covered: row_counts, the exchange layouts, peer stores.  Anything not covered
+ * returns TUTEL_AMD_ENOTSUP with nothing enqueued.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w4_glu_supported(int dtype, int H, int K);
+int tutel_amd_expert_gemm_w4_glu(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq_gu,
+                                 int64_t w_stride_e, const void *Ws_gu, int64_t s_stride_e, void *D, int64_t d_stride_e,
+                                 int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int H, int K, int dtype, int act,
+                                 const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                                 tutel_stream_t stream);
+
 /* The two W8A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w8.hip): the experts'
  * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value
  * and can be captured in a HIP graph.

@@ -50,6 +50,12 @@ SIGNATURES = {
     "tutel_amd_expert_gemm_w8_glu_supported": (_i, [_i, _i, _i]),
     "tutel_amd_expert_gemm_w8_glu": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _i64, _i, _i,
                                           _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tutel_amd_expert_gemm_w4_supported": (_i, [_i, _i, _i]),
+    "tutel_amd_expert_gemm_w4": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i,
+                                      _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tutel_amd_expert_gemm_w4_glu_supported": (_i, [_i, _i, _i]),
+    "tutel_amd_expert_gemm_w4_glu": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i,
+                                          _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "tutel_amd_quantize_w8_supported": (_i, [_i] * 7),
     "tutel_amd_quantize_w8": (_i, [_vp, _i, _i, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "tutel_amd_expert_ffn": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i,

@@ -22,6 +22,9 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     layer with `dropless_packed` and `dropless_packed_fp8` runs them over the packed layout instead (impls/packed_w8.py).
     module.fp8_freeze() makes images and scales the module's own buffers, written by the HIP quantiser (csrc/quantize_w8.hip), and
     frees the 16-bit weights: the same launches on the same bits, inference only, FP8 state dicts (experts/fp8_resident.py);
+  * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same experts read e2m1 codes with one
+    power-of-two scale byte per 32 values along K (W4A16; the widened weights are exact, activations are not quantised) -- two launches
+    of tutel_amd_expert_gemm_w4; the images are derived copies in the KMajorCache (experts/w4.py), the 16-bit parameters stay;
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
@@ -33,7 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import net, ops
-from . import fp8_resident, w8
+from . import fp8_resident, w4, w8
 
 # eval-mode weight pre-layout: keep a [E, N, K] (k-major) copy of weights stored [E, K, N]; 0 disables
 _PREPACK = int(os.environ.get("TUTEL_AMD_PREPACK", "1")) != 0
@@ -45,6 +48,9 @@ _NATIVE_FP32 = int(os.environ.get("TUTEL_AMD_NATIVE_FP32", "0")) != 0
 # opt-in: bf16 / fp16 experts in inference stream their weights as FP8 (e4m3) codes (csrc/expert_gemm_w8.hip); the default of every
 # module's `fp8_weights` switch.  Off: nothing changes
 _FP8_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP8_WEIGHTS", "0")) != 0
+# opt-in: the same experts stream their weights as OCP MXFP4 (csrc/expert_gemm_w4.hip); the default of every module's `fp4_weights`
+# switch.  Off: nothing changes
+_FP4_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP4_WEIGHTS", "0")) != 0
 
 
 def _FFN_FUSED_ON():
@@ -283,6 +289,13 @@ def _run_w8(net, x, R, slot_map):
     return ops.expert_gemm_w8(h, i2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
 
 
+def _run_w4(net, x, R, slot_map):
+    (c1, s1), (c2, s2) = net.w4_params()
+    w1, b1, w2, b2 = _inference_params(net)
+    h = ops.expert_gemm_w4(x, c1, s1, b1, w1.size(1), w1.size(2), act=net.fused_activation(), slot_map=slot_map, R=R)
+    return ops.expert_gemm_w4(h, c2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
+
+
 _W8_DTYPES = _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16))
 _W8_SHAPE = _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
                    lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K))
@@ -306,7 +319,23 @@ W8 = Engine(
             _rung(W8_CAPTURE_REASON,   # (FP8-resident experts hold their images for good)
                   lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.fp8_frozen and not (
                       net._kmajor.holds("fc1.w8", net.batched_fc1_w, "w8") and net._kmajor.holds("fc2.w8", net.batched_fc2_w, "w8")))))
-ENGINES = (W8, F32)   # the order FusedExpertsNetwork.forward tries them in; their dtype checks exclude each other
+# the FP4 switch's own rungs, shared with SwiGLU experts
+_SWITCH_W4 = _rung("fp4_weights is off (TUTEL_AMD_FP4_WEIGHTS)", lambda net, x, ctx, mb: not net.fp4_weights)
+_W4_NOT_W8 = _rung("fp8_weights is on as well (one weight format per module)", lambda net, x, ctx, mb: net.fp8_weights)
+_W4_NOT_FROZEN = _rung("the module is FP8-resident", lambda net, x, ctx, mb: net.fp8_frozen)
+# bf16 / fp16 experts in inference reading MXFP4 weights: the W8 ladder's rungs from _SKIP on, then its own shape and capture rungs
+W4 = Engine(
+    ran="_fp4_weights_ran", entry="tutel_amd_expert_gemm_w4", run=_run_w4,
+    ladder=(_SWITCH_W4, _W4_NOT_W8, _W4_NOT_FROZEN, _SKIP, _DEVICE, _AUTOGRAD_W8, _TRAINING_W8,
+            _AUTOCAST, _W8_DTYPES, _GATHERED, _MEGABLOCKS, _ACTIVATION,
+            _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
+                   lambda x, N, K: ops.gemm_w4_supported(x.dtype, N, K)),
+            _rung(W8_CAPTURE_REASON,
+                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not (
+                      net._kmajor.holds("fc1.w4", net.batched_fc1_w, "w4") and net._kmajor.holds("fc2.w4", net.batched_fc2_w, "w4")))))
+# the order FusedExpertsNetwork.forward tries them in.  W8 and W4 exclude each other by W4's second rung (with both switches on FP8
+# runs as it does alone), and either excludes F32 by dtype; an engine that is switched off is asked its first rung and nothing else
+ENGINES = (W8, W4, F32)
 
 
 class FusedExpertsNetwork(torch.nn.Module):
@@ -344,6 +373,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         self._kmajor = KMajorCache()
         # FP8 (e4m3) weights in inference, W8A16 (the W8 engine); the 16-bit parameters stay as they are
         self.fp8_weights = _FP8_WEIGHTS
+        # MXFP4 weights in inference, W4A16 (the W4 engine); the 16-bit parameters stay as they are
+        self.fp4_weights = _FP4_WEIGHTS
 
         E, H = num_experts_per_device, self.hidden_size
         self.batched_fc1_w = torch.nn.Parameter(torch.empty(E, H, model_dim))
@@ -478,6 +509,19 @@ class FusedExpertsNetwork(torch.nn.Module):
     def forward_fused_w8(self, x, ctx, R=None, slot_map=None):
         return self.forward_engine(W8, x, R, slot_map)
 
+    def w4_refusal(self, x, ctx, megablocks_size=None):
+        return self.engine_refusal(W4, x, ctx, megablocks_size)
+
+    def forward_fused_w4(self, x, ctx, R=None, slot_map=None):
+        return self.forward_engine(W4, x, R, slot_map)
+
+    def w4_params(self):
+        """((codes1, scales1), (codes2, scales2)): the MXFP4 images of fc1 (read as stored, k-major) and fc2 (from its [E, H, M_out]
+        storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy"""
+        p1 = self._kmajor.derived("fc1.w4", self.batched_fc1_w, "w4", lambda w: w4.prepare(w, True))
+        p2 = self._kmajor.derived("fc2.w4", self.batched_fc2_w, "w4", lambda w: w4.prepare(w, False))
+        return p1, p2
+
     def w8_params(self):
         """((image1, scale1), (image2, scale2)): the FP8 images and scales of fc1 (read as stored, k-major) and fc2 (from its
         [E, H, M_out] storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy; after fp8_freeze()
@@ -584,12 +628,15 @@ class FusedExpertsNetwork(torch.nn.Module):
     def forward(self, x, ctx):
         if self.skip_expert:
             return x
-        # the opt-in engines (W8 in front of the default GEMMs, F32 behind them); the reason one did not run is kept for the caller
+        # the opt-in engines (W8 and W4 in front of the default GEMMs, F32 behind them); the reason one did not run is kept for the caller
         y = self._forward_if_admitted(W8, x, ctx)
         if y is not None:
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
             raise RuntimeError(fp8_resident.REFUSED + (self.engine_refusal(W8, x, ctx) or "the input is not [E_loc, R, M]"))
+        y = self._forward_if_admitted(W4, x, ctx)
+        if y is not None:
+            return y
 
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)

@@ -17,6 +17,9 @@ Forward:
     are derived copies in the KMajorCache (experts/w8.py).  w8_refusal names why a forward keeps its 16-bit weights.  module.fp8_freeze()
     makes the images the module's own buffers and frees the 16-bit weights (experts/fp8_resident.py): a forward that w8_refusal
     refuses then raises;
+  * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same two launches over e2m1 codes with one
+    power-of-two scale byte per 32 values along K (tutel_amd_expert_gemm_w4_glu, then tutel_amd_expert_gemm_w4 on W_fc3; experts/w4.py).
+    w4_refusal names why a forward does not take it; the packed dropless forward keeps its 16-bit path;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
 the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.  With
@@ -29,7 +32,7 @@ import torch
 
 from .. import net, ops
 from . import ffn as _ffn
-from . import fp8_resident, w8
+from . import fp8_resident, w4, w8
 from .ffn import KMajorCache, classify_activation, _PREPACK
 
 
@@ -48,6 +51,15 @@ _W8_SHAPE = _ffn._rung("the shape is not covered (M a multiple of 64, H a multip
 W8_LADDER = (
     _ffn._SWITCH_W8, _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE,
     _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w8_cached()),
+)
+# the same for MXFP4 weights (W4A16): the FP4 switch's rungs, the W8 ladder's from the device rung on, its own shape and capture rungs
+_W4_SHAPE = _ffn._rung("the shape is not covered (M a multiple of 64, H a multiple of 64)",
+                       lambda net, x, ctx, mb: not (ops.gemm_w4_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
+                                                    and ops.gemm_w4_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1])))
+W4_LADDER = (
+    _ffn._SWITCH_W4, _ffn._W4_NOT_W8, _ffn._W4_NOT_FROZEN,
+    _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W4_SHAPE,
+    _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w4_cached()),
 )
 # the rungs a module answers without a forward, in the ladder's order: what fp8_freeze() requires
 W8_STATIC = (_ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE)
@@ -80,6 +92,8 @@ class LlamaFFNNetwork(torch.nn.Module):
         self._kmajor = KMajorCache()
         # FP8 (e4m3) weights in inference, W8A16; the 16-bit parameters stay as they are
         self.fp8_weights = _ffn._FP8_WEIGHTS
+        # MXFP4 weights in inference, W4A16; the 16-bit parameters stay as they are
+        self.fp4_weights = _ffn._FP4_WEIGHTS
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -185,6 +199,52 @@ class LlamaFFNNetwork(torch.nn.Module):
             pass
         return self.forward_fused_w8(x.contiguous()) if why is None else None
 
+    # -- MXFP4 weights (W4A16) ------------------------------------------------------------------
+    def w4_refusal(self, x, ctx):
+        """why this forward keeps its 16-bit weights (a string: the first failing check of W4_LADDER), or None when it reads MXFP4"""
+        reasons = (check(self, x, ctx, None) for check in W4_LADDER)
+        return next((why for why in reasons if why is not None), None)
+
+    def _w4_gate_up_key(self, w2):
+        return ("w4.glu", KMajorCache._key(w2))
+
+    def w4_cached(self):
+        w1, w2, w3 = self._w8_views()
+        return self._kmajor.holds("fc12.w4", w1, self._w4_gate_up_key(w2)) and self._kmajor.holds("fc3.w4", w3, "w4")
+
+    def w4_params(self):
+        """((codes_gu, scales_gu), (codes3, scales3)): the interleaved gate / up MXFP4 image of (W_fc1, W_fc2) and the image of W_fc3,
+        all read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes"""
+        w1, w2, w3 = self._w8_views()
+        gu = self._kmajor.derived("fc12.w4", w1, self._w4_gate_up_key(w2), lambda w: w4.prepare_gate_up(w, w2.detach(), False))
+        p3 = self._kmajor.derived("fc3.w4", w3, "w4", lambda w: w4.prepare(w, False))
+        return gu, p3
+
+    def forward_fused_w4(self, x):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M] in two launches: gate and up over one MXFP4 image, then W_fc3"""
+        (cgu, sgu), (c3, s3) = self.w4_params()
+        _, M, H = self.W_fc1_full_shape
+        h = ops.expert_gemm_w4_glu(x, cgu, sgu, H, M, act=self.fused_activation())
+        y = ops.expert_gemm_w4(h, c3, s3, None, M, H) if h is not None else None
+        if y is None:   # the ladder asked the library's own coverage queries: a refusal here is a bug, never a quiet forward elsewhere
+            from .. import _lib
+            raise _lib.TutelAmdError("the FP4 expert GEMMs refused a shape their own queries admit: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
+    def _forward_if_w4(self, x, ctx):
+        """forward()'s FP4 step: the output, or None where the switch is off or a check refuses -- the reason is kept for the caller"""
+        if not self.fp4_weights:
+            return None
+        why = self.w4_refusal(x, ctx)
+        if why is None and not (x.dim() == 3 and x.size(0) == self.W_fc1_full_shape[0] and x.size(2) == self.W_fc1_full_shape[1]):
+            why = "the input is not [E_loc, R, M]"
+        try:
+            setattr(ctx, "_fp4_weights_ran", True if why is None else why)
+        except AttributeError:
+            pass
+        return self.forward_fused_w4(x.contiguous()) if why is None else None
+
     def invalidate_prepacked(self):
         self._kmajor.invalidate()
 
@@ -231,6 +291,9 @@ class LlamaFFNNetwork(torch.nn.Module):
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
             raise RuntimeError(fp8_resident.REFUSED + (self.w8_refusal(x, ctx) or "the input is not [E_loc, R, M]"))
+        y = self._forward_if_w4(x, ctx)
+        if y is not None:
+            return y
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous())
         w1 = self._get_gathered_param(self.W_fc1, self.W_fc1_full_shape, ctx.group)

@@ -406,6 +406,8 @@ class MOELayer(torch.nn.Module):
                 if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights and not (
                         self.dropless_packed_fp8 and isinstance(self._fp8_weights_ran, str)):   # (the FP8 ladder's own reason stays)
                     self._fp8_weights_ran = "the packed dropless forward has no FP8 GEMM"   # it keeps its 16-bit one-call path
+                if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp4_weights and not isinstance(self._fp4_weights_ran, str):
+                    self._fp4_weights_ran = "the packed dropless forward has no FP4 GEMM"
                 y, l_aux, cnt, cap = res
                 self.megablocks_size = megablocks_size
                 self.dispatch_count = cnt
@@ -465,7 +467,7 @@ class MOELayer(torch.nn.Module):
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
-        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_weights_ran: True, or why this forward's experts did not take the engine
+        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_weights_ran, _fp4_weights_ran: True, or why this forward's experts did not take the engine
             setattr(self, engine.ran, None)
         if self.skip_moe:
             out = input
@@ -507,6 +509,8 @@ class MOELayer(torch.nn.Module):
         elif isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
             # SwiGLU experts: the same report (LlamaFFNNetwork.forward sets True, or a later reason)
             self._fp8_weights_ran = self.experts.w8_refusal(x, self)
+        if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp4_weights:
+            self._fp4_weights_ran = self.experts.w4_refusal(x, self)
         if getattr(self.experts, "fp8_frozen", False):
             # FP8-resident experts: what the ladder knows before routing decides here, in front of every launch -- no path below
             # may reach for 16-bit weights that are gone.  (Walked with megablocks_size 0: the packed FP8 forward takes any; the

@@ -536,6 +536,75 @@ def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None,
     return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu", out)
 
 
+def gemm_w4_supported(dtype, N, K):
+    """shapes the W4A16 grouped GEMM (tutel_amd_expert_gemm_w4) takes: bf16 / fp16 activations, K % 64 == 0, N % 32 == 0 -- the
+    library's own answer"""
+    if dtype not in _DT:
+        return False
+    return bool(_lib.lib().tutel_amd_expert_gemm_w4_supported(_DT[dtype], int(N), int(K)))
+
+
+def _w4_image(codes, scales):
+    """the checks the two W4A16 wrappers share -> (E_loc, an expert's code bytes, an expert's scale bytes)"""
+    assert codes.dtype == torch.uint8 and codes.is_contiguous() and scales.dtype == torch.uint8 and scales.is_contiguous()
+    E_loc = codes.shape[0]
+    assert scales.shape[0] == E_loc and codes.numel() % max(E_loc, 1) == 0 and scales.numel() % max(E_loc, 1) == 0
+    return E_loc, codes.numel() // max(E_loc, 1), scales.numel() // max(E_loc, 1)
+
+
+def expert_gemm_w4(a, codes, scales, bias, N, K, act="none", slot_map=None, R=None, out=None, row_counts=None):
+    """W4A16: D[e,r,n] = act(acc + bias[e,n]) rounded once to a.dtype, acc the fp32 sum over k of a[e,r,k] times the exact value of the
+    MXFP4 weight (e, n, k) -- its e2m1 code times its block's power-of-two scale (the contract of include/tutel_amd.h).
+
+    a: [E_loc, R, K] contiguous bf16 / fp16, or -- with slot_map [E_loc * R] -- the token array [T, K] whose rows fc1 gathers (negative
+    slots read the zero row).  codes, scales: experts/w4.py::pack's uint8 images of the [E_loc, N, K] weights; bias [E_loc, N] in
+    a.dtype or None, its rows may be strided.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, codes, scales, bias, out, slot_map, row_counts)
+    E_loc, wb, sb = _w4_image(codes, scales)
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
+    if out is None:
+        out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
+    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
+    rc = _lib.lib().tutel_amd_expert_gemm_w4(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        _ptr(codes), wb, _ptr(scales), sb,
+        _ptr(bias), (bias.stride(0) if bias is not None else 0),
+        _ptr(out), R * N, 0, max(R, 1), N,
+        E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4", out)
+
+
+def gemm_w4_glu_supported(dtype, H, K):
+    """shapes the W4A16 gate / up GEMM (tutel_amd_expert_gemm_w4_glu) takes: bf16 / fp16 activations, K % 64 == 0, H % 16 == 0 -- the
+    library's own answer"""
+    if dtype not in _DT:
+        return False
+    return bool(_lib.lib().tutel_amd_expert_gemm_w4_glu_supported(_DT[dtype], int(H), int(K)))
+
+
+def expert_gemm_w4_glu(a, codes, scales, H, K, act="silu", slot_map=None, R=None, out=None, row_counts=None):
+    """W4A16 gate and up products of a SwiGLU expert in ONE launch: D[e,r,n] = round(float(round(act(gacc))) * uacc), gacc / uacc the
+    fp32 sums over k of a[e,r,k] times the exact values of the gate / up MXFP4 weights (the contract of include/tutel_amd.h).
+
+    a: [E_loc, R, K] contiguous bf16 / fp16, or -- with slot_map [E_loc * R] -- the token array [T, K] whose rows are gathered.  codes,
+    scales: experts/w4.py::prepare_gate_up's uint8 images of the interleaved [E_loc, 2 H, K] weights.  -> [E_loc, R, H].  Returns None
+    when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, codes, scales, out, slot_map, row_counts)
+    E_loc, wb, sb = _w4_image(codes, scales)
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
+    if out is None:
+        out = torch.empty([E_loc, R, H], dtype=a.dtype, device=a.device)
+    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, H)
+    rc = _lib.lib().tutel_amd_expert_gemm_w4_glu(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        _ptr(codes), wb, _ptr(scales), sb,
+        _ptr(out), R * H, 0, max(R, 1), H,
+        E_loc, R, H, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4_glu", out)
+
+
 INT32_MAX = 2 ** 31 - 1
 
 
