@@ -444,6 +444,44 @@ int tutel_amd_quantize_w8(const void *W, int dtype, int w_kmajor, int64_t w_stri
                           int64_t wq_stride_e, float *scale, int64_t scale_stride_e, int image_channels, int group, int group_stride,
                           int group_offset, int32_t *status, tutel_stream_t stream);
 
+/* The quantiser of the W4A16 weights (csrc/quantize_w4.hip): reads a parameter as it is stored and writes the code image and the scale
+ * image of tutel_amd_expert_gemm_w4 / _w4_glu directly, in ONE pass -- an MX scale covers 32 values along K, so the parameter is read
+ * once and the images are written once; no fp32 copy, no intermediate code tensor, no permuted copies.
+ * Source: exactly tutel_amd_quantize_w8's -- expert e at W + e * w_stride_e ELEMENTS of `dtype` (TUTEL_BF16, TUTEL_F16 or TUTEL_F32),
+ * element (n, k) at n * ldw + k (w_kmajor = 1) or k * ldw + n (w_kmajor = 0); nothing outside the N x K elements of an expert is read.
+ * act_dtype (TUTEL_BF16 or TUTEL_F16): the dtype of the activations the image will meet; it selects the admitted scale bytes
+ * [lo, hi] = [2, 252] or [114, 140] (tutel_amd_expert_gemm_w4 above).
+ * Image channel map: tutel_amd_quantize_w8's four parameters with the same meaning, c(n) = (n / group) * group_stride + group_offset +
+ * n % group, applied to the code image (expert e at Wq + e * wq_stride_e BYTES) and the scale image (expert e at Ws + e * s_stride_e
+ * BYTES) alike, both image_channels wide.  A SwiGLU gate / up pair is two calls into ONE pair of images of 2 H channels: group = 16,
+ * group_stride = 32, group_offset = 0 (gate) and 16 (up) -- exactly w8.py::interleave_gate_up, then w4.py::pack.  A call writes only
+ * the 16-byte lane chunks and the scale dwords of its own channels.  Scale padding: a channel has ceil(K / 128) scale dwords; where
+ * K % 128 != 0 the call itself writes the bytes past K / 32 blocks as 127 (the images may come from uninitialised memory).
+ * Numeric contract (part of the interface): the images equal tutel_amd/experts/w4.py::prepare (a gate / up pair: prepare_gate_up) run
+ * on a CPU, BIT FOR BIT.  Per block of 32 consecutive k of one channel:
+ *     amax  = the largest |w| of the block, taken on the bit pattern of fp32(w) without its sign (inf and every NaN come out on top)
+ *     s     = clamp((fp32 exponent field of amax) - 2, lo, hi);   an all-zero block: s = 127 and all codes 0
+ *     code  = fp32(w) / 2^(s - 127) rounded to nearest on the e2m1 grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}: midpoints 0.25 / 0.75 / 1.25 /
+ *             1.75 / 2.5 / 3.5 / 5, a tie goes to the neighbour with mantissa bit 0 (0, 1, 1, 2, 2, 4, 4); saturated at +-6; the sign
+ *             bit 0x8 is set for a negative weight unless it rounds to zero: a value that rounds to zero gets code 0x0 whatever its sign
+ *   The rounding is done as integer comparisons on bit patterns: the codes do not depend on the kernel's denormal mode (with s = 2 the
+ *   quotient of a small weight is an fp32 subnormal), and fp32 subnormal weights are quantised like any other.
+ * Non-finite weights: *status is ONE int32 the caller presets to INT32_MAX; a block that holds an inf or a NaN does an atomicMin of
+ * e * N + n on it; that block's codes and scale byte are unspecified (the byte stays inside [lo, hi]).
+ * Wq == NULL and Ws == NULL: the finiteness check alone -- the status word, nothing else is written.
+ * Covered (tutel_amd_quantize_w4_supported == 1: a pure function, no HIP call): dtype one of the three, act_dtype bf16 / fp16,
+ * K % 64 == 0, image_channels % 32 == 0, group % 16 == 0, N % group == 0 (a plain parameter: N = image_channels, a multiple of 32),
+ * 0 <= group_offset and group_offset + group <= group_stride, (N / group) * group_stride <= image_channels; and, of the call: ldw >= K (k-major) or N (n-major), w_stride_e >= one
+ * expert's matrix, ldw and w_stride_e multiples of 16 bytes, wq_stride_e % 16 == 0 and >= image_channels * K / 2, s_stride_e % 4 == 0
+ * and >= image_channels * ceil(K / 128) * 4, E * N and the workgroup count E * ceil(N / 32) * ceil(K / 256) below 2^31, W and Wq 16-byte
+ * aligned.  Anything else returns TUTEL_AMD_ENOTSUP with its reason and nothing enqueued; E == 0 is a successful no-op.  Every check
+ * precedes the first HIP call.  One launch, no workspace, capturable. */
+int tutel_amd_quantize_w4_supported(int dtype, int act_dtype, int N, int K, int image_channels, int group, int group_stride,
+                                    int group_offset);
+int tutel_amd_quantize_w4(const void *W, int dtype, int act_dtype, int w_kmajor, int64_t w_stride_e, int ldw, int E, int N, int K,
+                          void *Wq, int64_t wq_stride_e, void *Ws, int64_t s_stride_e, int image_channels, int group,
+                          int group_stride, int group_offset, int32_t *status, tutel_stream_t stream);
+
 /* The whole expert FFN in ONE persistent launch (round 6; csrc/expert_ffn.hip) -- OPT-IN: TUTEL_OPT_FFN_FUSED = 1.
  *     hid[e] = act(A[e] @ W1[e]^T + b1[e]),   D[e] = hid[e] @ W2[e]^T + b2[e]        e < E_loc, R rows per expert
  * -- what FusedExpertsNetwork.forward computes with two batched matmuls, two bias adds and the activation

@@ -58,6 +58,8 @@ SIGNATURES = {
                                           _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "tutel_amd_quantize_w8_supported": (_i, [_i] * 7),
     "tutel_amd_quantize_w8": (_i, [_vp, _i, _i, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "tutel_amd_quantize_w4_supported": (_i, [_i] * 8),
+    "tutel_amd_quantize_w4": (_i, [_vp, _i, _i, _i, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "tutel_amd_expert_ffn": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i,
                                   _i, _i, _i, _i, _i, _i, _i, _vp]),
     "tutel_amd_expert_gemm_glu": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _i64,

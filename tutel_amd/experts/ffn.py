@@ -24,7 +24,9 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     frees the 16-bit weights: the same launches on the same bits, inference only, FP8 state dicts (experts/fp8_resident.py);
   * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same experts read e2m1 codes with one
     power-of-two scale byte per 32 values along K (W4A16; the widened weights are exact, activations are not quantised) -- two launches
-    of tutel_amd_expert_gemm_w4; the images are derived copies in the KMajorCache (experts/w4.py), the 16-bit parameters stay;
+    of tutel_amd_expert_gemm_w4; the images are derived copies in the KMajorCache (experts/w4.py).  module.fp4_freeze() makes the code
+    and scale images the module's own buffers, written by the HIP quantiser (csrc/quantize_w4.hip), and frees the 16-bit weights:
+    0.27 x the memory, the same launches on the same bits, inference only, MXFP4 state dicts (experts/fp8_resident.py);
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
@@ -323,16 +325,19 @@ W8 = Engine(
 _SWITCH_W4 = _rung("fp4_weights is off (TUTEL_AMD_FP4_WEIGHTS)", lambda net, x, ctx, mb: not net.fp4_weights)
 _W4_NOT_W8 = _rung("fp8_weights is on as well (one weight format per module)", lambda net, x, ctx, mb: net.fp8_weights)
 _W4_NOT_FROZEN = _rung("the module is FP8-resident", lambda net, x, ctx, mb: net.fp8_frozen)
+_W4_SHAPE = _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
+                   lambda x, N, K: ops.gemm_w4_supported(x.dtype, N, K))
 # bf16 / fp16 experts in inference reading MXFP4 weights: the W8 ladder's rungs from _SKIP on, then its own shape and capture rungs
 W4 = Engine(
     ran="_fp4_weights_ran", entry="tutel_amd_expert_gemm_w4", run=_run_w4,
     ladder=(_SWITCH_W4, _W4_NOT_W8, _W4_NOT_FROZEN, _SKIP, _DEVICE, _AUTOGRAD_W8, _TRAINING_W8,
             _AUTOCAST, _W8_DTYPES, _GATHERED, _MEGABLOCKS, _ACTIVATION,
-            _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
-                   lambda x, N, K: ops.gemm_w4_supported(x.dtype, N, K)),
-            _rung(W8_CAPTURE_REASON,
-                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not (
+            _W4_SHAPE,
+            _rung(W8_CAPTURE_REASON,   # (FP4-resident experts hold their images for good)
+                  lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.fp4_frozen and not (
                       net._kmajor.holds("fc1.w4", net.batched_fc1_w, "w4") and net._kmajor.holds("fc2.w4", net.batched_fc2_w, "w4")))))
+# the rungs of the W4 ladder that a module answers without a forward, in the ladder's order: what fp4_freeze() requires
+W4_STATIC = (_W4_NOT_W8, _W4_NOT_FROZEN, _SKIP, _DEVICE, _TRAINING_W8, _W8_DTYPES, _GATHERED, _ACTIVATION, _W4_SHAPE)
 # the order FusedExpertsNetwork.forward tries them in.  W8 and W4 exclude each other by W4's second rung (with both switches on FP8
 # runs as it does alone), and either excludes F32 by dtype; an engine that is switched off is asked its first rung and nothing else
 ENGINES = (W8, W4, F32)
@@ -340,6 +345,7 @@ ENGINES = (W8, W4, F32)
 
 class FusedExpertsNetwork(torch.nn.Module):
     fp8_frozen = False   # True after fp8_freeze(): the FP8 images are the module's own buffers, the 16-bit weights are gone
+    fp4_frozen = False   # True after fp4_freeze(): the same with the MXFP4 code and scale images
 
     def __init__(self, model_dim, hidden_size_per_expert, num_experts_per_device, sharded_count,
                  activation_fn=None, activation_fn_with_self=None, output_dim=None,
@@ -436,7 +442,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def can_fuse(self, x, ctx):
         """the plain fused route: this rank's own local experts (no weight gathering), no autograd, MFMA-able shapes.  (False does NOT
         mean ATen: adaptive_r = 0 / sharded experts gather their weights in forward() and run the same MFMA kernel on the result.)"""
-        if self.skip_expert or self.fp8_frozen or not x.is_cuda or not self._no_autograd(x):
+        if self.skip_expert or self.fp8_frozen or self.fp4_frozen or not x.is_cuda or not self._no_autograd(x):
             return False
         if getattr(ctx, "adaptive_degree", 1) == 0 or getattr(ctx, "sharded_count", 1) > 1:
             return False
@@ -448,7 +454,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def can_fuse_training(self, x, ctx):
         """the same local experts WITH autograd: bf16 / fp16 (or autocast over fp32 master weights), ReLU, all four GEMM
         products MFMA-able (forward K = M, H; backward K = M_out, H)"""
-        if (not _TRAIN_FUSED or self.skip_expert or self.fp8_frozen or not x.is_cuda or x.dim() != 3 or self._no_autograd(x)
+        if (not _TRAIN_FUSED or self.skip_expert or self.fp8_frozen or self.fp4_frozen or not x.is_cuda or x.dim() != 3 or self._no_autograd(x)
                 or getattr(ctx, "adaptive_degree", 1) == 0 or getattr(ctx, "sharded_count", 1) > 1):
             return False
         w1, w2 = self.batched_fc1_w, self.batched_fc2_w
@@ -468,7 +474,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def admitted_engine(self, x, ctx, megablocks_size=None):
         """the opt-in engine this forward's experts run on, or None: the default GEMMs.  An engine that is switched off costs its
         switch and nothing else"""
-        engines = (W8,) if self.fp8_frozen else ENGINES
+        engines = (W8,) if self.fp8_frozen else (W4,) if self.fp4_frozen else ENGINES
         return next((e for e in engines if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
 
     def forward_engine(self, engine, x, R=None, slot_map=None):
@@ -517,7 +523,10 @@ class FusedExpertsNetwork(torch.nn.Module):
 
     def w4_params(self):
         """((codes1, scales1), (codes2, scales2)): the MXFP4 images of fc1 (read as stored, k-major) and fc2 (from its [E, H, M_out]
-        storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy"""
+        storage), derived copies re-quantised whenever the KMajorCache would rebuild a k-major copy; after fp4_freeze() the module's
+        own buffers"""
+        if self.fp4_frozen:
+            return (self.fc1_w4, self.fc1_w4_scale), (self.fc2_w4, self.fc2_w4_scale)
         p1 = self._kmajor.derived("fc1.w4", self.batched_fc1_w, "w4", lambda w: w4.prepare(w, True))
         p2 = self._kmajor.derived("fc2.w4", self.batched_fc2_w, "w4", lambda w: w4.prepare(w, False))
         return p1, p2
@@ -535,8 +544,9 @@ class FusedExpertsNetwork(torch.nn.Module):
     def fused_params(self, dtype):
         """(w1, b1, w2, b2, w2_kmajor) of this rank's experts in the GEMM's compute dtype: the parameters themselves, or
         cached casts under autocast; fc2 as a k-major copy in eval mode."""
-        if self.fp8_frozen:
-            raise RuntimeError(fp8_resident.REFUSED + "the 16-bit grouped GEMM was asked for")
+        frozen = fp8_resident.resident(self)
+        if frozen is not None:
+            raise RuntimeError(frozen.refused + "the 16-bit grouped GEMM was asked for")
         w1, b1, w2, b2 = self.batched_fc1_w, self.batched_fc1_bias, self.batched_fc2_w, self.batched_fc2_bias
         cast = None if w1.dtype == dtype else dtype
         kmajor = self.w2_kmajor_now()
@@ -589,8 +599,9 @@ class FusedExpertsNetwork(torch.nn.Module):
         self._kmajor.invalidate()
 
     def train(self, mode=True):
-        if mode and self.fp8_frozen:
-            raise RuntimeError(fp8_resident.REFUSED + _TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
+        frozen = fp8_resident.resident(self)
+        if mode and frozen is not None:
+            raise RuntimeError(frozen.refused + _TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
         self._kmajor.invalidate()
         return super().train(mode)
 
@@ -624,12 +635,27 @@ class FusedExpertsNetwork(torch.nn.Module):
         way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP8 ladder refuses"""
         return fp8_resident.freeze(self)
 
+    # -- MXFP4-resident form: the same machinery under fp8_resident.FP4 -----------------------------------------------------
+    def _fp4_steps(self):
+        return tuple(step._replace(buffer=step.buffer.replace("_w8", "_w4")) for step in self._fp8_steps())
+
+    def _fp4_static_refusal(self):
+        """the first static rung of the W4 ladder this module fails (None: fp4_freeze() may run)"""
+        x, ctx = fp8_resident.static_stand_ins(self.batched_fc1_w, self.sharded_count)
+        return fp8_resident.first_reason(self, W4_STATIC, x, ctx)
+
+    def fp4_freeze(self):
+        """Quantise fc1 and fc2 to MXFP4 with the HIP quantiser, keep code and scale images as buffers (fc1_w4, fc1_w4_scale, fc2_w4,
+        fc2_w4_scale) and free the 16-bit weights, one parameter at a time; the biases stay.  Inference only from then on, and no
+        way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP4 ladder refuses"""
+        return fp8_resident.freeze(self, fp8_resident.FP4)
+
     # -- gathered-weight modes + the reference-equivalent ATen path ------------------------------
     def forward(self, x, ctx):
         if self.skip_expert:
             return x
         # the opt-in engines (W8 and W4 in front of the default GEMMs, F32 behind them); the reason one did not run is kept for the caller
-        y = self._forward_if_admitted(W8, x, ctx)
+        y = None if self.fp4_frozen else self._forward_if_admitted(W8, x, ctx)
         if y is not None:
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
@@ -637,6 +663,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         y = self._forward_if_admitted(W4, x, ctx)
         if y is not None:
             return y
+        if self.fp4_frozen:
+            raise RuntimeError(fp8_resident.REFUSED_FP4 + (self.engine_refusal(W4, x, ctx) or "the input is not [E_loc, R, M]"))
 
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous(), ctx)

@@ -15,6 +15,10 @@ the images and scales the module's own state and frees the 16-bit weights:
     checkpoint's tensors, one at a time.
 
 The two expert classes describe themselves by `_fp8_steps()` (below) and `_fp8_static_refusal()`; everything else is written once here.
+
+MXFP4-resident experts (`module.fp4_freeze()`) are the same machinery under another Format (below): the buffers are the W4A16 code
+image and scale image (`fc1_w4`, `fc1_w4_scale`, ...), written by ops.quantize_w4, and the ladder that decides is the W4 one.  A
+module is resident in one format at most: fp8_freeze() and fp4_freeze() refuse each other.
 """
 import types
 from typing import NamedTuple
@@ -24,6 +28,46 @@ import torch
 from .. import ops
 
 REFUSED = "FP8-resident experts (fp8_freeze) hold no 16-bit weights to fall back to: "
+REFUSED_FP4 = "FP4-resident experts (fp4_freeze) hold no 16-bit weights to fall back to: "
+
+
+class Format(NamedTuple):
+    """one resident form, by what differs between them"""
+    name: str            # "FP8" / "FP4", as the messages spell it
+    method: str          # the module's freezing method
+    flag: str            # the module's attribute that is True once frozen
+    switch: str          # the module's engine switch, on with the flag
+    steps: str           # the module's method that lists its Steps
+    static_refusal: str  # the module's method that walks the static rungs of the format's ladder
+    buffers: object      # (step, E) -> ((shape, dtype) of `buffer`, (shape, dtype) of `buffer`_scale)
+    quantize: object     # (w, src, image, scale, check_only) -> (image, scale), or None where the library refuses
+    entry: str           # the library entry point `quantize` calls
+    refused: str         # what a forward that would read the 16-bit weights raises, in front of the ladder's reason
+    no_apply: str        # what a cast or a move raises
+
+
+FP8 = Format(
+    name="FP8", method="fp8_freeze", flag="fp8_frozen", switch="fp8_weights", steps="_fp8_steps", static_refusal="_fp8_static_refusal",
+    buffers=lambda step, E: (([E, step.channels // 32, step.K // 32, 64, 16], torch.uint8), ([E, step.channels], torch.float32)),
+    quantize=lambda w, src, image, scale, check_only: ops.quantize_w8(w, src.w_kmajor, image=image, scale=scale,
+                                                                      channel_map=src.channel_map, check_only=check_only),
+    entry="tutel_amd_quantize_w8", refused=REFUSED,
+    no_apply="FP8-resident experts (fp8_freeze) cannot be cast or moved: the images belong to their device, the scales are fp32")
+FP4 = Format(
+    name="FP4", method="fp4_freeze", flag="fp4_frozen", switch="fp4_weights", steps="_fp4_steps", static_refusal="_fp4_static_refusal",
+    buffers=lambda step, E: (([E, step.channels // 32, step.K // 64, 64, 16], torch.uint8),
+                             ([E, step.channels // 32, (step.K + 127) // 128, 32, 4], torch.uint8)),
+    quantize=lambda w, src, image, scale, check_only: ops.quantize_w4(w, src.w_kmajor, codes=image, scales=scale,
+                                                                      channel_map=src.channel_map, check_only=check_only),
+    entry="tutel_amd_quantize_w4", refused=REFUSED_FP4,
+    no_apply="FP4-resident experts (fp4_freeze) cannot be cast or moved: the images belong to their device and to the dtype they were "
+             "quantised for")
+FORMATS = (FP8, FP4)
+
+
+def resident(mod):
+    """the Format a module is frozen in, or None"""
+    return next((fmt for fmt in FORMATS if getattr(mod, fmt.flag, False)), None)
 
 
 class Source(NamedTuple):
@@ -31,11 +75,12 @@ class Source(NamedTuple):
     name: str           # the parameter's attribute name (and its key in a 16-bit state dict)
     shape: tuple        # [E, N, K] (w_kmajor) or [E, K, N]: the parameter itself, or the view of a flat one
     w_kmajor: bool
-    channel_map: object  # ops.quantize_w8's, None: the plain map
+    channel_map: object  # ops.quantize_w8's / ops.quantize_w4's, None: the plain map
 
 
 class Step(NamedTuple):
-    """one image: the buffers `buffer` [E, channels / 32, K / 32, 64, 16] uint8 and `buffer`_scale [E, channels] fp32"""
+    """one image: the buffers `buffer` and `buffer`_scale, in the shapes of the Format (FP8: [E, channels / 32, K / 32, 64, 16] uint8
+    and [E, channels] fp32)"""
     buffer: str
     sources: tuple
     channels: int
@@ -65,75 +110,85 @@ def _register(mod, step, image, scale):
     mod.register_buffer(step.buffer + "_scale", scale)
 
 
-def _quantise(w, src, image=None, scale=None, check_only=False):
+def _quantise(fmt, w, src, image=None, scale=None, check_only=False):
     if w.data_ptr() % 16 or not w.is_contiguous():
         w = w.clone(memory_format=torch.contiguous_format)
-    res = ops.quantize_w8(w, src.w_kmajor, image=image, scale=scale, channel_map=src.channel_map, check_only=check_only)
+    res = fmt.quantize(w, src, image, scale, check_only)
     if res is None:   # the static rungs asked the GEMMs' coverage, which implies the quantiser's: a refusal here is a bug
         from .. import _lib
-        raise _lib.TutelAmdError("tutel_amd_quantize_w8 refused a shape the FP8 GEMMs admit: " +
+        raise _lib.TutelAmdError(f"{fmt.entry} refused a shape the {fmt.name} GEMMs admit: " +
                                  _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
     return res
 
 
-def freeze(mod):
-    """module.fp8_freeze(): see the module docstring.  Raises ValueError, the module untouched, where a static rung of the FP8
-    ladder fails or a weight is not finite"""
-    if mod.fp8_frozen:
+def freeze(mod, fmt=FP8):
+    """module.fp8_freeze() (fmt FP4: module.fp4_freeze()): see the module docstring.  Raises ValueError, the module untouched, where
+    a static rung of the format's ladder fails, the module is resident in the other format or a weight is not finite"""
+    now = resident(mod)
+    if now is fmt:
         return mod
-    why = mod._fp8_static_refusal()
+    if now is not None:
+        raise ValueError(f"{fmt.method}: the module is {now.name}-resident")
+    why = getattr(mod, fmt.static_refusal)()
     if why is not None:
-        raise ValueError("fp8_freeze: " + why)
-    steps = mod._fp8_steps()
+        raise ValueError(f"{fmt.method}: " + why)
+    steps = getattr(mod, fmt.steps)()
     with torch.no_grad():
         # a non-finite weight raises BEFORE anything is released: the quantiser's first pass alone, which writes nothing
         for step in steps:
             for src in step.sources:
-                _quantise(getattr(mod, src.name).detach().view(src.shape), src, check_only=True)
+                _quantise(fmt, getattr(mod, src.name).detach().view(src.shape), src, check_only=True)
         mod.invalidate_prepacked()   # the derived copies of the 16-bit weights go first
         for step in steps:
             image = scale = None
             for src in step.sources:
-                image, scale = _quantise(getattr(mod, src.name).detach().view(src.shape), src, image, scale)
+                image, scale = _quantise(fmt, getattr(mod, src.name).detach().view(src.shape), src, image, scale)
                 _release(mod, src.name)
             _register(mod, step, image, scale)
     for p in mod.parameters():   # the biases: inference only, nothing here takes a gradient any more
         p.requires_grad_(False)
-    mod.fp8_frozen = mod.fp8_weights = True
+    setattr(mod, fmt.flag, True)
+    setattr(mod, fmt.switch, True)
     return mod
 
 
-def _freeze_empty(mod):
+def _freeze_empty(mod, fmt):
     """the frozen form with unwritten buffers, for a state dict to fill"""
-    for step in mod._fp8_steps():
+    for step in getattr(mod, fmt.steps)():
         dev = getattr(mod, step.sources[0].name).device
         E = step.sources[0].shape[0]
         for src in step.sources:
             _release(mod, src.name)
-        _register(mod, step, torch.empty([E, step.channels // 32, step.K // 32, 64, 16], dtype=torch.uint8, device=dev),
-                  torch.empty([E, step.channels], dtype=torch.float32, device=dev))
+        (ishape, idtype), (sshape, sdtype) = fmt.buffers(step, E)
+        _register(mod, step, torch.empty(ishape, dtype=idtype, device=dev), torch.empty(sshape, dtype=sdtype, device=dev))
     mod.invalidate_prepacked()
     for p in mod.parameters():   # the biases: inference only, nothing here takes a gradient any more
         p.requires_grad_(False)
-    mod.fp8_frozen = mod.fp8_weights = True
+    setattr(mod, fmt.flag, True)
+    setattr(mod, fmt.switch, True)
 
 
 def load_from_state_dict(mod, super_load, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-    """_load_from_state_dict of both expert classes.  FP8 keys into an unfrozen module: it is frozen first (its own static rungs
-    decide, a refusal is a loading error), then the default copy fills the buffers.  16-bit keys into a frozen module: each tensor
-    is quantised into the module's buffers by the HIP quantiser, straight from the checkpoint (a CPU tensor is moved to the device
-    one parameter at a time); mismatches are reported as load_state_dict reports them"""
+    """_load_from_state_dict of both expert classes.  FP8 (or FP4) keys into an unfrozen module: it is frozen first in that format
+    (its own static rungs decide, a refusal is a loading error), then the default copy fills the buffers.  16-bit keys into a frozen
+    module: each tensor is quantised into the module's buffers by the format's HIP quantiser, straight from the checkpoint (a CPU
+    tensor is moved to the device one parameter at a time); mismatches are reported as load_state_dict reports them"""
     mod.invalidate_prepacked()
-    steps = mod._fp8_steps()
-    has8 = any(prefix + step.buffer in state_dict for step in steps)
-    has16 = any(prefix + src.name in state_dict for step in steps for src in step.sources)
-    if not mod.fp8_frozen and has8 and not has16:
-        why = mod._fp8_static_refusal()
-        if why is not None:
-            error_msgs.append(f"{prefix or 'experts'}: the state dict holds FP8-resident experts, which this module cannot become: {why}")
-            return
-        _freeze_empty(mod)
-    if mod.fp8_frozen:
+    fmt = resident(mod)
+    for cand in FORMATS if fmt is None else ():
+        steps = getattr(mod, cand.steps)()
+        has8 = any(prefix + step.buffer in state_dict for step in steps)
+        has16 = any(prefix + src.name in state_dict for step in steps for src in step.sources)
+        if has8 and not has16:
+            why = getattr(mod, cand.static_refusal)()
+            if why is not None:
+                error_msgs.append(f"{prefix or 'experts'}: the state dict holds {cand.name}-resident experts, which this module cannot become: {why}")
+                return
+            _freeze_empty(mod, cand)
+            fmt = cand
+            break
+    if fmt is not None:
+        steps = getattr(mod, fmt.steps)()
         state_dict = {k: v for k, v in state_dict.items() if k.startswith(prefix)}
         for step in steps:
             image, scale = getattr(mod, step.buffer), getattr(mod, step.buffer + "_scale")
@@ -149,12 +204,12 @@ def load_from_state_dict(mod, super_load, state_dict, prefix, local_metadata, st
                     error_msgs.append(f"size mismatch for {key}: copying a param with shape {t.shape} from checkpoint, "
                                       f"the shape in current model is {here.shape}.")
                 elif t.dtype != here.dtype:
-                    error_msgs.append(f"dtype mismatch for {key}: the checkpoint holds {t.dtype}, the FP8-resident module was frozen "
+                    error_msgs.append(f"dtype mismatch for {key}: the checkpoint holds {t.dtype}, the {fmt.name}-resident module was frozen "
                                       f"from {here.dtype} (quantising another dtype gives other codes).")
                 else:
                     try:
                         with torch.no_grad():
-                            _quantise(t.detach().to(image.device).view(src.shape), src, image, scale)
+                            _quantise(fmt, t.detach().to(image.device).view(src.shape), src, image, scale)
                     except ValueError as e:
                         error_msgs.append(f"While copying the parameter named \"{key}\": {e}")
             if any(seen):   # the buffers ARE this checkpoint's weights now (or an error says why not): their keys are not missing
@@ -171,9 +226,10 @@ def load_from_state_dict(mod, super_load, state_dict, prefix, local_metadata, st
 def check_apply(mod, fn):
     """Module._apply of a frozen module (.to(), .cuda(), .half() ...): the images are tied to their device and the scales to fp32 --
     a cast or a move is refused before it touches a buffer"""
-    if not mod.fp8_frozen:
+    fmt = resident(mod)
+    if fmt is None:
         return
-    image = getattr(mod, mod._fp8_steps()[0].buffer)
+    image = getattr(mod, getattr(mod, fmt.steps)()[0].buffer)
     probes = [torch.empty(0, dtype=dt, device=image.device) for dt in (torch.float32, mod._fp8_dtype())]
     if any(out.dtype != p.dtype or out.device != p.device for p, out in ((p, fn(p)) for p in probes)):
-        raise RuntimeError("FP8-resident experts (fp8_freeze) cannot be cast or moved: the images belong to their device, the scales are fp32")
+        raise RuntimeError(fmt.no_apply)

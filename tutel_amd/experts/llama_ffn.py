@@ -19,7 +19,8 @@ Forward:
     refuses then raises;
   * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same two launches over e2m1 codes with one
     power-of-two scale byte per 32 values along K (tutel_amd_expert_gemm_w4_glu, then tutel_amd_expert_gemm_w4 on W_fc3; experts/w4.py).
-    w4_refusal names why a forward does not take it; the packed dropless forward keeps its 16-bit path;
+    w4_refusal names why a forward does not take it; the packed dropless forward keeps its 16-bit path.  module.fp4_freeze() makes
+    the images the module's own buffers, written by the HIP quantiser (csrc/quantize_w4.hip), and frees the 16-bit weights;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
 the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.  With
@@ -61,12 +62,14 @@ W4_LADDER = (
     _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W4_SHAPE,
     _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w4_cached()),
 )
-# the rungs a module answers without a forward, in the ladder's order: what fp8_freeze() requires
+# the rungs a module answers without a forward, in the ladder's order: what fp8_freeze() and fp4_freeze() require
 W8_STATIC = (_ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE)
+W4_STATIC = (_ffn._W4_NOT_W8, _ffn._W4_NOT_FROZEN, _ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W4_SHAPE)
 
 
 class LlamaFFNNetwork(torch.nn.Module):
     fp8_frozen = False   # True after fp8_freeze(): the FP8 images are the module's own buffers, the 16-bit weights are gone
+    fp4_frozen = False   # True after fp4_freeze(): the same with the MXFP4 code and scale images
 
     def _create_sharded_param(self, *full_shape, **kwargs):
         full_shape = torch.Size(full_shape)
@@ -114,7 +117,7 @@ class LlamaFFNNetwork(torch.nn.Module):
         return self._act_cache[key]
 
     def can_fuse(self, x, ctx):
-        if self.fp8_frozen or not x.is_cuda or self.sharded_count > 1 or torch.is_autocast_enabled():
+        if self.fp8_frozen or self.fp4_frozen or not x.is_cuda or self.sharded_count > 1 or torch.is_autocast_enabled():
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
@@ -125,8 +128,9 @@ class LlamaFFNNetwork(torch.nn.Module):
     def kmajor_weights(self):
         """the eval-mode k-major copies (W_fc1 and W_fc2 [E, H, M], W_fc3 [E, M, H]) that forward_fused runs on: the operands of the
         packed dropless forward (impls/ep_native.py, tutel_amd_moe_forward_packed_glu)"""
-        if self.fp8_frozen:
-            raise RuntimeError(fp8_resident.REFUSED + "the 16-bit grouped GEMM was asked for")
+        frozen = fp8_resident.resident(self)
+        if frozen is not None:
+            raise RuntimeError(frozen.refused + "the 16-bit grouped GEMM was asked for")
         w1, w2, w3 = (self.W_fc1.view(self.W_fc1_full_shape), self.W_fc2.view(self.W_fc2_full_shape),
                       self.W_fc3.view(self.W_fc3_full_shape))
         return self._kmajor.get("fc1", w1), self._kmajor.get("fc2", w2), self._kmajor.get("fc3", w3)
@@ -209,12 +213,17 @@ class LlamaFFNNetwork(torch.nn.Module):
         return ("w4.glu", KMajorCache._key(w2))
 
     def w4_cached(self):
+        if self.fp4_frozen:
+            return True
         w1, w2, w3 = self._w8_views()
         return self._kmajor.holds("fc12.w4", w1, self._w4_gate_up_key(w2)) and self._kmajor.holds("fc3.w4", w3, "w4")
 
     def w4_params(self):
         """((codes_gu, scales_gu), (codes3, scales3)): the interleaved gate / up MXFP4 image of (W_fc1, W_fc2) and the image of W_fc3,
-        all read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes"""
+        all read from their [K, N] storage; derived copies re-quantised whenever a parameter they depend on changes; after
+        fp4_freeze() the module's own buffers"""
+        if self.fp4_frozen:
+            return (self.fc12_w4, self.fc12_w4_scale), (self.fc3_w4, self.fc3_w4_scale)
         w1, w2, w3 = self._w8_views()
         gu = self._kmajor.derived("fc12.w4", w1, self._w4_gate_up_key(w2), lambda w: w4.prepare_gate_up(w, w2.detach(), False))
         p3 = self._kmajor.derived("fc3.w4", w3, "w4", lambda w: w4.prepare(w, False))
@@ -249,8 +258,9 @@ class LlamaFFNNetwork(torch.nn.Module):
         self._kmajor.invalidate()
 
     def train(self, mode=True):
-        if mode and self.fp8_frozen:
-            raise RuntimeError(fp8_resident.REFUSED + _ffn._TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
+        frozen = fp8_resident.resident(self)
+        if mode and frozen is not None:
+            raise RuntimeError(frozen.refused + _ffn._TRAINING_W8(types.SimpleNamespace(training=True), None, None, None))
         self._kmajor.invalidate()
         return super().train(mode)
 
@@ -284,9 +294,25 @@ class LlamaFFNNetwork(torch.nn.Module):
         no way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP8 ladder refuses"""
         return fp8_resident.freeze(self)
 
+    # -- MXFP4-resident form: the same machinery under fp8_resident.FP4 -----------------------------------------------------
+    def _fp4_steps(self):
+        return tuple(step._replace(buffer=step.buffer.replace("_w8", "_w4")) for step in self._fp8_steps())
+
+    def _fp4_static_refusal(self):
+        """the first static rung of the W4 ladder this module fails (None: fp4_freeze() may run)"""
+        x, ctx = fp8_resident.static_stand_ins(self.W_fc1)
+        return fp8_resident.first_reason(self, W4_STATIC, x, ctx)
+
+    def fp4_freeze(self):
+        """Quantise gate and up into one MXFP4 image, then W_fc3, with the HIP quantiser; keep code and scale images as buffers
+        (fc12_w4, fc12_w4_scale, fc3_w4, fc3_w4_scale) and free the 16-bit weights, one parameter at a time.  Inference only from
+        then on, and no way back (experts/fp8_resident.py).  ValueError, the module untouched, where a static rung of the FP4 ladder
+        refuses"""
+        return fp8_resident.freeze(self, fp8_resident.FP4)
+
     # -- reference-equivalent ATen path -----------------------------------------------------
     def forward(self, x, ctx):
-        y = self._forward_if_w8(x, ctx)
+        y = None if self.fp4_frozen else self._forward_if_w8(x, ctx)
         if y is not None:
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
@@ -294,6 +320,8 @@ class LlamaFFNNetwork(torch.nn.Module):
         y = self._forward_if_w4(x, ctx)
         if y is not None:
             return y
+        if self.fp4_frozen:
+            raise RuntimeError(fp8_resident.REFUSED_FP4 + (self.w4_refusal(x, ctx) or "the input is not [E_loc, R, M]"))
         if self.can_fuse(x, ctx):
             return self.forward_fused(x.contiguous())
         w1 = self._get_gathered_param(self.W_fc1, self.W_fc1_full_shape, ctx.group)

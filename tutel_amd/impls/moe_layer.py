@@ -201,8 +201,8 @@ class MOELayer(torch.nn.Module):
         else:
             have, want = int(state_dict[key]), self.num_global_experts
             assert have == want, "Failed to load state from checkpoint: the number of global experts mismatch (%s <- %s)" % (want, have)
-        # an FP8-resident state dict (experts/fp8_resident.py) holds images instead of the 16-bit weights: those are not missing
-        steps = self.experts._fp8_steps() if hasattr(self.experts, "_fp8_steps") else ()
+        # an FP8- or FP4-resident state dict (experts/fp8_resident.py) holds images instead of the 16-bit weights: those are not missing
+        steps = [step for fmt in _fp8_resident.FORMATS if hasattr(self.experts, fmt.steps) for step in getattr(self.experts, fmt.steps)()]
         as_fp8 = {src.name for step in steps if prefix + "experts." + step.buffer in state_dict for src in step.sources}
         for name, param in self.experts.named_parameters():
             k = prefix + "experts." + name
@@ -216,8 +216,8 @@ class MOELayer(torch.nn.Module):
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def train(self, mode=True):
-        if mode and getattr(getattr(self, "experts", None), "fp8_frozen", False):
-            self.experts.train(True)   # raises (FP8-resident experts are inference only) before any module has changed its mode
+        if mode and _fp8_resident.resident(getattr(self, "experts", None)) is not None:
+            self.experts.train(True)   # raises (resident experts are inference only) before any module has changed its mode
         return super().train(mode)
 
     def extra_repr(self):
@@ -277,8 +277,8 @@ class MOELayer(torch.nn.Module):
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
         # reason: ep_native.packed_cover, asked in _run_native_moe)
         swiglu_packed = stage == "before_routing" and cf <= 0 and self.dropless_packed and isinstance(self.experts, LlamaFFNNetwork)
-        if getattr(self.experts, "fp8_frozen", False) and not packed_fp8:
-            swiglu_packed = False   # FP8-resident experts: the one-call pipelines have no FP8 GEMM and there are no 16-bit weights
+        if _fp8_resident.resident(self.experts) is not None and not packed_fp8:
+            swiglu_packed = False   # resident experts: the one-call pipelines have no FP8 / FP4 GEMM and there are no 16-bit weights
         packed_fp8 = packed_fp8 and stage == "before_routing" and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))
         fusable = (x.is_cuda and len(reserve_shape) == 1 and (swiglu_packed or packed_fp8 or isinstance(self.experts, FusedExpertsNetwork))
                    and not C.SKIP_A2A and self.num_global_experts >= W and self.adaptive_degree != 0 and logits.dim() == 2
@@ -486,7 +486,7 @@ class MOELayer(torch.nn.Module):
                 x = x.to(p.dtype)
                 break
             else:
-                if getattr(self.experts, "fp8_frozen", False):   # no parameter left to ask: the dtype the experts were frozen from
+                if _fp8_resident.resident(self.experts) is not None:   # no parameter left to ask: the dtype the experts were frozen from
                     x = x.to(self.experts._fp8_dtype())
         if x.is_cuda and x.data_ptr() % 16:
             x = x.clone()   # an offset view of a larger buffer: the kernels fetch 16-byte vectors, upstream takes any tensor (ops._a16)
@@ -519,6 +519,15 @@ class MOELayer(torch.nn.Module):
             if why is not None:
                 self._fp8_weights_ran = why
                 raise RuntimeError(_fp8_resident.REFUSED + why)
+        if getattr(self.experts, "fp4_frozen", False):
+            # FP4-resident experts: the same, by the W4 ladder; and never the packed layout, which would read 16-bit weights
+            swiglu = isinstance(self.experts, LlamaFFNNetwork)
+            why = self.experts.w4_refusal(x, self) if swiglu else self.experts.engine_refusal(_ffn.W4, x, self, 0)
+            if why is None and cf <= 0 and self.dropless_packed:
+                why = "the packed dropless forward has no FP4 GEMM"
+            if why is not None:
+                self._fp4_weights_ran = why
+                raise RuntimeError(_fp8_resident.REFUSED_FP4 + why)
 
         mega = max(megablocks_size, 1)
         alignment = (self.sharded_count * degree + mega - 1) // mega * mega

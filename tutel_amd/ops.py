@@ -656,6 +656,59 @@ def quantize_w8(w, w_kmajor, image=None, scale=None, channel_map=None, check_onl
     return image, scale
 
 
+def quantize_w4_supported(dtype, N, K, channel_map=None, act_dtype=None):
+    """shapes the HIP MXFP4 quantiser (tutel_amd_quantize_w4) takes -- the library's own answer.  dtype: the weights'; act_dtype: the
+    activations' (default: the weights' own).  channel_map: (image_channels, group, group_stride, group_offset), default (N, N, N, 0)"""
+    act_dtype = dtype if act_dtype is None else act_dtype
+    if dtype not in _DT or act_dtype not in _DT:
+        return False
+    C, g, gs, go = (N, N, N, 0) if channel_map is None else channel_map
+    return bool(_lib.lib().tutel_amd_quantize_w4_supported(_DT[dtype], _DT[act_dtype], int(N), int(K), int(C), int(g), int(gs), int(go)))
+
+
+def quantize_w4(w, w_kmajor, dtype=None, codes=None, scales=None, channel_map=None, check_only=False):
+    """The MXFP4 code image and scale image of one parameter, written by the HIP quantiser straight from the parameter as stored, in
+    one pass: bit for bit experts/w4.py::prepare (the contract of include/tutel_amd.h).
+
+    w: [E, N, K] (w_kmajor) or [E, K, N], bf16 / fp16 / fp32; the last dimension contiguous, rows and experts may be strided.  dtype:
+    the activations' (bf16 / fp16; default w's own), which selects the admitted scale bytes.  channel_map as ops.quantize_w8's; a
+    SwiGLU gate / up pair is two calls into one pair of images: (2 H, 16, 32, 0) for the gate, (2 H, 16, 32, 16) with codes= and
+    scales= for the up -- experts/w4.py::prepare_gate_up.
+    codes / scales: written in place when given (uint8, image_channels * K / 2 and image_channels * ceil(K / 128) * 4 bytes per
+    expert), else allocated as [E, C / 32, K / 64, 64, 16] and [E, C / 32, ceil(K / 128), 32, 4].  check_only: nothing is written but
+    the finiteness check runs.
+    -> (codes, scales); None where the library does not cover the call (nothing was enqueued).  A non-finite weight raises the torch
+    quantiser's ValueError, naming the same channel (this reads one word back: a synchronisation, the quantiser is a cold path)."""
+    _dev(w, codes, scales)
+    assert w.dim() == 3 and w.stride(2) == 1
+    dtype = w.dtype if dtype is None else dtype
+    E = w.shape[0]
+    N, K = (w.shape[1], w.shape[2]) if w_kmajor else (w.shape[2], w.shape[1])
+    C, g, gs, go = (N, N, N, 0) if channel_map is None else (int(v) for v in channel_map)
+    if not quantize_w4_supported(w.dtype, N, K, (C, g, gs, go), dtype):
+        return None
+    T = (K + 127) // 128
+    if not check_only:
+        if codes is None:
+            codes = torch.empty([E, C // 32, K // 64, 64, 16], dtype=torch.uint8, device=w.device)
+        if scales is None:
+            scales = torch.empty([E, C // 32, T, 32, 4], dtype=torch.uint8, device=w.device)
+        assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.numel() == E * C * K // 2
+        assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == E * C * T * 4
+    status = torch.full([1], INT32_MAX, dtype=torch.int32, device=w.device)
+    rc = _lib.lib().tutel_amd_quantize_w4(
+        _ptr(w), _DT[w.dtype], _DT[dtype], int(bool(w_kmajor)),
+        w.stride(0) if E > 1 else max(w.stride(0), w.shape[1] * w.stride(1)), w.stride(1), E, N, K,
+        None if check_only else _ptr(codes), C * K // 2, None if check_only else _ptr(scales), C * T * 4, C, g, gs, go,
+        _ptr(status), _stream())
+    if _unless_notsup(rc, "tutel_amd_quantize_w4", True) is None:
+        return None
+    bad = int(status.item())
+    if bad != INT32_MAX:
+        raise ValueError(f"quantize_mxfp4: channel (expert {bad // N}, output {bad % N}) holds a non-finite weight")
+    return codes, scales
+
+
 def expert_ffn(x, w1, b1, w2_kmajor, b2, act, R=None, smap=None, hid=None):
     """fc1 -> activation -> fc2 of every local expert in ONE persistent launch (tutel_amd_expert_ffn, csrc/expert_ffn.hip):
     x [E_loc, R, M] -- or the token array [T, M] with smap [E_loc * R] (fast_encode fused) -- w1 [E_loc, H, M], w2_kmajor
