@@ -381,6 +381,40 @@ int tutel_amd_expert_gemm_w4_glu(const void *A, int64_t a_stride_e, int64_t a_st
                                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                                  tutel_stream_t stream);
 
+/* The two W4A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w4.hip): the experts'
+ * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value
+ * and can be captured in a HIP graph.  Arguments: those of tutel_amd_expert_gemm_w8_packed / _glu_packed (below), with the scale image
+ * Ws / s_stride_e in place of `scale`.
+ *     expert e owns packed rows [offsets[e], offsets[e + 1]);  D[r, :] for each of them is what tutel_amd_expert_gemm_w4 /
+ *     tutel_amd_expert_gemm_w4_glu writes for the same input row and expert, BIT FOR BIT, wherever the row lies and whichever window
+ *     form computed it.  This holds by construction: one fp32 accumulator per output, K ascending, the same widen, the same epilogue.
+ * Rows, D, the tables: as for the W8A16 packed pair.  Every row in [0, offsets[E]) is written; rows at and past offsets[E] are neither
+ * read nor written.  Wq / w_stride_e / Ws / s_stride_e / bias / bias_stride_e (Wq_gu / Ws_gu): the code image, the scale image, the
+ * 16-channel gate / up interleave and the epilogue arithmetic are exactly those of the padded entry points.
+ * Window forms.  WIDE (TUTEL_AMD_W4_PACKED_TILE=wide): a work item is (table tile, 128 image channels) and covers ALL live rows of the table tile's
+ * window [tiles[2t+1], +256), clipped by offsets[e + 1]: each weight operand is fetched and widened ONCE and multiplied into up to eight
+ * 32-row groups (an expert above 128 rows does not stream its weights or run its converts twice).  Grid: tiles_bound * ceil(channels /
+ * 128) work items rounded up to a multiple of 8, the live (table tile, channel tile) pairs cut into eight contiguous chunks from
+ * *ntiles, one per XCD; a work item past the live pairs returns at once.  One workgroup per CU (376 registers per lane, 64 KB of LDS).
+ * HALVES (TUTEL_AMD_W4_PACKED_TILE=halves; the default, measured faster: tools/packed_w4_bench.py): the padded kernels' 128-row tile
+ * over the W8A16 packed kernels' order, two work items per pair, two workgroups per CU; an expert above 128 rows streams its weights
+ * once per half.  The variable is read at every call (wide | halves; anything else: the default).  Both forms write the same bits.
+ * Rows of a window past offsets[e + 1] are the next expert's: their loads clamp to the window's last live row, their stores are masked
+ * and wholly dead 32-row groups issue no matrix instruction.
+ * Covered: the padded W4A16 entry points' conditions without the bucket strides -- bf16 / fp16, K % 64 == 0, N % 32 == 0 (H % 16 == 0),
+ * lda % 8 == 0, ldd and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= one code image, s_stride_e % 4 == 0 and >= one scale image,
+ * act one of TUTEL_ACT_*, 16 K and the halves form's work item count below 2^31.  Anything else returns TUTEL_AMD_ENOTSUP with its
+ * reason and nothing enqueued; E == 0, rows_bound == 0 or tiles_bound == 0 is a successful no-op.  A, Wq and zero_row 16-byte aligned,
+ * D and bias 8-byte aligned, Ws 4-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w4_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq,
+                                    int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e,
+                                    void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
+                                    const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+int tutel_amd_expert_gemm_w4_glu_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq_gu,
+                                        int64_t w_stride_e, const void *Ws_gu, int64_t s_stride_e, void *D, int ldd, int E,
+                                        int rows_bound, int H, int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
+                                        const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+
 /* The two W8A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w8.hip): the experts'
  * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value
  * and can be captured in a HIP graph.
@@ -814,8 +848,8 @@ int tutel_amd_expert_gemm_packed(const void *A, int lda, const int32_t *a_rows, 
                                  void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
                                  const int32_t *tiles, const int32_t *ntiles, const int32_t *capacity, int tiles_bound,
                                  tutel_stream_t stream);
-/* (FP8 expert weights over the same tables: tutel_amd_expert_gemm_w8_packed / tutel_amd_expert_gemm_w8_glu_packed, declared with
- * the W8A16 contract above.) */
+/* (FP8 and MXFP4 expert weights over the same tables: tutel_amd_expert_gemm_w8_packed / _w8_glu_packed and
+ * tutel_amd_expert_gemm_w4_packed / _w4_glu_packed, declared with the W8A16 and W4A16 contracts above.) */
 /* tutel_amd_expert_wgrad_packed: the weight gradient D[e] = A[rows(e)]^T . B[rows(e)] -> [E, N_a, N_b] in dtype, rows(e) =
  * [offsets[e], offsets[e+1]), fp32 accumulation in a fixed order (deterministic, no atomics), one rounding.  A [*, N_a] row r at
  * A + r*lda, B [*, N_b] row r at B + r*ldb; gather = 1 (A) or 2 (B): that operand is the token array [T, *] read through

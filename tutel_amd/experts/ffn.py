@@ -24,7 +24,9 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     frees the 16-bit weights: the same launches on the same bits, inference only, FP8 state dicts (experts/fp8_resident.py);
   * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same experts read e2m1 codes with one
     power-of-two scale byte per 32 values along K (W4A16; the widened weights are exact, activations are not quantised) -- two launches
-    of tutel_amd_expert_gemm_w4; the images are derived copies in the KMajorCache (experts/w4.py).  module.fp4_freeze() makes the code
+    of tutel_amd_expert_gemm_w4; the images are derived copies in the KMajorCache (experts/w4.py).  A dropless layer with
+    `dropless_packed` and `dropless_packed_fp4` runs them over the packed layout instead (impls/packed_w8.py:
+    tutel_amd_expert_gemm_w4_packed, no host read, capturable), frozen or not.  module.fp4_freeze() makes the code
     and scale images the module's own buffers, written by the HIP quantiser (csrc/quantize_w4.hip), and frees the 16-bit weights:
     0.27 x the memory, the same launches on the same bits, inference only, MXFP4 state dicts (experts/fp8_resident.py);
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /

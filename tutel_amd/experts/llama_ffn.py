@@ -19,13 +19,15 @@ Forward:
     refuses then raises;
   * MXFP4 weights, opt-in (module.fp4_weights, default from TUTEL_AMD_FP4_WEIGHTS=1): the same two launches over e2m1 codes with one
     power-of-two scale byte per 32 values along K (tutel_amd_expert_gemm_w4_glu, then tutel_amd_expert_gemm_w4 on W_fc3; experts/w4.py).
-    w4_refusal names why a forward does not take it; the packed dropless forward keeps its 16-bit path.  module.fp4_freeze() makes
+    w4_refusal names why a forward does not take it; the packed dropless forward keeps its 16-bit path unless
+    `layer.dropless_packed_fp4` is on (below).  module.fp4_freeze() makes
     the images the module's own buffers, written by the HIP quantiser (csrc/quantize_w4.hip), and frees the 16-bit weights;
   * anything else -> ATen matmuls, op for op as the reference.
 A dropless layer with `dropless_packed` runs these experts inside tutel_amd_moe_forward_packed_glu instead (impls/ep_native.py):
 the gate and up products in ONE launch (tutel_amd_expert_gemm_gate_up's kernel), same bits as the two launches above.  With
 `layer.dropless_packed_fp8` as well, FP8 weights run on that layout too (impls/packed_w8.py: tutel_amd_expert_gemm_w8_glu_packed, then
-tutel_amd_expert_gemm_w8_packed on W_fc3), the bits of the padded FP8 forward.
+tutel_amd_expert_gemm_w8_packed on W_fc3), the bits of the padded FP8 forward; with `layer.dropless_packed_fp4`, MXFP4 weights
+(tutel_amd_expert_gemm_w4_glu_packed, then tutel_amd_expert_gemm_w4_packed on W_fc3), the bits of the padded FP4 forward.
 """
 import types
 

@@ -109,6 +109,8 @@ class MOELayer(torch.nn.Module):
         # opt-in: experts with fp8_weights on that packed layout (impls/packed_w8.py: the W8A16 GEMMs over the packed tables, six
         # launches, capturable).  Acts only with capacity_factor <= 0, dropless_packed and experts.fp8_weights; off: nothing changes
         self.dropless_packed_fp8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_FP8", "0")) != 0
+        # opt-in: the same forward for experts with fp4_weights (the W4A16 GEMMs over the packed tables); with both on FP8 runs
+        self.dropless_packed_fp4 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_FP4", "0")) != 0
         # gradient accumulation over micro-batches: the packed training step adds the expert gradients into p.main_grad (fp32) inside
         # the gradient kernels and returns no autograd gradient for them (impls/packed_train.py).  A forward that cannot do so raises
         self.dropless_packed_main_grad = int(os.environ.get("TUTEL_AMD_PACKED_MAIN_GRAD", "0")) != 0
@@ -271,8 +273,9 @@ class MOELayer(torch.nn.Module):
 
     def _route(self, stage, x, logits, gate, top_k, cf, degree, alignment, reserve_shape, inequivalent_tokens, megablocks_size,
                original_dtype, crit=None, allow_native=True, packed_fp8=False):
-        """packed_fp8 (before routing): the question of _packed_fp8_plan -- would this forward take the one-call path if its experts
-        ran on their 16-bit GEMMs?  The experts' own admission (engines, can_fuse) is then left to the FP8 ladder"""
+        """packed_fp8 (before routing): the question of _packed_plan, for FP8 and FP4 weights alike -- would this forward take the
+        one-call path if its experts ran on their 16-bit GEMMs?  The experts' own admission (engines, can_fuse) is then left to the
+        format's ladder"""
         W = self.world_size
         # SwiGLU experts have one native path: the packed dropless forward, asked for with dropless_packed (its refusals carry a
         # reason: ep_native.packed_cover, asked in _run_native_moe)
@@ -357,37 +360,50 @@ class MOELayer(torch.nn.Module):
         return w
 
     def _packed_fp8_plan(self, x, logits, plan_args):
-        """The admission of the packed FP8 forward (impls/packed_w8.py), asked before routing; logits may be a meta tensor (shape and
-        dtype only).  -> the packed plan of this call when dropless_packed_fp8 acts and nothing refuses, else None: the forward is
-        then what it is without the switch, and where the switch acts the reason is kept -- the packed layout's or the routing's in _dropless_packed_ran,
-        the FP8 ladder's alone in _fp8_weights_ran (the forward is then the 16-bit packed one)."""
+        return self._packed_plan(packed_w8.FP8, x, logits, plan_args)
+
+    def _packed_plan(self, fmt, x, logits, plan_args):
+        """The admission of the packed FP8 / FP4 forward (impls/packed_w8.py; fmt: its Format), asked before routing; logits may be a
+        meta tensor (shape and dtype only).  -> the packed plan of this call when the format's switch (dropless_packed_fp8 /
+        dropless_packed_fp4) acts and nothing refuses, else None: the forward is then what it is without the switch, and where the
+        switch acts the reason is kept -- the packed layout's or the routing's in _dropless_packed_ran, the format's ladder's alone
+        in _fp8_weights_ran / _fp4_weights_ran (the forward is then the 16-bit packed one)."""
         gate, top_k, cf, degree, alignment = plan_args[:5]
-        if not (self.dropless_packed_fp8 and cf <= 0 and self.dropless_packed and getattr(self.experts, "fp8_weights", False)
+        if not (getattr(self, fmt.switch) and cf <= 0 and self.dropless_packed and getattr(self.experts, fmt.weights, False)
                 and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))):
             return None
         T, E = logits.shape[0], logits.shape[-1]
         k = min(top_k, E)
-        frozen = getattr(self.experts, "fp8_frozen", False)   # no 16-bit packed forward to fall back to: a refusal raises
+        frozen = getattr(self.experts, fmt.frozen, False)   # no 16-bit packed forward to fall back to: a refusal raises
         plan, why = None, packed_w8.ROUTING_REASON
         if x.is_cuda and logits.dim() == 2 and self._plan("before_routing", x, logits, *plan_args, packed_fp8=True) == "native_moe":
             plan, why = ep_native.packed_cover(self, T, E, k, x.shape[1], x.dtype, ep_native.dropless_row_limit(T, E, k, cf), alignment)
         if plan is None:
             self._dropless_packed_ran = why or "the packed layout does not cover this shape"
             if frozen:
-                raise RuntimeError(_fp8_resident.REFUSED + "dropless_packed_fp8 is on and " + self._dropless_packed_ran)
+                raise RuntimeError(fmt.refused + fmt.switch + " is on and " + self._dropless_packed_ran)
             return None
-        why = packed_w8.fp8_refusal(self, x)
+        why = packed_w8.refusal(fmt, self, x)
         if why is not None:
-            self._fp8_weights_ran = why
+            setattr(self, fmt.engine.ran, why)
             if frozen:
-                raise RuntimeError(_fp8_resident.REFUSED + why)
+                raise RuntimeError(fmt.refused + why)
             return None
         return plan
 
-    def _run_packed_fp8(self, x, logits, plan, top_k, cf, alignment, megablocks_size):
-        y, l_aux = packed_w8.forward(self, x if x.is_contiguous() else x.contiguous(), logits.contiguous(), min(top_k, logits.shape[1]),
-                                     cf, alignment, plan)
-        self._dropless_packed_ran = self._fp8_weights_ran = True
+    def _packed_plans(self, x, logits, plan_args):
+        """-> (Format, plan) of the first format of packed_w8.FORMATS whose packed forward is admitted, or None"""
+        for fmt in packed_w8.FORMATS:
+            plan = self._packed_plan(fmt, x, logits, plan_args)
+            if plan is not None:
+                return fmt, plan
+        return None
+
+    def _run_packed_quantised(self, fmt, x, logits, plan, top_k, cf, alignment, megablocks_size):
+        y, l_aux = packed_w8.forward(fmt, self, x if x.is_contiguous() else x.contiguous(), logits.contiguous(),
+                                     min(top_k, logits.shape[1]), cf, alignment, plan)
+        self._dropless_packed_ran = True
+        setattr(self, fmt.engine.ran, True)
         self.megablocks_size = megablocks_size
         return y, l_aux
 
@@ -515,15 +531,15 @@ class MOELayer(torch.nn.Module):
             # FP8-resident experts: what the ladder knows before routing decides here, in front of every launch -- no path below
             # may reach for 16-bit weights that are gone.  (Walked with megablocks_size 0: the packed FP8 forward takes any; the
             # padded paths meet that rung with their own value, in the experts' forward.)
-            why = packed_w8.fp8_refusal(self, x)
+            why = packed_w8.refusal(packed_w8.FP8, self, x)
             if why is not None:
                 self._fp8_weights_ran = why
                 raise RuntimeError(_fp8_resident.REFUSED + why)
         if getattr(self.experts, "fp4_frozen", False):
-            # FP4-resident experts: the same, by the W4 ladder; and never the packed layout, which would read 16-bit weights
-            swiglu = isinstance(self.experts, LlamaFFNNetwork)
-            why = self.experts.w4_refusal(x, self) if swiglu else self.experts.engine_refusal(_ffn.W4, x, self, 0)
-            if why is None and cf <= 0 and self.dropless_packed:
+            # FP4-resident experts: the same, by the W4 ladder; and the packed layout only with dropless_packed_fp4 (the packed FP4
+            # forward, admitted below): the 16-bit packed forward would read weights that are gone
+            why = packed_w8.refusal(packed_w8.FP4, self, x)
+            if why is None and cf <= 0 and self.dropless_packed and not self.dropless_packed_fp4:
                 why = "the packed dropless forward has no FP4 GEMM"
             if why is not None:
                 self._fp4_weights_ran = why
@@ -545,11 +561,12 @@ class MOELayer(torch.nn.Module):
         # (a meta tensor stands in for them); anything else -- hooks on the gate, a gradient, fp32_gate, an uncovered shape --
         # projects below as before.  (_NATIVE_GATE_FP32: an fp32 gate over 16-bit tokens too; the logits are then fp32.)
         gate_w = self._native_gate_weight(gate, x)
-        fp8_plan = None   # the packed FP8 forward's plan, once admitted (dropless_packed_fp8; it projects the gate below, once)
+        # the packed FP8 / FP4 forward's (Format, plan), once admitted (dropless_packed_fp8 / _fp4; it projects the gate below, once)
+        quant_plan = None
         if gate_w is not None:
             spec = torch.empty([x.shape[0], gate_w.shape[0]], dtype=gate_w.dtype, device="meta")
-            fp8_plan = self._packed_fp8_plan(x, spec, plan_args)
-            if fp8_plan is None and self._plan("before_routing", x, spec, *plan_args) == "native_moe":
+            quant_plan = self._packed_plans(x, spec, plan_args)
+            if quant_plan is None and self._plan("before_routing", x, spec, *plan_args) == "native_moe":
                 res = self._run_native_moe(x, spec, top_k, cf, degree, alignment, megablocks_size, gate_w=gate_w)
                 if res is not None:
                     return finish(*res)
@@ -565,10 +582,10 @@ class MOELayer(torch.nn.Module):
                 logits = gate(x)
         else:
             logits = gate(x)
-        if fp8_plan is None and gate_w is None:
-            fp8_plan = self._packed_fp8_plan(x, logits, plan_args)
-        if fp8_plan is not None:
-            return finish(*self._run_packed_fp8(x, logits, fp8_plan, top_k, cf, alignment, megablocks_size))
+        if quant_plan is None and gate_w is None:
+            quant_plan = self._packed_plans(x, logits, plan_args)
+        if quant_plan is not None:
+            return finish(*self._run_packed_quantised(quant_plan[0], x, logits, quant_plan[1], top_k, cf, alignment, megablocks_size))
         if self._plan("before_routing", x, logits, *plan_args) == "native_moe":
             res = self._run_native_moe(x, logits, top_k, cf, degree, alignment, megablocks_size)
             if res is not None:

@@ -1,4 +1,4 @@
-"""FP8 expert weights on the packed dropless forward: `ffn` and SwiGLU experts, inference, single rank, no host synchronisation.
+"""FP8 and MXFP4 expert weights on the packed dropless forward: `ffn` and SwiGLU experts, inference, single rank, no host synchronisation.
 
 The padded dropless forward of experts with `fp8_weights` reads the capacity back to the host to shape [E, C, *] buckets
 (MOELayer's "routed" path), so it cannot be captured in a HIP graph; the one-call packed forwards (impls/ep_native.py) have no FP8
@@ -15,28 +15,57 @@ GEMM.  This forward composes the launches the library already has with the W8A16
 Six launches, every extent per expert read from the device tables.  Each packed row is bit for bit the row the padded FP8 forward
 computes (the W8 kernels' contract, include/tutel_amd.h), the routing and the decode are the padded path's own kernels, so the output,
 the routing and l_aux equal the padded dropless FP8 forward's bits.  Opt-in: layer.dropless_packed_fp8 (TUTEL_AMD_DROPLESS_PACKED_FP8=1)
-on top of layer.dropless_packed and experts.fp8_weights; MOELayer._packed_fp8_plan holds the admission.
+on top of layer.dropless_packed and experts.fp8_weights; MOELayer._packed_plan holds the admission.
+
+MXFP4 weights are the same forward under another Format (below): the W4A16 GEMMs over the packed tables (csrc/expert_gemm_w4.hip,
+tutel_amd_expert_gemm_w4_packed / _glu_packed), the W4 ladders, the W4 images, no scale multiply
+in the formulas above; the bits of the padded dropless FP4 forward.  Opt-in: layer.dropless_packed_fp4 (TUTEL_AMD_DROPLESS_PACKED_FP4=1)
+on top of layer.dropless_packed and experts.fp4_weights.  With both formats switched on FP8 runs (the W4 ladder's own rung).
 """
+from typing import NamedTuple
+
 import torch
 
 from . import ep_native, packed_train
 from .. import _lib, ops
 from ..experts import ffn as _ffn
+from ..experts import fp8_resident
 
 ROUTING_REASON = ("the forward does not run through the one-call native path (autocast, training, batch-prioritised routing, "
                   "a non-gshard loss, gate noise, a router that takes a gradient, unequal token counts ...)")
 
 
-def fp8_refusal(layer, x):
-    """why this forward's experts cannot read FP8 weights on the packed layout (None: they can): the engine's own ladder.  The
+class Format(NamedTuple):
+    """one weight format of this forward, by what differs between them"""
+    name: str          # "FP8" / "FP4", as the messages spell it
+    switch: str        # the layer's switch
+    weights: str       # the experts' engine switch
+    frozen: str        # the experts' attribute that is True once they are resident in this format
+    refused: str       # what a resident module's refusal raises, in front of the reason
+    engine: object     # the `ffn` experts' engine (experts/ffn.py: its ladder, and `ran`, the layer's report)
+    glu_refusal: str   # the SwiGLU experts' method that walks their ladder
+    params: str        # the experts' method that returns the two pairs of images
+    gemm: object       # (a, image, scale, bias, N, K, layout, act=, gather=, zero_row=) -> [rows_bound, N] or None
+    gemm_glu: object   # (a, image, scale, H, K, layout, act=, gather=, zero_row=) -> [rows_bound, H] or None
+
+
+FP8 = Format("FP8", "dropless_packed_fp8", "fp8_weights", "fp8_frozen", fp8_resident.REFUSED, _ffn.W8, "w8_refusal", "w8_params",
+             ops.expert_gemm_w8_packed, ops.expert_gemm_w8_glu_packed)
+FP4 = Format("FP4", "dropless_packed_fp4", "fp4_weights", "fp4_frozen", fp8_resident.REFUSED_FP4, _ffn.W4, "w4_refusal", "w4_params",
+             ops.expert_gemm_w4_packed, ops.expert_gemm_w4_glu_packed)
+FORMATS = (FP8, FP4)   # the order the layer asks them in: with both switched on FP8 runs
+
+
+def refusal(fmt, layer, x):
+    """why this forward's experts cannot read `fmt` weights on the packed layout (None: they can): the engine's own ladder.  The
     megablocks rung is walked with 0: on the packed layout megablocks_size only sets the alignment, as in the 16-bit packed forward"""
     ex = layer.experts
     if ep_native._swiglu(ex):
-        return ex.w8_refusal(x, layer)   # (these experts' ladder has no megablocks rung)
-    return ex.engine_refusal(_ffn.W8, x, layer, 0)
+        return getattr(ex, fmt.glu_refusal)(x, layer)   # (these experts' ladder has no megablocks rung)
+    return ex.engine_refusal(fmt.engine, x, layer, 0)
 
 
-def forward(layer, x, logits, k, cf, alignment, plan):
+def forward(fmt, layer, x, logits, k, cf, alignment, plan):
     """x [T, M] contiguous, logits [T, E] -> (y [T, M_out], l_aux); plan: ep_native.packed_cover's for this call.  Sets dispatch_count,
     dropless_capacity (device int32 [1]), dropless_offsets, protected_shape and last_routing as ep_native.forward_packed does."""
     ex = layer.experts
@@ -52,17 +81,17 @@ def forward(layer, x, logits, k, cf, alignment, plan):
         zero_row = ops.zero_row(M, x.dtype, x.device)
     act = ex.fused_activation()
     if ep_native._swiglu(ex):
-        (igu, sgu), (i3, s3) = ex.w8_params()
+        (igu, sgu), (i3, s3) = getattr(ex, fmt.params)()
         H = ex.W_fc1_full_shape[2]
-        hid = ops.expert_gemm_w8_glu_packed(x, igu, sgu, H, M, lay, act=act, gather=True, zero_row=zero_row)
-        yp = ops.expert_gemm_w8_packed(hid, i3, s3, None, ex.output_dim, H, lay) if hid is not None else None
+        hid = fmt.gemm_glu(x, igu, sgu, H, M, lay, act=act, gather=True, zero_row=zero_row)
+        yp = fmt.gemm(hid, i3, s3, None, ex.output_dim, H, lay) if hid is not None else None
     else:
-        (i1, s1), (i2, s2) = ex.w8_params()
+        (i1, s1), (i2, s2) = getattr(ex, fmt.params)()
         w1, b1, w2, b2 = _ffn._inference_params(ex)
-        hid = ops.expert_gemm_w8_packed(x, i1, s1, b1, w1.size(1), M, lay, act=act, gather=True, zero_row=zero_row)
-        yp = ops.expert_gemm_w8_packed(hid, i2, s2, b2, w2.size(2), w2.size(1), lay) if hid is not None else None
+        hid = fmt.gemm(x, i1, s1, b1, w1.size(1), M, lay, act=act, gather=True, zero_row=zero_row)
+        yp = fmt.gemm(hid, i2, s2, b2, w2.size(2), w2.size(1), lay) if hid is not None else None
     if yp is None:   # the ladder asked the library's own coverage queries: a refusal here is a bug, never a quiet forward elsewhere
-        raise _lib.TutelAmdError("the packed FP8 expert GEMMs refused a shape their own queries admit: " +
+        raise _lib.TutelAmdError(f"the packed {fmt.name} expert GEMMs refused a shape their own queries admit: " +
                                  _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
     y = ops.fast_decode_packed(yp, idx2d, loc2d, gates2d, lay)
     layer.dispatch_count = cnt
