@@ -20,8 +20,8 @@ DTYPES = [torch.bfloat16, torch.float16]
 # (E_loc, R, N, K): one K-tile (shorter than the weight ring), one live wave, one row; a ragged channel tile and K no multiple of 128
 # (the last scale dword is half pad); two row tiles, two channel tiles, five K-tiles (odd, no multiple of the ring depth); three row
 # tiles and three channel tiles with slivers; the tuned case, 128 rows, a long K
-SHAPES = [(3, 1, 32, 64), (2, 127, 96, 192), (2, 129, 160, 320), (1, 300, 288, 1024), (5, 128, 256, 2048)]
-GLU_SHAPES = [(3, 1, 16, 64), (2, 127, 48, 192), (2, 129, 80, 320), (1, 200, 144, 1024)]   # (E_loc, R, H, K)
+SHAPES = [(3, 1, 32, 64), (2, 127, 96, 192), (2, 129, 160, 320), (1, 300, 288, 1024), (5, 128, 256, 2048), (2, 70, 64, 128)]
+GLU_SHAPES = [(3, 1, 16, 64), (2, 127, 48, 192), (2, 129, 80, 320), (1, 200, 144, 1024), (2, 70, 32, 128)]   # (E_loc, R, H, K)
 _ids = dict(ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v).replace("torch.", ""))
 OUT_FILL = 1234.0
 

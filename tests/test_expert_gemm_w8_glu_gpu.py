@@ -21,7 +21,7 @@ F8 = torch.float8_e4m3fn
 DTYPES = [torch.bfloat16, torch.float16]
 # (E_loc, R, H, K): one row, one channel group, one K-tile; ragged rows, a ragged channel tile, an odd number of K-tiles; one row past
 # a row tile, two channel tiles; three row and three channel tiles with slivers, K longer than the weight ring; the tuned case
-SHAPES = [(3, 1, 16, 64), (2, 127, 48, 192), (2, 129, 80, 64), (1, 300, 144, 1024), (4, 128, 128, 512)]
+SHAPES = [(3, 1, 16, 64), (2, 127, 48, 192), (2, 129, 80, 64), (1, 300, 144, 1024), (4, 128, 128, 512), (2, 70, 32, 128)]
 _ids = dict(ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v).replace("torch.", ""))
 OUT_FILL = 1234.0
 ONE = 0x38   # the code of 1.0

@@ -19,7 +19,7 @@ F8 = torch.float8_e4m3fn
 DTYPES = [torch.bfloat16, torch.float16]
 # (E_loc, R, N, K): one row; ragged rows and a ragged channel tile, an odd number of K-tiles; one row past a row tile, two channel
 # tiles; three row tiles and three channel tiles with slivers, K longer than the weight ring; the tuned case, 128 rows, a long K
-SHAPES = [(3, 1, 32, 64), (2, 127, 96, 192), (2, 129, 160, 64), (1, 300, 288, 1024), (5, 128, 256, 2048)]
+SHAPES = [(3, 1, 32, 64), (2, 127, 96, 192), (2, 129, 160, 64), (1, 300, 288, 1024), (5, 128, 256, 2048), (2, 70, 64, 128)]
 _ids = dict(ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v).replace("torch.", ""))
 OUT_FILL = 1234.0
 

@@ -10,30 +10,20 @@
 // product runs on v_mfma_f32_32x32x16_{bf16,f16} with ONE fp32 accumulator per output (no split-K, no atomics); then one fp32 add of
 // the bias, the activation (gemm_dev.h::activate) and one rounding.  The contract is written into include/tutel_amd.h.
 //
-// The kernel is expert_gemm_w8.hip's weight-streaming kernel with another weight format -- a sibling with its own tile function, so
-// that the W8 kernels' code objects stay what they were.  What is the same: one 4-wave workgroup per (expert, 128 rows, 128 image
-// channels), wave w owning 32 channels and all 128 rows; weights global -> VGPR -> convert -> MFMA A operand, never through LDS, a
-// register ring of W4_DEPTH K-tiles in flight, every load unconditional through a buffer descriptor of exactly the run's size (the
-// refills past the last K-tile fetch nothing and return zeros that are never used); token rows through the swizzled 128-byte-row LDS
-// panel, two tiles ahead in registers, one barrier per K-tile; rows plain or gathered through the slot map (negative slot: the zero
-// row); ragged tiles clamp their loads and mask their stores; the XCD-local work-item order.  What differs:
+// The kernels are gemm_wstream.h's weight-streaming tile, the one expert_gemm_w8.hip runs (the design, the packed work-item order and
+// the host path are written there); this file is the MXFP4 format (W4Fmt), the kernels under their names and the C entry points.  It
+// stays a translation unit of its own because its object is built without packed fp32 arithmetic (Makefile).  The format:
 //   * ONE 16-byte load per lane per K-tile of 64 (1 KB contiguous per wave): dword q of it holds the lane's eight codes of operand q,
 //     k = 64 t + 16 q + 8 (lane >> 5) + j -- the image of include/tutel_amd.h (tutel_amd/experts/w4.py::pack);
 //   * one scale dword per lane per K-tile (128 B contiguous per 32 lanes): the scale bytes of the four 32-blocks of k-range
 //     [128 (t >> 1), + 128); K-tile t uses bytes 2 (t & 1) (operands 0, 1) and 2 (t & 1) + 1 (operands 2, 3);
 //   * operand q = four converts of dword q, byte_sel 0 .. 3;
-//   * the epilogue has no scale.
+//   * the epilogue has no scale;
+//   * the K loop is specialised per count of live 32-row groups, and the packed layout has a second, WIDE form (MG = 8).
 //
 // SwiGLU experts (tutel_amd_expert_gemm_w4_glu): D = round_T( float(round_T(act(gacc))) * uacc ); gate and up interleaved by 16 channels
 // in one image (experts/w8.py::interleave_gate_up over codes and scale bytes), the gating product register against register.
-#include "gemm_dev.h"  // Mma<T>, activate<ACT>
-
-#define W4_BM 128
-#define W4_BN 128
-#define W4_BK 64
-#define W4_THREADS 256
-#define W4_DEPTH 4       // K-tiles of weights in flight per wave (even: the token registers alternate with it)
-#define W4_STAGE (W4_BM * W4_BK * 2)
+#include "gemm_wstream.h"
 
 struct W4Args {
   const unsigned char *A; long long a_stride_e; int lda;     // elements
@@ -80,482 +70,141 @@ __device__ __forceinline__ uint32_t w4_sload(__amdgpu_buffer_rsrc_t rs, int voff
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0));
 }
 
-// One (expert, 32 MG rows, 128 image channels) work item; every kernel below is this function.  GLU: the image holds a SwiGLU expert's
-// gate and up channels interleaved by 16, p.N = 2 H image channels, and only the epilogue differs.
-//
-// The work item is a ROW WINDOW: expert e, rows [m0, min(m0 + 32 MG, rend)) and channel tile tn, rows numbered as the caller's layout
-// numbers them (within the bucket for the padded kernels; absolute packed rows, a_stride_e = d_stride_e = 0 and slot0 = 0, for the
-// packed ones: the rows from rend on are the NEXT expert's and are neither read nor written).
-//   MG = 4: the 128-row tile of the padded kernels (and of the packed kernels' halves form).
-//   MG = 8: the WIDE window of the packed kernels, a whole 256-row table tile.  Each operand of 8 k is widened ONCE and issued against
-//           up to eight 32-row groups; the K loop is specialised per live-group count 1 .. 8.  Counts 1 .. 4 are the 128-row loop itself
-//           (four token passes, four fragments: rows 128 .. 255 of the panel are neither written nor read); counts 5 .. 8 move eight
-//           token passes per K-tile into the 256-row panel (2 x 32 KB stages) and read exactly the live groups' fragments.
-// Whatever MG and whichever count: one fp32 accumulator per output, K ascending, the same widen, the same epilogue -- the same bits.
-template <typename T, int ACT, bool GLU, int MG = 4>
-__device__ __forceinline__ void w4_tile(const W4Args &p, unsigned char *smem, const int e, const int tn, const int m0, const int rend,
-                                        const long long slot0) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, kg = lane >> 5;
-  const int n0 = tn * W4_BN;
-  const int nk = p.K / W4_BK;
-  const int NT = p.N >> 5;
-  const int T128 = (p.K + 127) >> 7;              // scale dwords per channel
-  constexpr int STAGE = MG * 32 * W4_BK * 2;      // one stage of the token panel
-  const int nmi = min(MG, (rend - m0 + 31) >> 5);  // live 32-row groups of this tile
-  const bool wide = MG > 4 && nmi > 4;            // (block-uniform) the token passes 4 .. MG - 1 are live
+// TUTEL_AMD_W4_PACKED_TILE below
+#define W4_PACKED_DEFAULT_HALVES 1
 
-  // ---- token rows: thread `tid` moves chunk (tid & 7) of rows 32 i + (tid >> 3), i < MG, of every K-tile ------------------------------
-  const unsigned char *rowp[MG];
-  int ldst[MG];
-  {
-    int slot[MG];
-#pragma unroll
-    for (int i = 0; i < MG; ++i) slot[i] = 0;
-    if (p.slot_map != nullptr) {  // the slots first, so that their loads are in flight together
-#pragma unroll
-      for (int i = 0; i < MG; ++i) slot[i] = p.slot_map[slot0 + min(m0 + 32 * i + (tid >> 3), rend - 1)];
+struct W4Fmt {
+  using Args = W4Args;
+
+  // The group's codes are one run of 16 K bytes (K / 64 blocks of 1 KB) and its scales one run of 128 T128 bytes, one descriptor each.
+  // The K-tile's offset is part of the VECTOR offset: the hardware's range check covers the vector and the immediate offset, not the
+  // scalar one
+  template <typename T> struct Ring {
+    __amdgpu_buffer_rsrc_t rs_w, rs_s;
+    int wl, sl;
+    u32x4 w[WS_DEPTH];
+    uint32_t s[WS_DEPTH];
+    __device__ __forceinline__ void open(const W4Args &p, int e, int nt, int lane) {
+      const int nk = p.K / WS_BK;
+      const int T128 = (p.K + 127) >> 7;   // scale dwords per channel
+      rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(p.Wq + (long long)e * p.w_stride_e + (long long)nt * nk * 1024), 0,
+                                               nk * 1024, 0x00020000);
+      rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(p.Ws + (long long)e * p.s_stride_e + (long long)nt * T128 * 128), 0,
+                                               T128 * 128, 0x00020000);
+      wl = lane * 16;
+      sl = (lane & 31) * 4;
     }
-#pragma unroll
-    for (int i = 0; i < MG; ++i) {
-      const int r = 32 * i + (tid >> 3), c = tid & 7;
-      const int gr = min(m0 + r, rend - 1);
-      const unsigned char *row;
-      if (p.slot_map != nullptr) row = slot[i] < 0 ? p.zero_row : p.A + (long long)(slot[i] % p.T) * p.lda * 2;
-      else row = p.A + ((long long)e * p.a_stride_e + (long long)gr * p.lda) * 2;
-      rowp[i] = row + c * 16;
-      ldst[i] = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
+    __device__ __forceinline__ void load(int d, int t) {
+      w[d] = w4_wload(rs_w, wl + t * 1024);
+      s[d] = w4_sload(rs_s, sl + (t >> 1) * 128);
     }
-  }
-
-  // ---- weights: the wave's 32-channel group, clamped to the last one (a clamped wave computes and stores nothing new) ---------------------
-  const int nt = min((n0 >> 5) + wn, NT - 1);
-  const bool wave_live = (n0 >> 5) + wn < NT;
-  // The group's codes are one run of 16 K bytes (nk blocks of 1 KB) and its scales one run of 128 T128 bytes, each read through a
-  // buffer descriptor of exactly that size: every load of the K loop is UNCONDITIONAL, and the refills past the last K-tile are out
-  // of the descriptors' ranges -- they fetch nothing and return zeros that are never used.  The K-tile's offset is part of the VECTOR
-  // offset: the hardware's range check covers the vector and the immediate offset, not the scalar one.
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char *>(p.Wq + (long long)e * p.w_stride_e + (long long)nt * nk * 1024), 0, nk * 1024, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char *>(p.Ws + (long long)e * p.s_stride_e + (long long)nt * T128 * 128), 0, T128 * 128, 0x00020000);
-  const int wl = lane * 16, sl = l31 * 4;
-  u32x4 wreg[W4_DEPTH];
-  uint32_t sreg[W4_DEPTH];
+    // dword q holds k = 64 t + 16 q + 8 kg .. + 7; t & 1 == d & 1 (the ring depth is even): the tile's two 32-blocks are bytes
+    // 2 (d & 1) and 2 (d & 1) + 1 of its scale dword
+    __device__ __forceinline__ void widen(int d, u32x4 (&wa)[4]) const {
+      const float s0 = w4_scale(s[d], 2 * (d & 1)), s1 = w4_scale(s[d], 2 * (d & 1) + 1);
 #pragma unroll
-  for (int d = 0; d < W4_DEPTH; ++d) {
-    wreg[d] = w4_wload(rs_w, wl + d * 1024);
-    sreg[d] = w4_sload(rs_s, sl + (d >> 1) * 128);
-  }
-
-  f32x16 acc[MG];
-#pragma unroll
-  for (int mi = 0; mi < MG; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
-
-  // Token rows run TWO tiles ahead in registers (treg[j]: a tile of parity j), as in the W8 kernel: the memory counter retires loads
-  // in order, so a token tile asked for one step ago would wait for every weight refill issued before it.  Tile 0 goes to LDS here,
-  // tile 1 waits in treg[1]
-  u32x4 treg[2][MG];
-#pragma unroll
-  for (int i = 0; i < MG; ++i)
-    if (i < 4 || wide) treg[0][i] = *reinterpret_cast<const u32x4 *>(rowp[i]);
-#pragma unroll
-  for (int i = 0; i < MG; ++i)
-    if (i < 4 || wide) treg[1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + (long long)min(1, nk - 1) * (W4_BK * 2));
-#pragma unroll
-  for (int i = 0; i < MG; ++i)
-    if (i < 4 || wide) *reinterpret_cast<u32x4 *>(smem + ldst[i]) = treg[0][i];
-  __syncthreads();
-
-  const int sw = (l31 >> 1) & 7;
-  const int frag = l31 * 128;  // + mi * 32 rows
-
-  // The K loop, once per count of live 32-row groups: straight-line matrix instructions, no branch around any of them (the dead
-  // groups' accumulators stay zero and their stores are masked)
-  auto kloop = [&](auto nmi_c) __attribute__((always_inline)) {
-    constexpr int NMI = decltype(nmi_c)::value;
-    constexpr int NP = NMI <= 4 ? 4 : MG;   // token passes per K-tile; NF fragments per operand (the 128-row loop reads all four)
-    constexpr int NF = NMI <= 4 ? 4 : NMI;
-    for (int kt0 = 0; kt0 < nk; kt0 += W4_DEPTH) {
-#pragma unroll
-      for (int d = 0; d < W4_DEPTH; ++d) {
-        const int kt = kt0 + d;
-        if (kt >= nk) break;  // block-uniform
-        // token tile kt + 2 (behind the last tile: that tile again -- it is stored into the free stage and never read)
-        const long long tnext = (long long)min(kt + 2, nk - 1) * (W4_BK * 2);
-#pragma unroll
-        for (int i = 0; i < NP; ++i) treg[d & 1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + tnext);
-        // the K-tile's four operands of 8 k: dword q holds k = 64 kt + 16 q + 8 kg .. + 7; kt & 1 == d & 1 (kt0 is a multiple of the
-        // even ring depth): the tile's two 32-blocks are bytes 2 (d & 1) and 2 (d & 1) + 1 of its scale dword
-        const float s0 = w4_scale(sreg[d], 2 * (d & 1)), s1 = w4_scale(sreg[d], 2 * (d & 1) + 1);
-        u32x4 wa[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wa[q] = w4_widen<T>(wreg[d][q], q < 2 ? s0 : s1);
-        wreg[d] = w4_wload(rs_w, wl + (kt + W4_DEPTH) * 1024);
-        sreg[d] = w4_sload(rs_s, sl + ((kt + W4_DEPTH) >> 1) * 128);
-        // operand q multiplies token chunk 2 q + kg of every row; the fragments of operand q + 1 are asked for before the matrix
-        // instructions of operand q (two sets of NF in registers, not all of them)
-        const unsigned char *st = smem + (kt & 1) * STAGE + frag;
-        u32x4 tb[2][NF];
-#pragma unroll
-        for (int mi = 0; mi < NF; ++mi) tb[0][mi] = *reinterpret_cast<const u32x4 *>(st + mi * (32 * 128) + ((kg ^ sw) << 4));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q < 3) {
-#pragma unroll
-            for (int mi = 0; mi < NF; ++mi)
-              tb[(q + 1) & 1][mi] = *reinterpret_cast<const u32x4 *>(st + mi * (32 * 128) + (((2 * (q + 1) + kg) ^ sw) << 4));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int mi = 0; mi < NF; ++mi)
-            if (mi < NMI) acc[mi] = Mma<T>::run(wa[q], tb[q & 1][mi], acc[mi]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        {  // the other stage is free since the last barrier (behind the last tile nobody reads what is stored)
-          unsigned char *nx = smem + ((kt + 1) & 1) * STAGE;
-#pragma unroll
-          for (int i = 0; i < NP; ++i) *reinterpret_cast<u32x4 *>(nx + ldst[i]) = treg[(d + 1) & 1][i];
-        }
-        __syncthreads();
-      }
+      for (int q = 0; q < 4; ++q) wa[q] = w4_widen<T>(w[d][q], q < 2 ? s0 : s1);
     }
   };
-  switch (nmi) {
-    case 1: kloop(std::integral_constant<int, 1>{}); break;
-    case 2: kloop(std::integral_constant<int, 2>{}); break;
-    case 3: kloop(std::integral_constant<int, 3>{}); break;
-    default:
-      if constexpr (MG == 4) {
-        kloop(std::integral_constant<int, 4>{});
-      } else {
-        switch (nmi) {
-          case 4: kloop(std::integral_constant<int, 4>{}); break;
-          case 5: kloop(std::integral_constant<int, 5>{}); break;
-          case 6: kloop(std::integral_constant<int, 6>{}); break;
-          case 7: kloop(std::integral_constant<int, 7>{}); break;
-          default: kloop(std::integral_constant<int, 8>{}); break;
-        }
-      }
-      break;
-  }
 
-  // ---- epilogue: lane = row m0 + 32 mi + l31; register 4 rg + r of accumulator mi = channel 32 nt + 8 rg + 4 kg + r ---------------------
-  if (!wave_live) return;
-  if constexpr (GLU) {
-    // Registers rg = 0, 1 are gate channels 16 nt + 8 rg + 4 kg + r of the expert, registers rg + 2 the up channels of the same
-    // indices (the image's interleave).  g = act(gacc) rounded to T, D = round_T(float(g) * uacc); no bias
-#pragma unroll
-    for (int mi = 0; mi < MG; ++mi) {
-      const int m = m0 + mi * 32 + l31;
-      if (m >= rend) continue;
-      uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 16 + kg * 4;
-#pragma unroll
-      for (int rg = 0; rg < 2; ++rg) {
-        uint16_t o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float a = activate<ACT>(acc[mi][rg * 4 + r]);
-          asm("" : "+v"(a));  // the fp32 activation exists before it is rounded
-          const T g = Elem<T>::from_f32(a);
-          float v = __fmul_rn(Elem<T>::to_f32(g), acc[mi][(rg + 2) * 4 + r]);
-          asm("" : "+v"(v));  // and so does the product
-          const T tv = Elem<T>::from_f32(v);
-          __builtin_memcpy(&o[r], &tv, 2);
-        }
-        uint2 ov;
-        ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
-        ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
-        *reinterpret_cast<uint2 *>(drow + rg * 8) = ov;
-      }
-    }
-    return;
-  }
-  // the bias of the lane's channels 32 nt + 8 rg + 4 kg .. + 3, all fetched before the first is used
-  uint2 bi[4];
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg) {
-    const int n = nt * 32 + rg * 8 + kg * 4;
-    bi[rg] = p.bias != nullptr ? *reinterpret_cast<const uint2 *>(p.bias + (long long)e * p.bias_stride_e + n) : make_uint2(0u, 0u);
-  }
-#pragma unroll
-  for (int mi = 0; mi < MG; ++mi) {
-    const int m = m0 + mi * 32 + l31;
-    if (m >= rend) continue;
-    uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * 32 + kg * 4;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const uint16_t b4[4] = {(uint16_t)(bi[rg].x & 0xffff), (uint16_t)(bi[rg].x >> 16), (uint16_t)(bi[rg].y & 0xffff), (uint16_t)(bi[rg].y >> 16)};
-      uint16_t o[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[mi][rg * 4 + r];
-        if (p.bias != nullptr) {
-          T tb;
-          __builtin_memcpy(&tb, &b4[r], 2);
-          v = __fadd_rn(v, Elem<T>::to_f32(tb));
-        }
-        v = activate<ACT>(v);
-        asm("" : "+v"(v));  // the fp32 value exists before it is rounded (no fused multiply-and-round for fp16)
-        const T tv = Elem<T>::from_f32(v);
-        __builtin_memcpy(&o[r], &tv, 2);
-      }
-      uint2 ov;
-      ov.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
-      ov.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
-      *reinterpret_cast<uint2 *>(drow + rg * 8) = ov;
-    }
-  }
-}
+  // the block scales went into the widen: nothing per channel
+  struct Scale {
+    __device__ __forceinline__ void fetch(const W4Args &, int, int, int) {}
+    __device__ __forceinline__ float apply(float acc, int, int) const { return acc; }
+  };
 
-// (expert, row tile tm of the bucket [E_loc, R, *], channel tile): the channel tiles of one (expert, row tile) are consecutive work
-// items on ONE XCD, so that its L2 fetches the tile's token rows once
-template <typename T, int ACT, bool GLU>
-__device__ __forceinline__ void w4_padded(const W4Args &p, unsigned char *smem) {
-  const int b = xcd_work_item((int)gridDim.x);
-  const int tn = b % p.ntn, tm = (b / p.ntn) % p.ntm, e = b / (p.ntn * p.ntm);
-  w4_tile<T, ACT, GLU>(p, smem, e, tn, tm * W4_BM, p.R, (long long)e * p.R);
-}
+  struct Weights {
+    const void *Wq; int64_t w_stride_e; const void *Ws; int64_t s_stride_e;
+    bool strides_ok() const { return w_stride_e % 16 == 0 && s_stride_e % 4 == 0; }
+    bool image_ok(long long NI, int K) const { return w_stride_e >= NI * K / 2 && s_stride_e >= NI * (((long long)K + 127) / 128) * 4; }
+    static bool run_ok(int K) { return (long long)K * 16 <= 0x7fffffffLL; }
+    bool present() const { return Wq && Ws; }
+    bool aligned() const { return ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)Ws % 4) == 0; }
+    void fill(W4Args &a) const {
+      a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
+      a.Ws = (const unsigned char *)Ws; a.s_stride_e = s_stride_e;
+    }
+  };
+  static constexpr WsText TEXT = {
+      {"rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4",
+       "rows of A must stay 16-byte aligned (lda % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4"},
+      {"E_loc * R, the tile count and one channel group's run of 16 K bytes must stay below 2^31",
+       "the work item count tiles_bound * 2 * ceil(channels / 128) and one channel group's run of 16 K bytes must stay below 2^31"},
+      "%s: A and Wq must be 16-byte aligned, D and bias 8-byte aligned, Ws 4-byte aligned"};
+  // The form of the packed kernels, read at EVERY call: TUTEL_AMD_W4_PACKED_TILE=halves | wide; anything else is the default, which
+  // tools/packed_w4_bench.py's A/B decided: HALVES -- the wide form measured slower at 64 x 128 rows (108.7 against 79.5 us)
+  // AND at 64 x 160 rows (147.2 against 121.5 us); it stays selectable
+  static bool packed_halves() {
+    const char *s = getenv("TUTEL_AMD_W4_PACKED_TILE");
+    if (s != nullptr && strcmp(s, "halves") == 0) return true;
+    if (s != nullptr && strcmp(s, "wide") == 0) return false;
+    return W4_PACKED_DEFAULT_HALVES != 0;
+  }
+  template <typename T, int ACT, bool GLU>
+  static void launch(const W4Args &a, const WsTables *pk, bool halves, unsigned grid, hipStream_t st);
+};
 
 template <typename T, int ACT>
-__global__ __launch_bounds__(W4_THREADS, 2) void expert_gemm_w4_kernel(const W4Args p) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W4_STAGE];
-  w4_padded<T, ACT, false>(p, smem);
+__global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4_kernel(const W4Args p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * WS_STAGE];
+  ws_padded<W4Fmt, T, ACT, false, true>(p, smem);
 }
 
 // SwiGLU gate and up products in one launch: 128 image channels = 64 output channels x 128 rows per workgroup
 template <typename T, int ACT>
-__global__ __launch_bounds__(W4_THREADS, 2) void expert_gemm_w4_glu_kernel(const W4Args p) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W4_STAGE];
-  w4_padded<T, ACT, true>(p, smem);
+__global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4_glu_kernel(const W4Args p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * WS_STAGE];
+  ws_padded<W4Fmt, T, ACT, true, true>(p, smem);
 }
 
-// ---- the packed dropless layout (dropless.hip: tutel_amd_packed_layout) -------------------------------------------------------------------
-// Table tile t is rows [tiles[2t+1], +256) of expert tiles[2t], clipped by offsets[e + 1].  Two forms compute it:
-//
-// WIDE (the new tile, w4_tile<.., 8>): a work item is (table tile, channel tile) and owns ALL live rows of the window, so an expert
-// above 128 rows streams its weights and runs its converts once -- this kernel is bound by its converts, not by the bytes (DESIGN
-// 4.3), and a second half of 32 live rows would redo every one of them for a quarter of the matrix instructions.  The (table tile,
-// channel tile) pairs, channel tile fastest, are cut into eight contiguous chunks from the LIVE pair count (*ntiles x ntn, one scalar
-// load), one chunk per XCD: the channel tiles of a table tile run on ONE XCD, whose L2 fetches the token rows once.  The grid is the
-// host's bound, tiles_bound x ntn rounded up to a multiple of 8; a work item past its XCD's chunk returns before any barrier.
-// Registers: eight accumulators are 128 of a lane's registers, and with the ring, the token tiles two ahead and the fragments the
-// tile does not fit 256 without scratch, so the wide kernels take ONE workgroup per CU (512 registers per lane, zero scratch:
-// profiles/expert_gemm_w4_packed_kernel_resources.txt); the panel is 2 x 32 KB of LDS.
-//
-// HALVES (TUTEL_AMD_W4_PACKED_TILE=halves): the padded kernels' 128-row tile over expert_gemm_w8.hip's halves order -- a work item is
-// (table tile, channel tile, half), an XCD runs the first halves of its chunk, then the second halves; two workgroups per CU.  The
-// measurement's other arm and a second, independent computation of the same bits -- and, measured faster at both shapes, the default
-// (w4_packed_halves below): one workgroup of four waves per CU does not hide the wide tile's converts and LDS traffic.
+// ---- the packed dropless layout, both forms of gemm_wstream.h's ws_packed, always cut from the live pairs --------------------------
+// WIDE: this kernel is bound by its converts, not by the bytes, and a second half of 32 live rows would redo every one of
+// them for a quarter of the matrix instructions.  Registers: eight accumulators are 128 of a lane's registers, and with the ring, the
+// token tiles two ahead and the fragments the tile does not fit 256 without scratch, so the wide kernels take ONE workgroup per CU (512
+// registers per lane, zero scratch: profiles/expert_gemm_w4_packed_kernel_resources.txt); the panel is 2 x 32 KB of LDS.
+// HALVES (TUTEL_AMD_W4_PACKED_TILE=halves): the measurement's other arm and a second, independent computation of the same bits -- and,
+// measured faster at both shapes, the default: one workgroup of four waves per CU does not hide the wide tile's converts and LDS traffic.
 struct W4Tables { const int32_t *off, *tiles, *ntiles; int tiles_bound; };
 
-// -> this block's position in its XCD's chunk of the live (table tile, channel tile) pairs: `start` of the chunk, its `len`
-__device__ __forceinline__ int w4_packed_chunk(const W4Tables &t, int ntn, int &start, int &len, int &live) {
-  live = min(__builtin_amdgcn_readfirstlane(*t.ntiles), t.tiles_bound);
-  const int pairs = max(live, 0) * ntn;   // <= tiles_bound * ntn: the host sized the grid for it
-  const int xcd = blockIdx.x & 7;
-  const int q = pairs >> 3, r = pairs & 7;
-  len = q + (xcd < r ? 1 : 0);
-  start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return blockIdx.x >> 3;
+template <typename T, int ACT, bool GLU>
+__global__ __launch_bounds__(WS_THREADS, 1) void expert_gemm_w4_packed_kernel(const W4Args p, const W4Tables t) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * WS_STAGE];   // two stages of 256 rows
+  ws_packed<W4Fmt, T, ACT, GLU, 8, true>(p, t.off, t.tiles, t.ntiles, t.tiles_bound, 1, smem);
 }
 
 template <typename T, int ACT, bool GLU>
-__global__ __launch_bounds__(W4_THREADS, 1) void expert_gemm_w4_packed_kernel(const W4Args p, const W4Tables t) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * W4_STAGE];   // two stages of 256 rows
-  int start, len, live;
-  const int pos = w4_packed_chunk(t, p.ntn, start, len, live);
-  if (pos >= len) return;
-  const int it = start + pos;
-  const int tn = it % p.ntn, ti = it / p.ntn;   // ti < live: the chunks partition the live pairs
-  const int e = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti]);
-  const int m0 = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti + 1]);
-  const int rend = __builtin_amdgcn_readfirstlane(t.off[e + 1]);
-  if (m0 >= rend) return;
-  w4_tile<T, ACT, GLU, 8>(p, smem, e, tn, m0, rend, 0);
+__global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4_packed_halves_kernel(const W4Args p, const W4Tables t) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * WS_STAGE];
+  ws_packed<W4Fmt, T, ACT, GLU, 4, true>(p, t.off, t.tiles, t.ntiles, t.tiles_bound, 1, smem);
 }
 
 template <typename T, int ACT, bool GLU>
-__global__ __launch_bounds__(W4_THREADS, 2) void expert_gemm_w4_packed_halves_kernel(const W4Args p, const W4Tables t) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * W4_STAGE];
-  int start, len, live;
-  const int pos = w4_packed_chunk(t, p.ntn, start, len, live);
-  if (pos >= 2 * len) return;
-  const int half = pos >= len ? 1 : 0, it = start + pos - half * len;
-  const int tn = it % p.ntn, ti = it / p.ntn;
-  const int e = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti]);
-  const int m0 = __builtin_amdgcn_readfirstlane(t.tiles[2 * ti + 1]) + half * W4_BM;
-  const int rend = __builtin_amdgcn_readfirstlane(t.off[e + 1]);
-  if (m0 >= rend) return;
-  w4_tile<T, ACT, GLU>(p, smem, e, tn, m0, rend, 0);
+void W4Fmt::launch(const W4Args &a, const WsTables *pk, bool halves, unsigned grid, hipStream_t st) {
+  if (pk != nullptr) {
+    const W4Tables t = {pk->offsets, pk->tiles, pk->ntiles, pk->tiles_bound};
+    if (halves) hipLaunchKernelGGL((expert_gemm_w4_packed_halves_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a, t);
+    else hipLaunchKernelGGL((expert_gemm_w4_packed_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a, t);
+  } else if constexpr (GLU) {
+    hipLaunchKernelGGL((expert_gemm_w4_glu_kernel<T, ACT>), dim3(grid), dim3(WS_THREADS), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((expert_gemm_w4_kernel<T, ACT>), dim3(grid), dim3(WS_THREADS), 0, st, a);
+  }
 }
 
-static bool w4_dtype_ok(int dtype) { return dtype == TUTEL_BF16 || dtype == TUTEL_F16; }
-static bool w4_shape_ok(int N, int K) { return N >= 32 && N % 32 == 0 && K >= W4_BK && K % W4_BK == 0; }
+extern "C" int tutel_amd_expert_gemm_w4_supported(int dtype, int N, int K) { return ws_supported(dtype, N, K); }
+extern "C" int tutel_amd_expert_gemm_w4_glu_supported(int dtype, int H, int K) { return ws_glu_supported(dtype, H, K); }
 
-extern "C" int tutel_amd_expert_gemm_w4_supported(int dtype, int N, int K) { return w4_dtype_ok(dtype) && w4_shape_ok(N, K) ? 1 : 0; }
-// the gate / up image has 2 H channels: H a multiple of 16
-extern "C" int tutel_amd_expert_gemm_w4_glu_supported(int dtype, int H, int K) {
-  return w4_dtype_ok(dtype) && H >= 16 && H % 16 == 0 && w4_shape_ok(2 * H, K) ? 1 : 0;
-}
-
-// what differs between the two entry points on the host: the names in the messages, and the image's channels per output channel
-struct W4Entry { const char *name, *bad_n, *small_image; int per_out; };
-static const W4Entry W4_PLAIN = {"tutel_amd_expert_gemm_w4", "N must be a multiple of 32",
-                                 "w_stride_e / s_stride_e is smaller than one expert's image (N * K / 2 code bytes, N * ceil(K / 128) * 4 scale bytes)", 1};
-static const W4Entry W4_GLU = {"tutel_amd_expert_gemm_w4_glu", "H must be a multiple of 16",
-                               "w_stride_e / s_stride_e is smaller than one expert's image (H * K code bytes, 2 * H * ceil(K / 128) * 4 scale bytes)", 2};
-
-// (the activations last to first: the compiler instantiates the list's kernels from its end, and they keep their order in the code object)
-template <typename T, bool GLU> static int w4_launch(const W4Entry &en, const W4Args &a, int act, unsigned grid, hipStream_t st) {
-  return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
-      act,
-      [&](auto ac) {
-        if constexpr (GLU) hipLaunchKernelGGL((expert_gemm_w4_glu_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W4_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((expert_gemm_w4_kernel<T, decltype(ac)::value>), dim3(grid), dim3(W4_THREADS), 0, st, a);
-        TUTEL_CHECK_LAUNCH(en.name);
-        return 0;
-      },
-      [&] { return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu"); });
-}
-
-static const W4Entry W4_PLAIN_PK = {"tutel_amd_expert_gemm_w4_packed", "N must be a multiple of 32", W4_PLAIN.small_image, 1};
-static const W4Entry W4_GLU_PK = {"tutel_amd_expert_gemm_w4_glu_packed", "H must be a multiple of 16", W4_GLU.small_image, 2};
-
-template <typename T, bool GLU>
-static int w4_launch_packed(const W4Entry &en, const W4Args &a, const W4Tables &t, int act, bool halves, unsigned grid, hipStream_t st) {
-  return dispatch_act<TUTEL_ACT_SILU, TUTEL_ACT_GELU, TUTEL_ACT_RELU, TUTEL_ACT_NONE>(
-      act,
-      [&](auto ac) {
-        if (halves) hipLaunchKernelGGL((expert_gemm_w4_packed_halves_kernel<T, decltype(ac)::value, GLU>), dim3(grid), dim3(W4_THREADS), 0, st, a, t);
-        else hipLaunchKernelGGL((expert_gemm_w4_packed_kernel<T, decltype(ac)::value, GLU>), dim3(grid), dim3(W4_THREADS), 0, st, a, t);
-        TUTEL_CHECK_LAUNCH(en.name);
-        return 0;
-      },
-      [&] { return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu"); });
-}
-
-// The form of the packed kernels, read at EVERY call: TUTEL_AMD_W4_PACKED_TILE=halves | wide; anything else is the default, which
-// tools/packed_w4_bench.py's A/B decided: HALVES -- the wide form measured slower at 64 x 128 rows (108.7 against 79.5 us)
-// AND at 64 x 160 rows (147.2 against 121.5 us); it stays selectable
-#define W4_PACKED_DEFAULT_HALVES 1
-static bool w4_packed_halves() {
-  const char *s = getenv("TUTEL_AMD_W4_PACKED_TILE");
-  if (s != nullptr && strcmp(s, "halves") == 0) return true;
-  if (s != nullptr && strcmp(s, "wide") == 0) return false;
-  return W4_PACKED_DEFAULT_HALVES != 0;
-}
-
-// The packed entry points: the padded ones' checks (minus the bucket strides the packed layout does not have), every one in front of
-// the first HIP call
-template <bool GLU>
-static int w4_run_packed(const W4Entry &en, const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row, const void *Wq,
-                         int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e, void *D, int ldd,
-                         int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
-                         const int32_t *ntiles, int tiles_bound, tutel_stream_t stream) {
-  TUTEL_REQUIRE(E >= 0 && rows_bound >= 0 && tiles_bound >= 0 && N >= 1 && K >= 1, "%s: bad sizes E=%d rows_bound=%d tiles_bound=%d %s=%d K=%d",
-                en.name, E, rows_bound, tiles_bound, GLU ? "H" : "N", N, K);
-  if (!w4_dtype_ok(dtype)) return tutel_notsup(en.name, "the activations must be bf16 or fp16");
-  if (K % W4_BK != 0) return tutel_notsup(en.name, "K must be a multiple of 64");
-  if (N % (32 / en.per_out) != 0) return tutel_notsup(en.name, en.bad_n);
-  if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
-    return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu");
-  if (lda % 8 != 0 || ldd % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0 || s_stride_e % 4 != 0)
-    return tutel_notsup(en.name, "rows of A must stay 16-byte aligned (lda % 8), rows of D and bias 8-byte aligned (% 4), "
-                                 "w_stride_e % 16, s_stride_e % 4");
-  const long long NI = (long long)en.per_out * N;   // image channels
-  const long long T128 = ((long long)K + 127) / 128;
-  if (w_stride_e < NI * K / 2 || s_stride_e < NI * T128 * 4) return tutel_notsup(en.name, en.small_image);
-  const bool halves = w4_packed_halves();
-  const long long ntn = (NI + W4_BN - 1) / W4_BN;
-  // a whole number of blocks per XCD; the halves form has two work items per (table tile, channel tile) pair
-  const long long grid = ((long long)tiles_bound * ntn + 7) / 8 * (halves ? 16 : 8);
-  if (((long long)tiles_bound * ntn + 7) / 8 * 16 > 0x7fffffffLL || NI > 0x7fffffffLL || (long long)K * 16 > 0x7fffffffLL)
-    return tutel_notsup(en.name, "the work item count tiles_bound * 2 * ceil(channels / 128) and one channel group's run of 16 K bytes "
-                                 "must stay below 2^31");
-  if (E == 0 || rows_bound == 0 || tiles_bound == 0) return 0;
-  TUTEL_REQUIRE(A && Wq && Ws && D && offsets && tiles && ntiles, "%s: null pointer", en.name);
-  TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)Ws % 4) == 0 && ((uintptr_t)D % 8) == 0 &&
-                    ((uintptr_t)bias % 8) == 0,
-                "%s: A and Wq must be 16-byte aligned, D and bias 8-byte aligned, Ws 4-byte aligned", en.name);
-  if (a_rows != nullptr)
-    TUTEL_REQUIRE(T >= 1 && zero_row != nullptr && ((uintptr_t)zero_row % 16) == 0,
-                  "%s: a slot map needs T >= 1 and a 16-byte aligned zero row", en.name);
-
-  W4Args a;
-  a.A = (const unsigned char *)A; a.a_stride_e = 0; a.lda = lda;
-  a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
-  a.Ws = (const unsigned char *)Ws; a.s_stride_e = s_stride_e;
-  a.bias = (const uint16_t *)bias; a.bias_stride_e = bias_stride_e;
-  a.D = (uint16_t *)D; a.d_stride_e = 0; a.ldd = ldd;
-  a.R = rows_bound; a.N = (int)NI; a.K = K; a.ntm = 0; a.ntn = (int)ntn;
-  a.slot_map = a_rows; a.T = T; a.zero_row = (const unsigned char *)zero_row;
-  const W4Tables t = {offsets, tiles, ntiles, tiles_bound};
-  hipStream_t st = (hipStream_t)stream;
-  StageScope stage(GLU || act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
-  return dtype == TUTEL_BF16 ? w4_launch_packed<bf16_t, GLU>(en, a, t, act, halves, (unsigned)grid, st)
-                             : w4_launch_packed<f16_t, GLU>(en, a, t, act, halves, (unsigned)grid, st);
-}
-
-// Both entry points: N output channels per row of D, en.per_out * N image channels.  Every check stands in front of the first HIP call
-template <bool GLU>
-static int w4_run(const W4Entry &en, const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
-                  int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e, void *D,
-                  int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K, int dtype, int act,
-                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row, tutel_stream_t stream) {
-  TUTEL_REQUIRE(E_loc >= 0 && R >= 0 && N >= 1 && K >= 1, "%s: bad sizes E_loc=%d R=%d %s=%d K=%d", en.name, E_loc, R, GLU ? "H" : "N", N, K);
-  if (!w4_dtype_ok(dtype)) return tutel_notsup(en.name, "the activations must be bf16 or fp16");
-  if (K % W4_BK != 0) return tutel_notsup(en.name, "K must be a multiple of 64");
-  if (N % (32 / en.per_out) != 0) return tutel_notsup(en.name, en.bad_n);
-  if (act != TUTEL_ACT_NONE && act != TUTEL_ACT_RELU && act != TUTEL_ACT_GELU && act != TUTEL_ACT_SILU)
-    return tutel_notsup(en.name, "the activation must be none, relu, gelu or silu");
-  if (row_counts != nullptr) return tutel_notsup(en.name, "row_counts (megablocks) are not covered");
-  if ((slot_map == nullptr && (a_rows_per_w < R || a_stride_w != 0)) || d_rows_per_w < R || d_stride_w != 0)
-    return tutel_notsup(en.name, "the [W, E_loc, C, *] exchange layouts are not covered (rows_per_w >= R and stride_w == 0)");
-  if (lda % 8 != 0 || ldd % 4 != 0 || a_stride_e % 8 != 0 || d_stride_e % 4 != 0 || bias_stride_e % 4 != 0 || w_stride_e % 16 != 0 ||
-      s_stride_e % 4 != 0)
-    return tutel_notsup(en.name, "rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), "
-                                 "w_stride_e % 16, s_stride_e % 4");
-  const long long NI = (long long)en.per_out * N;   // image channels
-  const long long T128 = ((long long)K + 127) / 128;
-  if (w_stride_e < NI * K / 2 || s_stride_e < NI * T128 * 4) return tutel_notsup(en.name, en.small_image);
-  const long long ntm = (R + W4_BM - 1) / W4_BM, ntn = (NI + W4_BN - 1) / W4_BN;
-  if ((long long)E_loc * R > 0x7fffffffLL || (long long)E_loc * ntm * ntn > 0x7fffffffLL || NI > 0x7fffffffLL ||
-      (long long)K * 16 > 0x7fffffffLL)
-    return tutel_notsup(en.name, "E_loc * R, the tile count and one channel group's run of 16 K bytes must stay below 2^31");
-  if (E_loc == 0 || R == 0) return 0;
-  TUTEL_REQUIRE(A && Wq && Ws && D, "%s: null pointer", en.name);
-  TUTEL_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)Ws % 4) == 0 && ((uintptr_t)D % 8) == 0 &&
-                    ((uintptr_t)bias % 8) == 0,
-                "%s: A and Wq must be 16-byte aligned, D and bias 8-byte aligned, Ws 4-byte aligned", en.name);
-  if (slot_map != nullptr)
-    TUTEL_REQUIRE(T >= 1 && zero_row != nullptr && ((uintptr_t)zero_row % 16) == 0,
-                  "%s: a slot map needs T >= 1 and a 16-byte aligned zero row", en.name);
-
-  W4Args a;
-  a.A = (const unsigned char *)A; a.a_stride_e = a_stride_e; a.lda = lda;
-  a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
-  a.Ws = (const unsigned char *)Ws; a.s_stride_e = s_stride_e;
-  a.bias = (const uint16_t *)bias; a.bias_stride_e = bias_stride_e;
-  a.D = (uint16_t *)D; a.d_stride_e = d_stride_e; a.ldd = ldd;
-  a.R = R; a.N = (int)NI; a.K = K; a.ntm = (int)ntm; a.ntn = (int)ntn;
-  a.slot_map = slot_map; a.T = T; a.zero_row = (const unsigned char *)zero_row;
-  hipStream_t st = (hipStream_t)stream;
-  StageScope stage(GLU || act != TUTEL_ACT_NONE ? TUTEL_STAGE_FC1 : TUTEL_STAGE_FC2, st);
-  const unsigned grid = (unsigned)((long long)E_loc * ntm * ntn);
-  return dtype == TUTEL_BF16 ? w4_launch<bf16_t, GLU>(en, a, act, grid, st) : w4_launch<f16_t, GLU>(en, a, act, grid, st);
-}
+#define W4_SMALL "w_stride_e / s_stride_e is smaller than one expert's image (N * K / 2 code bytes, N * ceil(K / 128) * 4 scale bytes)"
+#define W4_SMALL_GU "w_stride_e / s_stride_e is smaller than one expert's image (H * K code bytes, 2 * H * ceil(K / 128) * 4 scale bytes)"
 
 extern "C" int tutel_amd_expert_gemm_w4(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
                                         int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e,
                                         void *D, int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N,
                                         int K, int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T,
                                         const void *zero_row, tutel_stream_t stream) {
-  return w4_run<false>(W4_PLAIN, A, a_stride_e, a_stride_w, a_rows_per_w, lda, Wq, w_stride_e, Ws, s_stride_e, bias, bias_stride_e, D,
-                       d_stride_e, d_stride_w, d_rows_per_w, ldd, E_loc, R, N, K, dtype, act, row_counts, slot_map, T, zero_row, stream);
+  const WsBucket bk = {a_stride_e, a_stride_w, a_rows_per_w, d_stride_e, d_stride_w, d_rows_per_w, row_counts};
+  return ws_run<W4Fmt, false>({"tutel_amd_expert_gemm_w4", W4_SMALL}, {Wq, w_stride_e, Ws, s_stride_e}, &bk, nullptr, A, lda, slot_map, T,
+                              zero_row, bias, bias_stride_e, D, ldd, E_loc, R, N, K, dtype, act, stream);
 }
 
 // SwiGLU gate and up products of MXFP4 weights in one launch (the contract: include/tutel_amd.h).  No bias: these experts have none
@@ -564,8 +213,9 @@ extern "C" int tutel_amd_expert_gemm_w4_glu(const void *A, int64_t a_stride_e, i
                                             int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int H, int K,
                                             int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T,
                                             const void *zero_row, tutel_stream_t stream) {
-  return w4_run<true>(W4_GLU, A, a_stride_e, a_stride_w, a_rows_per_w, lda, Wq_gu, w_stride_e, Ws_gu, s_stride_e, nullptr, 0, D, d_stride_e,
-                      d_stride_w, d_rows_per_w, ldd, E_loc, R, H, K, dtype, act, row_counts, slot_map, T, zero_row, stream);
+  const WsBucket bk = {a_stride_e, a_stride_w, a_rows_per_w, d_stride_e, d_stride_w, d_rows_per_w, row_counts};
+  return ws_run<W4Fmt, true>({"tutel_amd_expert_gemm_w4_glu", W4_SMALL_GU}, {Wq_gu, w_stride_e, Ws_gu, s_stride_e}, &bk, nullptr, A, lda,
+                             slot_map, T, zero_row, nullptr, 0, D, ldd, E_loc, R, H, K, dtype, act, stream);
 }
 
 // The two GEMMs above over the packed dropless layout (the contract: include/tutel_amd.h): the row ranges come from the device tables
@@ -574,8 +224,9 @@ extern "C" int tutel_amd_expert_gemm_w4_packed(const void *A, int lda, const int
                                                int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype,
                                                int act, const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles,
                                                int tiles_bound, tutel_stream_t stream) {
-  return w4_run_packed<false>(W4_PLAIN_PK, A, lda, a_rows, T, zero_row, Wq, w_stride_e, Ws, s_stride_e, bias, bias_stride_e, D, ldd, E,
-                              rows_bound, N, K, dtype, act, offsets, tiles, ntiles, tiles_bound, stream);
+  const WsTables pk = {offsets, tiles, ntiles, tiles_bound};
+  return ws_run<W4Fmt, false>({"tutel_amd_expert_gemm_w4_packed", W4_SMALL}, {Wq, w_stride_e, Ws, s_stride_e}, nullptr, &pk, A, lda, a_rows,
+                              T, zero_row, bias, bias_stride_e, D, ldd, E, rows_bound, N, K, dtype, act, stream);
 }
 
 extern "C" int tutel_amd_expert_gemm_w4_glu_packed(const void *A, int lda, const int32_t *a_rows, int T, const void *zero_row,
@@ -583,6 +234,7 @@ extern "C" int tutel_amd_expert_gemm_w4_glu_packed(const void *A, int lda, const
                                                    int ldd, int E, int rows_bound, int H, int K, int dtype, int act,
                                                    const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles, int tiles_bound,
                                                    tutel_stream_t stream) {
-  return w4_run_packed<true>(W4_GLU_PK, A, lda, a_rows, T, zero_row, Wq_gu, w_stride_e, Ws_gu, s_stride_e, nullptr, 0, D, ldd, E,
-                             rows_bound, H, K, dtype, act, offsets, tiles, ntiles, tiles_bound, stream);
+  const WsTables pk = {offsets, tiles, ntiles, tiles_bound};
+  return ws_run<W4Fmt, true>({"tutel_amd_expert_gemm_w4_glu_packed", W4_SMALL_GU}, {Wq_gu, w_stride_e, Ws_gu, s_stride_e}, nullptr, &pk, A,
+                             lda, a_rows, T, zero_row, nullptr, 0, D, ldd, E, rows_bound, H, K, dtype, act, stream);
 }

@@ -470,12 +470,43 @@ def expert_gemm_f32(a, w, bias, w_kmajor, act="none", slot_map=None, R=None, a_l
     return _unless_notsup(rc, "tutel_amd_expert_gemm_f32", out)
 
 
+def _ws_supported(entry, dtype, N, K):
+    """the four gemm_w*_supported functions below: the library's `entry`_supported(dtype, N or H, K) as a bool"""
+    if dtype not in _DT:
+        return False
+    return bool(getattr(_lib.lib(), entry + "_supported")(_DT[dtype], int(N), int(K)))
+
+
+def _ws_padded(entry, a, E_loc, weights, bias, N, K, act, slot_map, R, out, row_counts, glu=False):
+    """The padded W8A16 / W4A16 wrappers behind their own weight checks: `weights` is the format's weight operands as the C entry point
+    takes them (already checked), everything else the wrappers' arguments.  glu: the gate / up entry points, which take no bias."""
+    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
+    if out is None:
+        out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
+    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
+    bias_args = () if glu else (_ptr(bias), (bias.stride(0) if bias is not None else 0))
+    rc = getattr(_lib.lib(), entry)(
+        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        *weights, *bias_args,
+        _ptr(out), R * N, 0, max(R, 1), N,
+        E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    return _unless_notsup(rc, entry, out)
+
+
+def _w8_image(image, scale, channels):
+    """the checks the W8A16 wrappers share -> (E_loc, the weight operands of the C entry points: image, an expert's image bytes, scale)"""
+    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
+    E_loc = image.shape[0]
+    assert scale.shape == (E_loc, channels) and image.numel() % max(E_loc, 1) == 0
+    return E_loc, (_ptr(image), image.numel() // max(E_loc, 1), _ptr(scale))
+
+
 def gemm_w8_supported(dtype, N, K):
     """shapes the W8A16 grouped GEMM (tutel_amd_expert_gemm_w8) takes: bf16 / fp16 activations, K % 64 == 0, N % 32 == 0 -- the
     library's own answer"""
-    if dtype not in _DT:
-        return False
-    return bool(_lib.lib().tutel_amd_expert_gemm_w8_supported(_DT[dtype], int(N), int(K)))
+    return _ws_supported("tutel_amd_expert_gemm_w8", dtype, N, K)
 
 
 def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=None, out=None, row_counts=None):
@@ -486,30 +517,14 @@ def expert_gemm_w8(a, image, scale, bias, N, K, act="none", slot_map=None, R=Non
     slots read the zero row).  image: experts/w8.py::pack's uint8 image of the [E_loc, N, K] codes; scale [E_loc, N] fp32; bias [E_loc, N]
     in a.dtype or None, its rows may be strided.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
     _dev(a, image, scale, bias, out, slot_map, row_counts)
-    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
-    E_loc = image.shape[0]
-    assert scale.shape == (E_loc, N) and image.numel() % max(E_loc, 1) == 0
-    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
-    if out is None:
-        out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
-    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
-    if bias is not None:
-        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
-    rc = _lib.lib().tutel_amd_expert_gemm_w8(
-        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
-        _ptr(image), image.numel() // max(E_loc, 1), _ptr(scale),
-        _ptr(bias), (bias.stride(0) if bias is not None else 0),
-        _ptr(out), R * N, 0, max(R, 1), N,
-        E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8", out)
+    E_loc, weights = _w8_image(image, scale, N)
+    return _ws_padded("tutel_amd_expert_gemm_w8", a, E_loc, weights, bias, N, K, act, slot_map, R, out, row_counts)
 
 
 def gemm_w8_glu_supported(dtype, H, K):
     """shapes the W8A16 gate / up GEMM (tutel_amd_expert_gemm_w8_glu) takes: bf16 / fp16 activations, K % 64 == 0, H % 16 == 0 -- the
     library's own answer"""
-    if dtype not in _DT:
-        return False
-    return bool(_lib.lib().tutel_amd_expert_gemm_w8_glu_supported(_DT[dtype], int(H), int(K)))
+    return _ws_supported("tutel_amd_expert_gemm_w8_glu", dtype, H, K)
 
 
 def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None, out=None, row_counts=None):
@@ -521,35 +536,23 @@ def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None,
     scale: experts/w8.py::prepare_gate_up's uint8 image of the interleaved [E_loc, 2 H, K] codes and its [E_loc, 2 H] fp32 scales.
     -> [E_loc, R, H].  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
     _dev(a, image, scale, out, slot_map, row_counts)
-    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
-    E_loc = image.shape[0]
-    assert scale.shape == (E_loc, 2 * H) and image.numel() % max(E_loc, 1) == 0
-    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
-    if out is None:
-        out = torch.empty([E_loc, R, H], dtype=a.dtype, device=a.device)
-    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, H)
-    rc = _lib.lib().tutel_amd_expert_gemm_w8_glu(
-        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
-        _ptr(image), image.numel() // max(E_loc, 1), _ptr(scale),
-        _ptr(out), R * H, 0, max(R, 1), H,
-        E_loc, R, H, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu", out)
+    E_loc, weights = _w8_image(image, scale, 2 * H)
+    return _ws_padded("tutel_amd_expert_gemm_w8_glu", a, E_loc, weights, None, H, K, act, slot_map, R, out, row_counts, glu=True)
 
 
 def gemm_w4_supported(dtype, N, K):
     """shapes the W4A16 grouped GEMM (tutel_amd_expert_gemm_w4) takes: bf16 / fp16 activations, K % 64 == 0, N % 32 == 0 -- the
     library's own answer"""
-    if dtype not in _DT:
-        return False
-    return bool(_lib.lib().tutel_amd_expert_gemm_w4_supported(_DT[dtype], int(N), int(K)))
+    return _ws_supported("tutel_amd_expert_gemm_w4", dtype, N, K)
 
 
 def _w4_image(codes, scales):
-    """the checks the two W4A16 wrappers share -> (E_loc, an expert's code bytes, an expert's scale bytes)"""
+    """the checks the W4A16 wrappers share -> (E_loc, the weight operands of the C entry points: codes, an expert's code bytes, scales,
+    an expert's scale bytes)"""
     assert codes.dtype == torch.uint8 and codes.is_contiguous() and scales.dtype == torch.uint8 and scales.is_contiguous()
     E_loc = codes.shape[0]
     assert scales.shape[0] == E_loc and codes.numel() % max(E_loc, 1) == 0 and scales.numel() % max(E_loc, 1) == 0
-    return E_loc, codes.numel() // max(E_loc, 1), scales.numel() // max(E_loc, 1)
+    return E_loc, (_ptr(codes), codes.numel() // max(E_loc, 1), _ptr(scales), scales.numel() // max(E_loc, 1))
 
 
 def expert_gemm_w4(a, codes, scales, bias, N, K, act="none", slot_map=None, R=None, out=None, row_counts=None):
@@ -560,28 +563,14 @@ def expert_gemm_w4(a, codes, scales, bias, N, K, act="none", slot_map=None, R=No
     slots read the zero row).  codes, scales: experts/w4.py::pack's uint8 images of the [E_loc, N, K] weights; bias [E_loc, N] in
     a.dtype or None, its rows may be strided.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
     _dev(a, codes, scales, bias, out, slot_map, row_counts)
-    E_loc, wb, sb = _w4_image(codes, scales)
-    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
-    if out is None:
-        out = torch.empty([E_loc, R, N], dtype=a.dtype, device=a.device)
-    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
-    if bias is not None:
-        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
-    rc = _lib.lib().tutel_amd_expert_gemm_w4(
-        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
-        _ptr(codes), wb, _ptr(scales), sb,
-        _ptr(bias), (bias.stride(0) if bias is not None else 0),
-        _ptr(out), R * N, 0, max(R, 1), N,
-        E_loc, R, N, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4", out)
+    E_loc, weights = _w4_image(codes, scales)
+    return _ws_padded("tutel_amd_expert_gemm_w4", a, E_loc, weights, bias, N, K, act, slot_map, R, out, row_counts)
 
 
 def gemm_w4_glu_supported(dtype, H, K):
     """shapes the W4A16 gate / up GEMM (tutel_amd_expert_gemm_w4_glu) takes: bf16 / fp16 activations, K % 64 == 0, H % 16 == 0 -- the
     library's own answer"""
-    if dtype not in _DT:
-        return False
-    return bool(_lib.lib().tutel_amd_expert_gemm_w4_glu_supported(_DT[dtype], int(H), int(K)))
+    return _ws_supported("tutel_amd_expert_gemm_w4_glu", dtype, H, K)
 
 
 def expert_gemm_w4_glu(a, codes, scales, H, K, act="silu", slot_map=None, R=None, out=None, row_counts=None):
@@ -592,17 +581,8 @@ def expert_gemm_w4_glu(a, codes, scales, H, K, act="silu", slot_map=None, R=None
     scales: experts/w4.py::prepare_gate_up's uint8 images of the interleaved [E_loc, 2 H, K] weights.  -> [E_loc, R, H].  Returns None
     when the library answers ENOTSUP (nothing was enqueued)."""
     _dev(a, codes, scales, out, slot_map, row_counts)
-    E_loc, wb, sb = _w4_image(codes, scales)
-    a, R, a_layout, T, z = _a_rows(a, E_loc, K, slot_map, R, None)
-    if out is None:
-        out = torch.empty([E_loc, R, H], dtype=a.dtype, device=a.device)
-    assert out.dtype == a.dtype and out.is_contiguous() and out.shape == (E_loc, R, H)
-    rc = _lib.lib().tutel_amd_expert_gemm_w4_glu(
-        _ptr(a), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
-        _ptr(codes), wb, _ptr(scales), sb,
-        _ptr(out), R * H, 0, max(R, 1), H,
-        E_loc, R, H, K, _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4_glu", out)
+    E_loc, weights = _w4_image(codes, scales)
+    return _ws_padded("tutel_amd_expert_gemm_w4_glu", a, E_loc, weights, None, H, K, act, slot_map, R, out, row_counts, glu=True)
 
 
 INT32_MAX = 2 ** 31 - 1
@@ -798,58 +778,9 @@ def expert_gemm_packed(a, w, bias, w_kmajor, layout, act="none", gather=None, ze
     return out
 
 
-def _w8_packed_operands(a, image, scale, channels, N, K, layout, gather, zero_row, out):
-    """the operand checks the two packed W8A16 wrappers share -> (a at a 16-byte aligned address, out [rows_bound, N], a_rows, T, zero row)"""
-    _dev(a, image, scale, out, zero_row)
-    assert image.dtype == torch.uint8 and image.is_contiguous() and scale.dtype == torch.float32 and scale.is_contiguous()
-    E = image.shape[0]
-    assert E == layout.E and scale.shape == (E, channels) and image.numel() % max(E, 1) == 0
-    assert a.dim() == 2 and a.is_contiguous() and a.shape[1] == K
-    a = _a16(a)
-    if gather:
-        assert zero_row is not None and zero_row.dtype == a.dtype and zero_row.numel() >= K
-    else:
-        assert a.shape[0] >= layout.rows_bound
-    if out is None:
-        out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
-    assert out.shape == (layout.rows_bound, N) and out.is_contiguous() and out.dtype == a.dtype
-    return a, out, (_ptr(layout.slot_map) if gather else None), (a.shape[0] if gather else 0), (_ptr(zero_row) if gather else None)
-
-
-def expert_gemm_w8_packed(a, image, scale, bias, N, K, layout, act="none", gather=None, zero_row=None, out=None):
-    """expert_gemm_w8 over the packed dropless layout: D[r] = act(acc * scale[e] + bias[e]) for the packed rows r of expert e
-    -> [rows_bound, N], bit for bit what expert_gemm_w8 writes for the same row and expert (the contract of include/tutel_amd.h).
-    a [rows_bound, K] bf16 / fp16, or with gather=True the token array [T, K] read through layout.slot_map (zero_row, >= K zeros,
-    for pad rows); image / scale / bias as expert_gemm_w8's.  Rows past layout.offsets[E] are left unwritten.  Returns None when
-    the library answers ENOTSUP (nothing was enqueued)."""
-    a, out, rows, T, z = _w8_packed_operands(a, image, scale, N, N, K, layout, gather, zero_row, out)
-    if bias is not None:
-        _dev(bias)
-        assert bias.dim() == 2 and bias.shape == (layout.E, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
-    rc = _lib.lib().tutel_amd_expert_gemm_w8_packed(
-        _ptr(a), K, rows, T, z, _ptr(image), image.numel() // max(layout.E, 1), _ptr(scale),
-        _ptr(bias), (bias.stride(0) if bias is not None else 0), _ptr(out), N, layout.E, layout.rows_bound, N, K,
-        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_packed", out)
-
-
-def expert_gemm_w8_glu_packed(a, image, scale, H, K, layout, act="silu", gather=None, zero_row=None, out=None):
-    """expert_gemm_w8_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w8_glu writes for the same
-    row and expert.  a, gather, zero_row as expert_gemm_w8_packed's; image / scale: the interleaved gate / up image and its
-    [E, 2 H] scales.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
-    a, out, rows, T, z = _w8_packed_operands(a, image, scale, 2 * H, H, K, layout, gather, zero_row, out)
-    rc = _lib.lib().tutel_amd_expert_gemm_w8_glu_packed(
-        _ptr(a), K, rows, T, z, _ptr(image), image.numel() // max(layout.E, 1), _ptr(scale),
-        _ptr(out), H, layout.E, layout.rows_bound, H, K,
-        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w8_glu_packed", out)
-
-
-def _w4_packed_operands(a, codes, scales, N, K, layout, gather, zero_row, out):
-    """the operand checks the two packed W4A16 wrappers share -> (a at a 16-byte aligned address, out [rows_bound, N], a_rows, T, zero
-    row, an expert's code bytes, an expert's scale bytes)"""
-    _dev(a, codes, scales, out, zero_row)
-    E, wb, sb = _w4_image(codes, scales)
+def _ws_packed(entry, a, E, weights, bias, N, K, layout, act, gather, zero_row, out, glu=False):
+    """The packed W8A16 / W4A16 wrappers behind their own weight checks (`weights`, glu: as _ws_padded's): a at a 16-byte aligned
+    address, out [rows_bound, N], the rows through layout.slot_map when gather"""
     assert E == layout.E and a.dim() == 2 and a.is_contiguous() and a.shape[1] == K
     a = _a16(a)
     if gather:
@@ -859,7 +790,34 @@ def _w4_packed_operands(a, codes, scales, N, K, layout, gather, zero_row, out):
     if out is None:
         out = torch.empty([layout.rows_bound, N], dtype=a.dtype, device=a.device)
     assert out.shape == (layout.rows_bound, N) and out.is_contiguous() and out.dtype == a.dtype
-    return a, out, (_ptr(layout.slot_map) if gather else None), (a.shape[0] if gather else 0), (_ptr(zero_row) if gather else None), wb, sb
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
+    bias_args = () if glu else (_ptr(bias), (bias.stride(0) if bias is not None else 0))
+    rc = getattr(_lib.lib(), entry)(
+        _ptr(a), K, (_ptr(layout.slot_map) if gather else None), (a.shape[0] if gather else 0), (_ptr(zero_row) if gather else None),
+        *weights, *bias_args, _ptr(out), N, E, layout.rows_bound, N, K,
+        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
+    return _unless_notsup(rc, entry, out)
+
+
+def expert_gemm_w8_packed(a, image, scale, bias, N, K, layout, act="none", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8 over the packed dropless layout: D[r] = act(acc * scale[e] + bias[e]) for the packed rows r of expert e
+    -> [rows_bound, N], bit for bit what expert_gemm_w8 writes for the same row and expert (the contract of include/tutel_amd.h).
+    a [rows_bound, K] bf16 / fp16, or with gather=True the token array [T, K] read through layout.slot_map (zero_row, >= K zeros,
+    for pad rows); image / scale / bias as expert_gemm_w8's.  Rows past layout.offsets[E] are left unwritten.  Returns None when
+    the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, image, scale, bias, out, zero_row)
+    E, weights = _w8_image(image, scale, N)
+    return _ws_packed("tutel_amd_expert_gemm_w8_packed", a, E, weights, bias, N, K, layout, act, gather, zero_row, out)
+
+
+def expert_gemm_w8_glu_packed(a, image, scale, H, K, layout, act="silu", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w8_glu writes for the same
+    row and expert.  a, gather, zero_row as expert_gemm_w8_packed's; image / scale: the interleaved gate / up image and its
+    [E, 2 H] scales.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(a, image, scale, out, zero_row)
+    E, weights = _w8_image(image, scale, 2 * H)
+    return _ws_packed("tutel_amd_expert_gemm_w8_glu_packed", a, E, weights, None, H, K, layout, act, gather, zero_row, out, glu=True)
 
 
 def expert_gemm_w4_packed(a, codes, scales, bias, N, K, layout, act="none", gather=None, zero_row=None, out=None):
@@ -870,27 +828,18 @@ def expert_gemm_w4_packed(a, codes, scales, bias, N, K, layout, act="none", gath
     tile runs as two 128-row halves; TUTEL_AMD_W4_PACKED_TILE=wide (read at every call) covers it in one work item instead (measured
     slower), the same bits.  Returns None
     when the library answers ENOTSUP (nothing was enqueued)."""
-    a, out, rows, T, z, wb, sb = _w4_packed_operands(a, codes, scales, N, K, layout, gather, zero_row, out)
-    if bias is not None:
-        _dev(bias)
-        assert bias.dim() == 2 and bias.shape == (layout.E, N) and bias.stride(1) == 1 and bias.dtype == a.dtype
-    rc = _lib.lib().tutel_amd_expert_gemm_w4_packed(
-        _ptr(a), K, rows, T, z, _ptr(codes), wb, _ptr(scales), sb,
-        _ptr(bias), (bias.stride(0) if bias is not None else 0), _ptr(out), N, layout.E, layout.rows_bound, N, K,
-        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4_packed", out)
+    _dev(a, codes, scales, bias, out, zero_row)
+    E, weights = _w4_image(codes, scales)
+    return _ws_packed("tutel_amd_expert_gemm_w4_packed", a, E, weights, bias, N, K, layout, act, gather, zero_row, out)
 
 
 def expert_gemm_w4_glu_packed(a, codes, scales, H, K, layout, act="silu", gather=None, zero_row=None, out=None):
     """expert_gemm_w4_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w4_glu writes for the same
     row and expert.  a, gather, zero_row as expert_gemm_w4_packed's; codes / scales: the interleaved gate / up images.  Returns None
     when the library answers ENOTSUP (nothing was enqueued)."""
-    a, out, rows, T, z, wb, sb = _w4_packed_operands(a, codes, scales, H, K, layout, gather, zero_row, out)
-    rc = _lib.lib().tutel_amd_expert_gemm_w4_glu_packed(
-        _ptr(a), K, rows, T, z, _ptr(codes), wb, _ptr(scales), sb,
-        _ptr(out), H, layout.E, layout.rows_bound, H, K,
-        _DT.get(a.dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
-    return _unless_notsup(rc, "tutel_amd_expert_gemm_w4_glu_packed", out)
+    _dev(a, codes, scales, out, zero_row)
+    E, weights = _w4_image(codes, scales)
+    return _ws_packed("tutel_amd_expert_gemm_w4_glu_packed", a, E, weights, None, H, K, layout, act, gather, zero_row, out, glu=True)
 
 
 def _grad_out_dtype(out_dtype, operand_dtype):
