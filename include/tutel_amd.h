@@ -314,6 +314,67 @@ int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_st
                                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                                  tutel_stream_t stream);
 
+/* W8A8 (csrc/expert_gemm_w8a8.hip): tutel_amd_expert_gemm_w8 with the activations quantised as well -- e4m3 codes with ONE fp32 scale
+ * per row (tutel_amd_quantize_rows_a8, below) -- so that both operands enter the fp8 matrix instruction as stored.  The weight image
+ * Wq, scale, bias, D, `dtype` (bias' and D's: TUTEL_BF16 or TUTEL_F16) and act are exactly tutel_amd_expert_gemm_w8's.
+ * Numeric contract (part of the interface):
+ *     acc[e, r, n] = sum_k val(Aq[row, k]) * val(Wq[e, n, k])    ONE fp32 accumulator per output: a chain of
+ *                                                                v_mfma_f32_32x32x16_fp8_fp8 over K ascending in steps of 16; no
+ *                                                                split-K, no atomics.  val(c): the value of the e4m3 code; 0x7F and
+ *                                                                0xFF are NaN and propagate.  The order of the 16 products summed
+ *                                                                inside one instruction is the hardware's: the result is exact whenever
+ *                                                                every partial sum is representable in fp32, and otherwise within fp32
+ *                                                                accumulation error of the exact sum
+ *     v = acc * a_scale[row]         one fp32 multiply with its own rounding
+ *     v = v * scale[e, n]            a second fp32 multiply with its own rounding, not contracted with what follows
+ *     v = v + float(bias[e, n])      one fp32 add (skipped when bias is NULL)
+ *     v = act(v)                     tutel_amd_expert_gemm_w8's formulas
+ *     D[e, r, n] = v rounded once to `dtype`.
+ * Rows of Aq: e4m3 BYTES with byte strides.  Plain form: [E_loc, R, K], row (e, r) at Aq + e * a_stride_e + r * lda and its scale at
+ * a_scale[e * R + r] (a_rows_per_w >= R, a_stride_w = 0).  Gathered form: slot_map != NULL, Aq is the quantised TOKEN array [T, lda]
+ * and a_scale [T]; row (e, r) is token slot_map[e*R + r] % T with that token's scale; a negative slot reads zero_row (>= K bytes
+ * 0x00) with scale 1.0.  Rows of D as in tutel_amd_expert_gemm_w8.
+ * Covered (tutel_amd_expert_gemm_w8a8_supported(dtype, N, K) == 1: a pure function, no HIP call): bf16 / fp16 outputs, K % 64 == 0,
+ * N % 32 == 0; lda and a_stride_e % 16 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K; any
+ * R >= 1 (tuned for R <= 128; more rows stream the weights once per 128), E_loc * R and the tile count below 2^31.  Ragged last tiles
+ * clamp their loads and mask their stores: nothing is read or written outside the operands.  NOT covered: row_counts (megablocks), the
+ * [W, E_loc, C, *] exchange layouts, peer stores, the packed dropless layout.  Anything not covered returns TUTEL_AMD_ENOTSUP with
+ * nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  Aq, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte
+ * aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w8a8_supported(int dtype, int N, int K);
+int tutel_amd_expert_gemm_w8a8(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
+                               const void *Wq, int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
+                               int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int N, int K,
+                               int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                               tutel_stream_t stream);
+
+/* W8A8 for SwiGLU experts: tutel_amd_expert_gemm_w8_glu over quantised rows, in its order:
+ *     gacc, uacc as acc above, over the gate / up channels of the interleaved image Wq_gu (tutel_amd_expert_gemm_w8_glu's)
+ *     g = round_T( act( (gacc * a_scale[row]) * scale_gate[e, n] ) )
+ *     u = (uacc * a_scale[row]) * scale_up[e, n]
+ *     D[e, r, n] = round_T( float(g) * u )                n < H, no bias
+ * Covered (tutel_amd_expert_gemm_w8a8_glu_supported(dtype, H, K) == 1): K % 64 == 0, H % 16 == 0, H >= 16, w_stride_e >= 2 * H * K and
+ * the conditions of tutel_amd_expert_gemm_w8a8. */
+int tutel_amd_expert_gemm_w8a8_glu_supported(int dtype, int H, int K);
+int tutel_amd_expert_gemm_w8a8_glu(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w,
+                                   int lda, const void *Wq_gu, int64_t w_stride_e, const float *scale_gu, void *D, int64_t d_stride_e,
+                                   int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int H, int K, int dtype, int act,
+                                   const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                                   tutel_stream_t stream);
+
+/* The per-row activation quantiser of the W8A8 GEMMs (csrc/quantize_a8.hip).  X [rows, K] in `dtype` (TUTEL_BF16 or TUTEL_F16), row r
+ * at X + r * ldx elements -> Xq [rows, K] e4m3 bytes, row r at Xq + r * ldq bytes, and scale [rows] fp32.  Contract, per row, bit for
+ * bit tutel_amd/experts/w8.py::quantize_e4m3(X.unsqueeze(0), True) on a CPU:
+ *     scale[r]  = fp32(amax_k |X[r, k]|) / 448.0f      a correctly rounded fp32 division; an all-zero row: 1
+ *     Xq[r, k]  = e4m3_rne(clamp(fp32(X[r, k]) / scale[r], -448, 448))
+ * A row that holds an inf or a NaN gets scale = NaN and the NaN code 0x7F in every position (the GEMM then writes NaN outputs for the
+ * row): there is no status word and no host read, the launch can be captured in a HIP graph.
+ * Covered (tutel_amd_quantize_rows_a8_supported(dtype, K) == 1: a pure function): bf16 / fp16, K % 64 == 0, 64 <= K <= 8192 (a row is
+ * kept in registers between the amax pass and the convert); ldx, ldq >= K, ldx % 8 == 0, ldq % 8 == 0 (% 16 for the GEMM), X 16-byte
+ * and Xq 8-byte aligned.  Anything else returns TUTEL_AMD_ENOTSUP with nothing enqueued; rows == 0 is a successful no-op. */
+int tutel_amd_quantize_rows_a8_supported(int dtype, int K);
+int tutel_amd_quantize_rows_a8(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale, tutel_stream_t stream);
+
 /* W4A16 (csrc/expert_gemm_w4.hip): the grouped GEMM of bf16 / fp16 experts whose weights are stored as OCP MXFP4 -- e2m1 codes, two
  * per byte, with one e8m0 scale byte per block of 32 values along K.  Activations, bias and output stay in `dtype` (TUTEL_BF16 or
  * TUTEL_F16).  Numeric contract (part of the interface):

@@ -50,6 +50,14 @@ SIGNATURES = {
     "tutel_amd_expert_gemm_w8_glu_supported": (_i, [_i, _i, _i]),
     "tutel_amd_expert_gemm_w8_glu": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _i64, _i, _i,
                                           _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tutel_amd_expert_gemm_w8a8_supported": (_i, [_i, _i, _i]),
+    "tutel_amd_expert_gemm_w8a8": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i,
+                                        _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tutel_amd_expert_gemm_w8a8_glu_supported": (_i, [_i, _i, _i]),
+    "tutel_amd_expert_gemm_w8a8_glu": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _i64, _i, _i,
+                                            _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tutel_amd_quantize_rows_a8_supported": (_i, [_i, _i]),
+    "tutel_amd_quantize_rows_a8": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "tutel_amd_expert_gemm_w4_supported": (_i, [_i, _i, _i]),
     "tutel_amd_expert_gemm_w4": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i,
                                       _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),

@@ -16,7 +16,7 @@
 // bit for bit against the CPU must not depend on an instruction's treatment of denormal quotients or of -0.
 // Byte model: the parameter read twice (the second time from L2 where a workgroup's 32 x K tile stays resident: 128 KB at K = 2048
 // in 16 bits), the image written once.
-#include "common.h"
+#include "quantize_e4m3.h"   // qw_e4m3fn, qw_code, qw_umax: shared with the row quantiser (quantize_a8.hip)
 
 #define QW_THREADS 256
 #define QW_CH 32          // source channels per workgroup
@@ -32,35 +32,6 @@ struct QwArgs {
   int group, group_stride, group_offset;
   int32_t *status;
 };
-
-// fp32 -> e4m3fn code, round to nearest even; |x| >= 480 and NaN give the NaN code (never reached behind the clamp for finite input).
-// Below 2^-6 the codes are subnormal, spacing 2^-9: adding 2^14 (whose ulp is 2^-9) rounds to that spacing in one fp32 addition and
-// leaves the code in the low mantissa bits.  Above, the rounding is done on the bit pattern: rebias the exponent by 7 - 127, add half
-// of the dropped 20 bits minus one, plus the kept part's last bit (ties to even), and drop them.
-__device__ __forceinline__ uint32_t qw_e4m3fn(float x) {
-  uint32_t u = __float_as_uint(x);
-  const uint32_t sign = u & 0x80000000u;
-  u ^= sign;
-  uint32_t r;
-  if (u >= 0x43f00000u) {
-    r = 0x7fu;
-  } else if (u < 0x3c800000u) {
-    r = __float_as_uint(__fadd_rn(__uint_as_float(u), 16384.0f)) - 0x46800000u;
-  } else {
-    u += 0xc4000000u + 0x7ffffu + ((u >> 20) & 1u);
-    r = u >> 20;
-  }
-  return r | (sign >> 24);
-}
-
-// clamp(w / scale, -448, 448) as the reference's: a true division, NaN passes through, -0 keeps its sign
-__device__ __forceinline__ uint32_t qw_code(float w, float scale) {
-  float q = __fdiv_rn(w, scale);
-  q = q < -448.0f ? -448.0f : (q > 448.0f ? 448.0f : q);
-  return qw_e4m3fn(q);
-}
-
-__device__ __forceinline__ uint32_t qw_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // source channel n -> image channel
 __device__ __forceinline__ int qw_image_channel(const QwArgs &p, int n) {

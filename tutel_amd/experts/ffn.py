@@ -18,7 +18,9 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     gathered from the tokens, fc2 read in its checkpoint layout.  No autograd, no megablocks row counts, local experts only;
   * FP8 weights, opt-in (module.fp8_weights, default from TUTEL_AMD_FP8_WEIGHTS=1): bf16 / fp16 experts in inference read e4m3 codes
     with one fp32 scale per (expert, output channel) instead of the 16-bit weights (W8A16: activations are not quantised) -- two
-    launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py).  A dropless
+    launches of tutel_amd_expert_gemm_w8; the quantised images are derived copies in the KMajorCache (experts/w8.py).  With
+    module.fp8_activations as well (default from TUTEL_AMD_FP8_ACTIVATIONS=1) the rows are quantised per token too (W8A8): four
+    launches -- quantise the tokens, fc1 on the fp8 matrix instruction, quantise the hidden rows, fc2 -- over the same images.  A dropless
     layer with `dropless_packed` and `dropless_packed_fp8` runs them over the packed layout instead (impls/packed_w8.py).
     module.fp8_freeze() makes images and scales the module's own buffers, written by the HIP quantiser (csrc/quantize_w8.hip), and
     frees the 16-bit weights: the same launches on the same bits, inference only, FP8 state dicts (experts/fp8_resident.py);
@@ -55,6 +57,9 @@ _FP8_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP8_WEIGHTS", "0")) != 0
 # opt-in: the same experts stream their weights as OCP MXFP4 (csrc/expert_gemm_w4.hip); the default of every module's `fp4_weights`
 # switch.  Off: nothing changes
 _FP4_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP4_WEIGHTS", "0")) != 0
+# opt-in, on top of FP8 weights: the activations are quantised per row as well and both operands run on the fp8 matrix instruction
+# (csrc/quantize_a8.hip, csrc/expert_gemm_w8a8.hip); the default of every module's `fp8_activations` switch.  Off: nothing changes
+_FP8_ACTIVATIONS = int(os.environ.get("TUTEL_AMD_FP8_ACTIVATIONS", "0")) != 0
 
 
 def _FFN_FUSED_ON():
@@ -300,6 +305,20 @@ def _run_w4(net, x, R, slot_map):
     return ops.expert_gemm_w4(h, c2, s2, b2, w2.size(2), w2.size(1)) if h is not None else None
 
 
+def _run_w8a8(net, x, R, slot_map):
+    """four launches: the rows quantised per row (the TOKENS, once, where fc1 gathers), fc1, the hidden rows quantised, fc2"""
+    (i1, s1), (i2, s2) = net.w8_params()
+    w1, b1, w2, b2 = _inference_params(net)
+    E, H, M = w1.shape
+    xq = ops.quantize_rows_a8(x.reshape(-1, M))
+    if xq is None:
+        return None
+    h = ops.expert_gemm_w8a8(xq[0] if slot_map is not None else xq[0].view(E, -1, M), xq[1], i1, s1, b1, H, M, x.dtype,
+                             act=net.fused_activation(), slot_map=slot_map, R=R)
+    hq = ops.quantize_rows_a8(h.view(-1, H)) if h is not None else None
+    return ops.expert_gemm_w8a8(hq[0].view(E, -1, H), hq[1], i2, s2, b2, w2.size(2), H, x.dtype) if hq is not None else None
+
+
 _W8_DTYPES = _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16))
 _W8_SHAPE = _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
                    lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K))
@@ -323,6 +342,18 @@ W8 = Engine(
             _rung(W8_CAPTURE_REASON,   # (FP8-resident experts hold their images for good)
                   lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.fp8_frozen and not (
                       net._kmajor.holds("fc1.w8", net.batched_fc1_w, "w8") and net._kmajor.holds("fc2.w8", net.batched_fc2_w, "w8")))))
+# FP8 activations on top of FP8 weights (W8A8): its switch, what it applies to, then the W8 ladder's rungs from _SKIP on and its own shape
+# rung (the row quantiser keeps a row in registers: K <= 8192).  The switch's rungs are shared with SwiGLU experts
+_SWITCH_A8 = _rung("fp8_activations is off (TUTEL_AMD_FP8_ACTIVATIONS)", lambda net, x, ctx, mb: not net.fp8_activations)
+_A8_NEEDS_W8 = _rung("fp8_activations applies on top of fp8_weights or an FP8-resident module",
+                     lambda net, x, ctx, mb: not (net.fp8_weights or net.fp8_frozen))
+_A8_SHAPE = _rung("the shape is not covered by the W8A8 kernels (M and H multiples of 64, at most 8192)",
+                  lambda net, x, ctx, mb: not all(ops.gemm_w8a8_supported(x.dtype, N, K) and ops.quantize_rows_a8_supported(x.dtype, K)
+                                                  for N, K in ((net.batched_fc1_w.size(1), net.batched_fc1_w.size(2)),
+                                                               (net.batched_fc2_w.size(2), net.batched_fc2_w.size(1)))))
+W8A8 = Engine(
+    ran="_fp8_activations_ran", entry="tutel_amd_expert_gemm_w8a8", run=_run_w8a8,
+    ladder=(_SWITCH_A8, _A8_NEEDS_W8) + W8.ladder[1:-1] + (_A8_SHAPE, W8.ladder[-1]))
 # the FP4 switch's own rungs, shared with SwiGLU experts
 _SWITCH_W4 = _rung("fp4_weights is off (TUTEL_AMD_FP4_WEIGHTS)", lambda net, x, ctx, mb: not net.fp4_weights)
 _W4_NOT_W8 = _rung("fp8_weights is on as well (one weight format per module)", lambda net, x, ctx, mb: net.fp8_weights)
@@ -340,9 +371,10 @@ W4 = Engine(
                       net._kmajor.holds("fc1.w4", net.batched_fc1_w, "w4") and net._kmajor.holds("fc2.w4", net.batched_fc2_w, "w4")))))
 # the rungs of the W4 ladder that a module answers without a forward, in the ladder's order: what fp4_freeze() requires
 W4_STATIC = (_W4_NOT_W8, _W4_NOT_FROZEN, _SKIP, _DEVICE, _TRAINING_W8, _W8_DTYPES, _GATHERED, _ACTIVATION, _W4_SHAPE)
-# the order FusedExpertsNetwork.forward tries them in.  W8 and W4 exclude each other by W4's second rung (with both switches on FP8
+# the order FusedExpertsNetwork.forward tries them in.  W8A8 stands in front of W8: it asks for W8's own conditions and more, so a
+# forward it refuses is W8's as before.  W8 and W4 exclude each other by W4's second rung (with both switches on FP8
 # runs as it does alone), and either excludes F32 by dtype; an engine that is switched off is asked its first rung and nothing else
-ENGINES = (W8, W4, F32)
+ENGINES = (W8A8, W8, W4, F32)
 
 
 class FusedExpertsNetwork(torch.nn.Module):
@@ -381,6 +413,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         self._kmajor = KMajorCache()
         # FP8 (e4m3) weights in inference, W8A16 (the W8 engine); the 16-bit parameters stay as they are
         self.fp8_weights = _FP8_WEIGHTS
+        # on top of it (or of an FP8-resident module): FP8 activations, W8A8 (the W8A8 engine)
+        self.fp8_activations = _FP8_ACTIVATIONS
         # MXFP4 weights in inference, W4A16 (the W4 engine); the 16-bit parameters stay as they are
         self.fp4_weights = _FP4_WEIGHTS
 
@@ -476,7 +510,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def admitted_engine(self, x, ctx, megablocks_size=None):
         """the opt-in engine this forward's experts run on, or None: the default GEMMs.  An engine that is switched off costs its
         switch and nothing else"""
-        engines = (W8,) if self.fp8_frozen else (W4,) if self.fp4_frozen else ENGINES
+        engines = (W8A8, W8) if self.fp8_frozen else (W4,) if self.fp4_frozen else ENGINES
         return next((e for e in engines if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
 
     def forward_engine(self, engine, x, R=None, slot_map=None):
@@ -657,9 +691,10 @@ class FusedExpertsNetwork(torch.nn.Module):
         if self.skip_expert:
             return x
         # the opt-in engines (W8 and W4 in front of the default GEMMs, F32 behind them); the reason one did not run is kept for the caller
-        y = None if self.fp4_frozen else self._forward_if_admitted(W8, x, ctx)
-        if y is not None:
-            return y
+        for engine in (W8A8, W8):
+            y = None if self.fp4_frozen else self._forward_if_admitted(engine, x, ctx)
+            if y is not None:
+                return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
             raise RuntimeError(fp8_resident.REFUSED + (self.engine_refusal(W8, x, ctx) or "the input is not [E_loc, R, M]"))
         y = self._forward_if_admitted(W4, x, ctx)

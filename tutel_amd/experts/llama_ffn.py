@@ -55,6 +55,13 @@ W8_LADDER = (
     _ffn._SWITCH_W8, _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE,
     _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w8_cached()),
 )
+# FP8 activations on top (W8A8): the switch's rungs of experts/ffn.py, the W8 ladder from the device rung on, the W8A8 kernels' shapes
+_A8_SHAPE = _ffn._rung("the shape is not covered by the W8A8 kernels (M and H multiples of 64, at most 8192)",
+                       lambda net, x, ctx, mb: not (ops.gemm_w8a8_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
+                                                    and ops.gemm_w8a8_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1])
+                                                    and ops.quantize_rows_a8_supported(x.dtype, net.W_fc1_full_shape[1])
+                                                    and ops.quantize_rows_a8_supported(x.dtype, net.W_fc1_full_shape[2])))
+A8_LADDER = (_ffn._SWITCH_A8, _ffn._A8_NEEDS_W8) + W8_LADDER[1:-1] + (_A8_SHAPE, W8_LADDER[-1])
 # the same for MXFP4 weights (W4A16): the FP4 switch's rungs, the W8 ladder's from the device rung on, its own shape and capture rungs
 _W4_SHAPE = _ffn._rung("the shape is not covered (M a multiple of 64, H a multiple of 64)",
                        lambda net, x, ctx, mb: not (ops.gemm_w4_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
@@ -97,6 +104,8 @@ class LlamaFFNNetwork(torch.nn.Module):
         self._kmajor = KMajorCache()
         # FP8 (e4m3) weights in inference, W8A16; the 16-bit parameters stay as they are
         self.fp8_weights = _ffn._FP8_WEIGHTS
+        # on top of it (or of an FP8-resident module): FP8 activations, W8A8
+        self.fp8_activations = _ffn._FP8_ACTIVATIONS
         # MXFP4 weights in inference, W4A16; the 16-bit parameters stay as they are
         self.fp4_weights = _ffn._FP4_WEIGHTS
         self.reset_parameters()
@@ -204,6 +213,40 @@ class LlamaFFNNetwork(torch.nn.Module):
         except AttributeError:
             pass
         return self.forward_fused_w8(x.contiguous()) if why is None else None
+
+    # -- FP8 activations on top of FP8 weights (W8A8) ---------------------------------------------
+    def w8a8_refusal(self, x, ctx):
+        """why this forward does not quantise its activations (the first failing check of A8_LADDER), or None when it runs W8A8"""
+        reasons = (check(self, x, ctx, None) for check in A8_LADDER)
+        return next((why for why in reasons if why is not None), None)
+
+    def forward_fused_w8a8(self, x):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M] in four launches: the rows quantised, gate and up on the fp8 matrix instruction,
+        the hidden rows quantised, W_fc3"""
+        (igu, sgu), (i3, s3) = self.w8_params()
+        E, M, H = self.W_fc1_full_shape
+        xq = ops.quantize_rows_a8(x.view(-1, M))
+        h = ops.expert_gemm_w8a8_glu(xq[0].view(E, -1, M), xq[1], igu, sgu, H, M, x.dtype, act=self.fused_activation()) if xq is not None else None
+        hq = ops.quantize_rows_a8(h.view(-1, H)) if h is not None else None
+        y = ops.expert_gemm_w8a8(hq[0].view(E, -1, H), hq[1], i3, s3, None, M, H, x.dtype) if hq is not None else None
+        if y is None:   # the ladder asked the library's own coverage queries: a refusal here is a bug, never a quiet forward elsewhere
+            from .. import _lib
+            raise _lib.TutelAmdError("the W8A8 expert GEMMs refused a shape their own queries admit: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
+    def _forward_if_w8a8(self, x, ctx):
+        """forward()'s W8A8 step, in front of the W8A16 one: the output, or None where a check refuses -- the reason is kept"""
+        if not (self.fp8_weights or self.fp8_frozen):
+            return None
+        why = self.w8a8_refusal(x, ctx)
+        if why is None and not (x.dim() == 3 and x.size(0) == self.W_fc1_full_shape[0] and x.size(2) == self.W_fc1_full_shape[1]):
+            why = "the input is not [E_loc, R, M]"
+        try:
+            setattr(ctx, "_fp8_activations_ran", True if why is None else why)
+        except AttributeError:
+            pass
+        return self.forward_fused_w8a8(x.contiguous()) if why is None else None
 
     # -- MXFP4 weights (W4A16) ------------------------------------------------------------------
     def w4_refusal(self, x, ctx):
@@ -314,7 +357,9 @@ class LlamaFFNNetwork(torch.nn.Module):
 
     # -- reference-equivalent ATen path -----------------------------------------------------
     def forward(self, x, ctx):
-        y = None if self.fp4_frozen else self._forward_if_w8(x, ctx)
+        y = None if self.fp4_frozen else self._forward_if_w8a8(x, ctx)
+        if y is None and not self.fp4_frozen:
+            y = self._forward_if_w8(x, ctx)
         if y is not None:
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights

@@ -404,6 +404,8 @@ class MOELayer(torch.nn.Module):
                                      min(top_k, logits.shape[1]), cf, alignment, plan)
         self._dropless_packed_ran = True
         setattr(self, fmt.engine.ran, True)
+        if fmt is packed_w8.FP8 and getattr(self.experts, "fp8_activations", False):
+            self._fp8_activations_ran = "the packed dropless forward has no W8A8 GEMM"   # it keeps W8A16
         self.megablocks_size = megablocks_size
         return y, l_aux
 
@@ -483,7 +485,7 @@ class MOELayer(torch.nn.Module):
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
-        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_weights_ran, _fp4_weights_ran: True, or why this forward's experts did not take the engine
+        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_activations_ran, _fp8_weights_ran, _fp4_weights_ran: True, or why this forward's experts did not take the engine
             setattr(self, engine.ran, None)
         if self.skip_moe:
             out = input
@@ -520,11 +522,13 @@ class MOELayer(torch.nn.Module):
             # why this forward's experts will not take an engine that is switched on, known before routing (None: admitted so far;
             # whoever runs them -- the "fused_encode" route below, FusedExpertsNetwork.forward -- sets True, or a later reason)
             for engine in _ffn.ENGINES:
-                if engine.on(self.experts):
+                # (W8A8 reports wherever W8 is asked for: with its own switch off the reason names that switch)
+                if engine.on(self.experts) or (engine is _ffn.W8A8 and (_ffn.W8.on(self.experts) or self.experts.fp8_frozen)):
                     setattr(self, engine.ran, self.experts.engine_refusal(engine, x, self, megablocks_size))
         elif isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp8_weights:
             # SwiGLU experts: the same report (LlamaFFNNetwork.forward sets True, or a later reason)
             self._fp8_weights_ran = self.experts.w8_refusal(x, self)
+            self._fp8_activations_ran = self.experts.w8a8_refusal(x, self)
         if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp4_weights:
             self._fp4_weights_ran = self.experts.w4_refusal(x, self)
         if getattr(self.experts, "fp8_frozen", False):

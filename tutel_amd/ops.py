@@ -540,6 +540,87 @@ def expert_gemm_w8_glu(a, image, scale, H, K, act="silu", slot_map=None, R=None,
     return _ws_padded("tutel_amd_expert_gemm_w8_glu", a, E_loc, weights, None, H, K, act, slot_map, R, out, row_counts, glu=True)
 
 
+def quantize_rows_a8_supported(dtype, K):
+    """rows the HIP activation quantiser (tutel_amd_quantize_rows_a8) takes: bf16 / fp16, K % 64 == 0, K <= 8192 -- the library's own
+    answer"""
+    return dtype in _DT and bool(_lib.lib().tutel_amd_quantize_rows_a8_supported(_DT[dtype], int(K)))
+
+
+def quantize_rows_a8(x, out=None, scale=None):
+    """x [rows, K] bf16 / fp16 (rows may be strided) -> (codes [rows, K] uint8, scale [rows] fp32): per row, bit for bit
+    experts/w8.py::quantize_e4m3(x.unsqueeze(0), True) -- scale = amax / 448, e4m3 codes of x / scale (the contract of
+    include/tutel_amd.h).  A row with a non-finite value gets scale NaN and code 0x7F throughout; no host read, capturable.
+    out / scale: written in place when given (contiguous).  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(x, out, scale)
+    assert x.dim() == 2 and x.stride(1) == 1
+    x = _a16(x)
+    rows, K = x.shape
+    if out is None:
+        out = torch.empty([rows, K], dtype=torch.uint8, device=x.device)
+    if scale is None:
+        scale = torch.empty([rows], dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (rows, K)
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == rows
+    rc = _lib.lib().tutel_amd_quantize_rows_a8(_ptr(x), _DT.get(x.dtype, -1), x.stride(0) if rows > 1 else max(x.stride(0), K), rows, K,
+                                               _ptr(out), K, _ptr(scale), _stream())
+    return _unless_notsup(rc, "tutel_amd_quantize_rows_a8", (out, scale))
+
+
+def _a8_padded(entry, aq, a_scale, E_loc, weights, bias, N, K, dtype, act, slot_map, R, out, row_counts, glu=False):
+    """The W8A8 wrappers behind their weight checks, in _ws_padded's shape: aq is uint8 (e4m3 codes) with a_scale fp32 per row of aq,
+    and the output's dtype is an argument of its own"""
+    if aq.dtype == torch.float8_e4m3fn:
+        aq = aq.view(torch.uint8)
+    assert aq.dtype == torch.uint8 and a_scale.dtype == torch.float32 and a_scale.is_contiguous()
+    aq, R, a_layout, T, z = _a_rows(aq, E_loc, K, slot_map, R, None)
+    assert a_scale.numel() == (T if slot_map is not None else E_loc * R)
+    if out is None:
+        out = torch.empty([E_loc, R, N], dtype=dtype, device=aq.device)
+    assert out.dtype == dtype and out.is_contiguous() and out.shape == (E_loc, R, N)
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E_loc, N) and bias.stride(1) == 1 and bias.dtype == dtype
+    bias_args = () if glu else (_ptr(bias), (bias.stride(0) if bias is not None else 0))
+    rc = getattr(_lib.lib(), entry)(
+        _ptr(aq), _ptr(a_scale), a_layout[0], a_layout[1], a_layout[2], a_layout[3],
+        *weights, *bias_args,
+        _ptr(out), R * N, 0, max(R, 1), N,
+        E_loc, R, N, K, _DT.get(dtype, -1), ACT_CODES[act], _ptr(row_counts), _ptr(slot_map), T, _ptr(z), _stream())
+    return _unless_notsup(rc, entry, out)
+
+
+def gemm_w8a8_supported(dtype, N, K):
+    """shapes the W8A8 grouped GEMM (tutel_amd_expert_gemm_w8a8) takes: bf16 / fp16 outputs, K % 64 == 0, N % 32 == 0 -- the library's
+    own answer"""
+    return _ws_supported("tutel_amd_expert_gemm_w8a8", dtype, N, K)
+
+
+def gemm_w8a8_glu_supported(dtype, H, K):
+    """the same for the gate / up GEMM (tutel_amd_expert_gemm_w8a8_glu): K % 64 == 0, H % 16 == 0"""
+    return _ws_supported("tutel_amd_expert_gemm_w8a8_glu", dtype, H, K)
+
+
+def expert_gemm_w8a8(aq, a_scale, image, scale, bias, N, K, dtype, act="none", slot_map=None, R=None, out=None, row_counts=None):
+    """W8A8: D[e,r,n] = act((acc * a_scale[row]) * scale[e,n] + bias[e,n]) rounded once to `dtype`, acc the fp32 accumulator of the fp8
+    matrix instruction over the e4m3 codes of row and weight (the contract of include/tutel_amd.h).
+
+    aq: uint8 codes [E_loc, R, K] contiguous with a_scale [E_loc * R] fp32 -- quantize_rows_a8's outputs -- or, with slot_map
+    [E_loc * R], the quantised token array [T, K] with a_scale [T] whose rows fc1 gathers (a negative slot reads a zero row with scale
+    1).  image, scale, bias: expert_gemm_w8's.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, image, scale, bias, out, slot_map, row_counts)
+    E_loc, weights = _w8_image(image, scale, N)
+    return _a8_padded("tutel_amd_expert_gemm_w8a8", aq, a_scale, E_loc, weights, bias, N, K, dtype, act, slot_map, R, out, row_counts)
+
+
+def expert_gemm_w8a8_glu(aq, a_scale, image, scale, H, K, dtype, act="silu", slot_map=None, R=None, out=None, row_counts=None):
+    """W8A8 gate and up products of a SwiGLU expert in ONE launch: expert_gemm_w8_glu over quantised rows, D[e,r,n] =
+    round(round(act(gacc * a_scale[row] * scale_gate[e,n])) * (uacc * a_scale[row] * scale_up[e,n])) -> [E_loc, R, H].  aq, a_scale,
+    slot_map as expert_gemm_w8a8's; image, scale: expert_gemm_w8_glu's.  Returns None when the library answers ENOTSUP."""
+    _dev(aq, a_scale, image, scale, out, slot_map, row_counts)
+    E_loc, weights = _w8_image(image, scale, 2 * H)
+    return _a8_padded("tutel_amd_expert_gemm_w8a8_glu", aq, a_scale, E_loc, weights, None, H, K, dtype, act, slot_map, R, out, row_counts,
+                      glu=True)
+
+
 def gemm_w4_supported(dtype, N, K):
     """shapes the W4A16 grouped GEMM (tutel_amd_expert_gemm_w4) takes: bf16 / fp16 activations, K % 64 == 0, N % 32 == 0 -- the
     library's own answer"""
