@@ -442,6 +442,52 @@ int tutel_amd_expert_gemm_w4_glu(const void *A, int64_t a_stride_e, int64_t a_st
                                  const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
                                  tutel_stream_t stream);
 
+/* W4A8 (csrc/expert_gemm_w4a8.hip): tutel_amd_expert_gemm_w4 with the activations quantised -- e4m3 codes with ONE fp32 scale per row
+ * (tutel_amd_quantize_rows_a8) -- so that both operands enter the block-scaled matrix instruction v_mfma_scale_f32_32x32x64_f8f6f4 as
+ * stored (A = fp4 e2m1, B = fp8 e4m3) and the hardware applies the MX block scale.  The code image Wq, the scale image Ws, bias, D,
+ * `dtype` (bias' and D's: TUTEL_BF16 or TUTEL_F16) and act are exactly tutel_amd_expert_gemm_w4's; the rows Aq, a_scale, slot_map, T and
+ * zero_row exactly tutel_amd_expert_gemm_w8a8's (byte strides; a negative slot reads zero_row with scale 1.0).
+ * Numeric contract (part of the interface):
+ *     acc[e, r, n] = sum over K-tiles of 64, ascending, of the instruction's result over
+ *                        val(code[e, n, k]) * 2^(s[e, n, k / 32] - 127) * val(Aq[row, k])
+ *                    ONE fp32 accumulator per output: no split-K, no atomics.  Each lane hands the instruction one 32-block of codes with
+ *                    its e8m0 scale byte; the activations' block scale is the constant byte 127 (2^0).  val(Aq): the value of the e4m3
+ *                    code, 0x7F and 0xFF are NaN and propagate.  The order of the 64 products summed inside one instruction is the
+ *                    hardware's: the result is exact whenever every partial sum is representable in fp32, and otherwise within fp32
+ *                    accumulation error of the exact sum
+ *     v = acc * a_scale[row]         one fp32 multiply with its own rounding; there is NO channel-scale multiply
+ *     v = v + float(bias[e, n])      one fp32 add (skipped when bias is NULL)
+ *     v = act(v)                     tutel_amd_expert_gemm_w8's formulas
+ *     D[e, r, n] = v rounded once to `dtype`.
+ * Admitted scale bytes: tutel_amd_expert_gemm_w4's ranges (bf16 2 .. 252, fp16 114 .. 140) -- the image is shared with W4A16.
+ * Covered (tutel_amd_expert_gemm_w4a8_supported(dtype, N, K) == 1: a pure function, no HIP call): bf16 / fp16 outputs, K % 64 == 0,
+ * N % 32 == 0; lda and a_stride_e % 16 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K / 2,
+ * s_stride_e % 4 == 0 and >= N * ceil(K / 128) * 4; any R >= 1 (tuned for R <= 128; more rows stream the weights once per 128),
+ * E_loc * R, the tile count and 16 K below 2^31.  Ragged last tiles clamp their loads and mask their stores: nothing is read or written
+ * outside the operands.  NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange layouts, peer stores, the packed dropless
+ * layout.  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  Aq, Wq
+ * and zero_row 16-byte aligned, D and bias 8-byte aligned, Ws and a_scale 4-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w4a8_supported(int dtype, int N, int K);
+int tutel_amd_expert_gemm_w4a8(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
+                               const void *Wq, int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias,
+                               int64_t bias_stride_e, void *D, int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd,
+                               int E_loc, int R, int N, int K, int dtype, int act, const int32_t *row_counts, const int32_t *slot_map,
+                               int T, const void *zero_row, tutel_stream_t stream);
+
+/* W4A8 for SwiGLU experts: tutel_amd_expert_gemm_w4_glu over quantised rows, in its order:
+ *     gacc, uacc as acc above, over the gate / up channels of the interleaved image (tutel_amd_expert_gemm_w4_glu's)
+ *     g = round_T( act( gacc * a_scale[row] ) )
+ *     u = uacc * a_scale[row]
+ *     D[e, r, n] = round_T( float(g) * u )                n < H, no bias
+ * Covered (tutel_amd_expert_gemm_w4a8_glu_supported(dtype, H, K) == 1): K % 64 == 0, H % 16 == 0, H >= 16, w_stride_e >= H * K,
+ * s_stride_e >= 2 * H * ceil(K / 128) * 4 and the conditions of tutel_amd_expert_gemm_w4a8. */
+int tutel_amd_expert_gemm_w4a8_glu_supported(int dtype, int H, int K);
+int tutel_amd_expert_gemm_w4a8_glu(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w,
+                                   int lda, const void *Wq_gu, int64_t w_stride_e, const void *Ws_gu, int64_t s_stride_e, void *D,
+                                   int64_t d_stride_e, int64_t d_stride_w, int d_rows_per_w, int ldd, int E_loc, int R, int H, int K,
+                                   int dtype, int act, const int32_t *row_counts, const int32_t *slot_map, int T, const void *zero_row,
+                                   tutel_stream_t stream);
+
 /* The two W4A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w4.hip): the experts'
  * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value
  * and can be captured in a HIP graph.  Arguments: those of tutel_amd_expert_gemm_w8_packed / _glu_packed (below), with the scale image

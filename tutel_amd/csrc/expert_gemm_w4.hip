@@ -23,17 +23,7 @@
 //
 // SwiGLU experts (tutel_amd_expert_gemm_w4_glu): D = round_T( float(round_T(act(gacc))) * uacc ); gate and up interleaved by 16 channels
 // in one image (experts/w8.py::interleave_gate_up over codes and scale bytes), the gating product register against register.
-#include "gemm_wstream.h"
-
-struct W4Args {
-  const unsigned char *A; long long a_stride_e; int lda;     // elements
-  const unsigned char *Wq; long long w_stride_e;             // bytes
-  const unsigned char *Ws; long long s_stride_e;             // bytes
-  const uint16_t *bias; long long bias_stride_e;             // elements
-  uint16_t *D; long long d_stride_e; int ldd;                // elements
-  int R, N, K, ntm, ntn;
-  const int32_t *slot_map; int T; const unsigned char *zero_row;
-};
+#include "w4_image.h"  // W4Args, W4Ring, W4Weights: shared with expert_gemm_w4a8.hip
 
 template <typename T> struct W4Cvt;
 template <> struct W4Cvt<bf16_t> {  // the two codes of byte SEL of `u`, times `scale` -> two bf16 in one word (low nibble first)
@@ -62,42 +52,14 @@ __device__ __forceinline__ float w4_scale(uint32_t sd, int i) {
   return __builtin_bit_cast(float, ((sd >> (8 * i)) & 0xffu) << 23);
 }
 
-// streamed loads through the channel group's descriptors (each byte is read once by one workgroup per row tile)
-__device__ __forceinline__ u32x4 w4_wload(__amdgpu_buffer_rsrc_t rs, int voff) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 2));
-}
-__device__ __forceinline__ uint32_t w4_sload(__amdgpu_buffer_rsrc_t rs, int voff) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0));
-}
-
 // TUTEL_AMD_W4_PACKED_TILE below
 #define W4_PACKED_DEFAULT_HALVES 1
 
 struct W4Fmt {
   using Args = W4Args;
 
-  // The group's codes are one run of 16 K bytes (K / 64 blocks of 1 KB) and its scales one run of 128 T128 bytes, one descriptor each.
-  // The K-tile's offset is part of the VECTOR offset: the hardware's range check covers the vector and the immediate offset, not the
-  // scalar one
-  template <typename T> struct Ring {
-    __amdgpu_buffer_rsrc_t rs_w, rs_s;
-    int wl, sl;
-    u32x4 w[WS_DEPTH];
-    uint32_t s[WS_DEPTH];
-    __device__ __forceinline__ void open(const W4Args &p, int e, int nt, int lane) {
-      const int nk = p.K / WS_BK;
-      const int T128 = (p.K + 127) >> 7;   // scale dwords per channel
-      rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(p.Wq + (long long)e * p.w_stride_e + (long long)nt * nk * 1024), 0,
-                                               nk * 1024, 0x00020000);
-      rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(p.Ws + (long long)e * p.s_stride_e + (long long)nt * T128 * 128), 0,
-                                               T128 * 128, 0x00020000);
-      wl = lane * 16;
-      sl = (lane & 31) * 4;
-    }
-    __device__ __forceinline__ void load(int d, int t) {
-      w[d] = w4_wload(rs_w, wl + t * 1024);
-      s[d] = w4_sload(rs_s, sl + (t >> 1) * 128);
-    }
+  // w4_image.h's ring, widened to the dtype
+  template <typename T> struct Ring : W4Ring {
     // dword q holds k = 64 t + 16 q + 8 kg .. + 7; t & 1 == d & 1 (the ring depth is even): the tile's two 32-blocks are bytes
     // 2 (d & 1) and 2 (d & 1) + 1 of its scale dword
     __device__ __forceinline__ void widen(int d, u32x4 (&wa)[4]) const {
@@ -113,18 +75,7 @@ struct W4Fmt {
     __device__ __forceinline__ float apply(float acc, int, int) const { return acc; }
   };
 
-  struct Weights {
-    const void *Wq; int64_t w_stride_e; const void *Ws; int64_t s_stride_e;
-    bool strides_ok() const { return w_stride_e % 16 == 0 && s_stride_e % 4 == 0; }
-    bool image_ok(long long NI, int K) const { return w_stride_e >= NI * K / 2 && s_stride_e >= NI * (((long long)K + 127) / 128) * 4; }
-    static bool run_ok(int K) { return (long long)K * 16 <= 0x7fffffffLL; }
-    bool present() const { return Wq && Ws; }
-    bool aligned() const { return ((uintptr_t)Wq % 16) == 0 && ((uintptr_t)Ws % 4) == 0; }
-    void fill(W4Args &a) const {
-      a.Wq = (const unsigned char *)Wq; a.w_stride_e = w_stride_e;
-      a.Ws = (const unsigned char *)Ws; a.s_stride_e = s_stride_e;
-    }
-  };
+  using Weights = W4Weights;
   static constexpr WsText TEXT = {
       {"rows of A must stay 16-byte aligned (lda, a_stride_e % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4",
        "rows of A must stay 16-byte aligned (lda % 8), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4"},
@@ -193,9 +144,6 @@ void W4Fmt::launch(const W4Args &a, const WsTables *pk, bool halves, unsigned gr
 
 extern "C" int tutel_amd_expert_gemm_w4_supported(int dtype, int N, int K) { return ws_supported(dtype, N, K); }
 extern "C" int tutel_amd_expert_gemm_w4_glu_supported(int dtype, int H, int K) { return ws_glu_supported(dtype, H, K); }
-
-#define W4_SMALL "w_stride_e / s_stride_e is smaller than one expert's image (N * K / 2 code bytes, N * ceil(K / 128) * 4 scale bytes)"
-#define W4_SMALL_GU "w_stride_e / s_stride_e is smaller than one expert's image (H * K code bytes, 2 * H * ceil(K / 128) * 4 scale bytes)"
 
 extern "C" int tutel_amd_expert_gemm_w4(const void *A, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda, const void *Wq,
                                         int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias, int64_t bias_stride_e,

@@ -30,7 +30,10 @@ Forward, y = act(x @ W1^T + b1) @ W2 + b2 per local expert, x [E_loc, R, M]:
     `dropless_packed` and `dropless_packed_fp4` runs them over the packed layout instead (impls/packed_w8.py:
     tutel_amd_expert_gemm_w4_packed, no host read, capturable), frozen or not.  module.fp4_freeze() makes the code
     and scale images the module's own buffers, written by the HIP quantiser (csrc/quantize_w4.hip), and frees the 16-bit weights:
-    0.27 x the memory, the same launches on the same bits, inference only, MXFP4 state dicts (experts/fp8_resident.py);
+    0.27 x the memory, the same launches on the same bits, inference only, MXFP4 state dicts (experts/fp8_resident.py).  With
+    module.w4a8 as well (default from TUTEL_AMD_W4A8=1) the rows are quantised per token to e4m3 (W4A8): four launches -- quantise the
+    tokens, fc1 on the block-scaled fp4 x fp8 matrix instruction (tutel_amd_expert_gemm_w4a8), quantise the hidden rows, fc2 -- over
+    the same images, frozen or not; the packed dropless forward keeps W4A16;
   * otherwise fp32 / fp64 experts, weight gradients, and arbitrary python activations stay on ATen batched matmul (rocBLAS /
     hipBLASLt), op for op as the reference.
 """
@@ -60,6 +63,9 @@ _FP4_WEIGHTS = int(os.environ.get("TUTEL_AMD_FP4_WEIGHTS", "0")) != 0
 # opt-in, on top of FP8 weights: the activations are quantised per row as well and both operands run on the fp8 matrix instruction
 # (csrc/quantize_a8.hip, csrc/expert_gemm_w8a8.hip); the default of every module's `fp8_activations` switch.  Off: nothing changes
 _FP8_ACTIVATIONS = int(os.environ.get("TUTEL_AMD_FP8_ACTIVATIONS", "0")) != 0
+# opt-in, on top of MXFP4 weights: the activations are quantised per row (e4m3) and both operands run on the block-scaled fp4 x fp8
+# matrix instruction (csrc/quantize_a8.hip, csrc/expert_gemm_w4a8.hip); the default of every module's `w4a8` switch.  Off: nothing changes
+_W4A8 = int(os.environ.get("TUTEL_AMD_W4A8", "0")) != 0
 
 
 def _FFN_FUSED_ON():
@@ -319,6 +325,20 @@ def _run_w8a8(net, x, R, slot_map):
     return ops.expert_gemm_w8a8(hq[0].view(E, -1, H), hq[1], i2, s2, b2, w2.size(2), H, x.dtype) if hq is not None else None
 
 
+def _run_w4a8(net, x, R, slot_map):
+    """_run_w8a8 over the MXFP4 images: quantise the rows (the TOKENS, once, where fc1 gathers), fc1, quantise the hidden rows, fc2"""
+    (c1, s1), (c2, s2) = net.w4_params()
+    w1, b1, w2, b2 = _inference_params(net)
+    E, H, M = w1.shape
+    xq = ops.quantize_rows_a8(x.reshape(-1, M))
+    if xq is None:
+        return None
+    h = ops.expert_gemm_w4a8(xq[0] if slot_map is not None else xq[0].view(E, -1, M), xq[1], c1, s1, b1, H, M, x.dtype,
+                             act=net.fused_activation(), slot_map=slot_map, R=R)
+    hq = ops.quantize_rows_a8(h.view(-1, H)) if h is not None else None
+    return ops.expert_gemm_w4a8(hq[0].view(E, -1, H), hq[1], c2, s2, b2, w2.size(2), H, x.dtype) if hq is not None else None
+
+
 _W8_DTYPES = _dtypes(W8_DTYPE_REASON, (torch.bfloat16, torch.float16))
 _W8_SHAPE = _shape("the shape is not covered (M and H multiples of 64, H and M_out multiples of 32)",
                    lambda x, N, K: ops.gemm_w8_supported(x.dtype, N, K))
@@ -371,10 +391,25 @@ W4 = Engine(
                       net._kmajor.holds("fc1.w4", net.batched_fc1_w, "w4") and net._kmajor.holds("fc2.w4", net.batched_fc2_w, "w4")))))
 # the rungs of the W4 ladder that a module answers without a forward, in the ladder's order: what fp4_freeze() requires
 W4_STATIC = (_W4_NOT_W8, _W4_NOT_FROZEN, _SKIP, _DEVICE, _TRAINING_W8, _W8_DTYPES, _GATHERED, _ACTIVATION, _W4_SHAPE)
+# FP8 activations on top of MXFP4 weights (W4A8): its switch, what it applies to, then the W4 ladder's rungs from the second on and its own
+# shape rung (the row quantiser keeps a row in registers: K <= 8192).  The switch's rungs are shared with SwiGLU experts
+_SWITCH_W4A8 = _rung("w4a8 is off (TUTEL_AMD_W4A8)", lambda net, x, ctx, mb: not net.w4a8)
+_W4A8_NEEDS_W4 = _rung("w4a8 applies on top of fp4_weights or an FP4-resident module",
+                       lambda net, x, ctx, mb: not (net.fp4_weights or net.fp4_frozen))
+_W4A8_SHAPE = _rung("the shape is not covered by the W4A8 kernels (M and H multiples of 64, at most 8192)",
+                    lambda net, x, ctx, mb: not all(ops.gemm_w4a8_supported(x.dtype, N, K) and ops.quantize_rows_a8_supported(x.dtype, K)
+                                                    for N, K in ((net.batched_fc1_w.size(1), net.batched_fc1_w.size(2)),
+                                                                 (net.batched_fc2_w.size(2), net.batched_fc2_w.size(1)))))
+W4A8 = Engine(
+    ran="_w4a8_ran", entry="tutel_amd_expert_gemm_w4a8", run=_run_w4a8,
+    ladder=(_SWITCH_W4A8, _W4A8_NEEDS_W4) + W4.ladder[1:-1] + (_W4A8_SHAPE, W4.ladder[-1]))
 # the order FusedExpertsNetwork.forward tries them in.  W8A8 stands in front of W8: it asks for W8's own conditions and more, so a
 # forward it refuses is W8's as before.  W8 and W4 exclude each other by W4's second rung (with both switches on FP8
 # runs as it does alone), and either excludes F32 by dtype; an engine that is switched off is asked its first rung and nothing else
-ENGINES = (W8A8, W8, W4, F32)
+# ENGINES: every engine, in the order the records were added (the layer resets and reports each one's `ran`); TRIAL: the order they
+# are TRIED in -- W4A8 in front of W4 for W8A8's reason
+ENGINES = (W8A8, W8, W4, F32, W4A8)
+TRIAL = (W8A8, W8, W4A8, W4, F32)
 
 
 class FusedExpertsNetwork(torch.nn.Module):
@@ -417,6 +452,8 @@ class FusedExpertsNetwork(torch.nn.Module):
         self.fp8_activations = _FP8_ACTIVATIONS
         # MXFP4 weights in inference, W4A16 (the W4 engine); the 16-bit parameters stay as they are
         self.fp4_weights = _FP4_WEIGHTS
+        # on top of it (or of an FP4-resident module): FP8 activations on the block-scaled matrix instruction, W4A8 (the W4A8 engine)
+        self.w4a8 = _W4A8
 
         E, H = num_experts_per_device, self.hidden_size
         self.batched_fc1_w = torch.nn.Parameter(torch.empty(E, H, model_dim))
@@ -510,7 +547,7 @@ class FusedExpertsNetwork(torch.nn.Module):
     def admitted_engine(self, x, ctx, megablocks_size=None):
         """the opt-in engine this forward's experts run on, or None: the default GEMMs.  An engine that is switched off costs its
         switch and nothing else"""
-        engines = (W8A8, W8) if self.fp8_frozen else (W4,) if self.fp4_frozen else ENGINES
+        engines = (W8A8, W8) if self.fp8_frozen else (W4A8, W4) if self.fp4_frozen else TRIAL
         return next((e for e in engines if self.engine_refusal(e, x, ctx, megablocks_size) is None), None)
 
     def forward_engine(self, engine, x, R=None, slot_map=None):
@@ -697,9 +734,10 @@ class FusedExpertsNetwork(torch.nn.Module):
                 return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
             raise RuntimeError(fp8_resident.REFUSED + (self.engine_refusal(W8, x, ctx) or "the input is not [E_loc, R, M]"))
-        y = self._forward_if_admitted(W4, x, ctx)
-        if y is not None:
-            return y
+        for engine in (W4A8, W4):
+            y = self._forward_if_admitted(engine, x, ctx)
+            if y is not None:
+                return y
         if self.fp4_frozen:
             raise RuntimeError(fp8_resident.REFUSED_FP4 + (self.engine_refusal(W4, x, ctx) or "the input is not [E_loc, R, M]"))
 

@@ -71,6 +71,13 @@ W4_LADDER = (
     _ffn._DEVICE, _ffn._AUTOGRAD_W8, _ffn._TRAINING_W8, _ffn._AUTOCAST, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W4_SHAPE,
     _ffn._rung(_ffn.W8_CAPTURE_REASON, lambda net, x, ctx, mb: torch.cuda.is_current_stream_capturing() and not net.w4_cached()),
 )
+# FP8 activations on top (W4A8): the switch's rungs of experts/ffn.py, the W4 ladder from its second rung on, the W4A8 kernels' shapes
+_W4A8_SHAPE = _ffn._rung("the shape is not covered by the W4A8 kernels (M and H multiples of 64, at most 8192)",
+                         lambda net, x, ctx, mb: not (ops.gemm_w4a8_glu_supported(x.dtype, net.W_fc1_full_shape[2], net.W_fc1_full_shape[1])
+                                                      and ops.gemm_w4a8_supported(x.dtype, net.W_fc3_full_shape[2], net.W_fc3_full_shape[1])
+                                                      and ops.quantize_rows_a8_supported(x.dtype, net.W_fc1_full_shape[1])
+                                                      and ops.quantize_rows_a8_supported(x.dtype, net.W_fc1_full_shape[2])))
+W4A8_LADDER = (_ffn._SWITCH_W4A8, _ffn._W4A8_NEEDS_W4) + W4_LADDER[1:-1] + (_W4A8_SHAPE, W4_LADDER[-1])
 # the rungs a module answers without a forward, in the ladder's order: what fp8_freeze() and fp4_freeze() require
 W8_STATIC = (_ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W8_SHAPE)
 W4_STATIC = (_ffn._W4_NOT_W8, _ffn._W4_NOT_FROZEN, _ffn._DEVICE, _ffn._TRAINING_W8, _W8_DTYPES, _W8_GATHERED, _ffn._ACTIVATION, _W4_SHAPE)
@@ -108,6 +115,8 @@ class LlamaFFNNetwork(torch.nn.Module):
         self.fp8_activations = _ffn._FP8_ACTIVATIONS
         # MXFP4 weights in inference, W4A16; the 16-bit parameters stay as they are
         self.fp4_weights = _ffn._FP4_WEIGHTS
+        # on top of it (or of an FP4-resident module): FP8 activations on the block-scaled matrix instruction, W4A8
+        self.w4a8 = _ffn._W4A8
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -299,6 +308,41 @@ class LlamaFFNNetwork(torch.nn.Module):
             pass
         return self.forward_fused_w4(x.contiguous()) if why is None else None
 
+    # -- FP8 activations on top of MXFP4 weights (W4A8) ------------------------------------------
+    def w4a8_refusal(self, x, ctx):
+        """why this forward does not run W4A8 (the first failing check of W4A8_LADDER), or None when it does"""
+        reasons = (check(self, x, ctx, None) for check in W4A8_LADDER)
+        return next((why for why in reasons if why is not None), None)
+
+    def forward_fused_w4a8(self, x):
+        """x [E_loc, R, M] contiguous -> [E_loc, R, M] in four launches: the rows quantised, gate and up on the block-scaled matrix
+        instruction, the hidden rows quantised, W_fc3"""
+        (cgu, sgu), (c3, s3) = self.w4_params()
+        E, M, H = self.W_fc1_full_shape
+        xq = ops.quantize_rows_a8(x.view(-1, M))
+        h = ops.expert_gemm_w4a8_glu(xq[0].view(E, -1, M), xq[1], cgu, sgu, H, M, x.dtype, act=self.fused_activation()) if xq is not None else None
+        hq = ops.quantize_rows_a8(h.view(-1, H)) if h is not None else None
+        y = ops.expert_gemm_w4a8(hq[0].view(E, -1, H), hq[1], c3, s3, None, M, H, x.dtype) if hq is not None else None
+        if y is None:   # the ladder asked the library's own coverage queries: a refusal here is a bug, never a quiet forward elsewhere
+            from .. import _lib
+            raise _lib.TutelAmdError("the W4A8 expert GEMMs refused a shape their own queries admit: " +
+                                     _lib.lib().tutel_amd_last_error().decode("utf-8", "replace"))
+        return y
+
+    def _forward_if_w4a8(self, x, ctx):
+        """forward()'s W4A8 step, in front of the W4A16 one: the output, or None where the switch is off or a check refuses -- the
+        reason is kept"""
+        if not self.w4a8:
+            return None
+        why = self.w4a8_refusal(x, ctx)
+        if why is None and not (x.dim() == 3 and x.size(0) == self.W_fc1_full_shape[0] and x.size(2) == self.W_fc1_full_shape[1]):
+            why = "the input is not [E_loc, R, M]"
+        try:
+            setattr(ctx, "_w4a8_ran", True if why is None else why)
+        except AttributeError:
+            pass
+        return self.forward_fused_w4a8(x.contiguous()) if why is None else None
+
     def invalidate_prepacked(self):
         self._kmajor.invalidate()
 
@@ -364,7 +408,9 @@ class LlamaFFNNetwork(torch.nn.Module):
             return y
         if self.fp8_frozen:   # nothing below can run: every other forward reads the 16-bit weights
             raise RuntimeError(fp8_resident.REFUSED + (self.w8_refusal(x, ctx) or "the input is not [E_loc, R, M]"))
-        y = self._forward_if_w4(x, ctx)
+        y = self._forward_if_w4a8(x, ctx)
+        if y is None:
+            y = self._forward_if_w4(x, ctx)
         if y is not None:
             return y
         if self.fp4_frozen:

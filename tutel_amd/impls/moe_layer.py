@@ -406,6 +406,8 @@ class MOELayer(torch.nn.Module):
         setattr(self, fmt.engine.ran, True)
         if fmt is packed_w8.FP8 and getattr(self.experts, "fp8_activations", False):
             self._fp8_activations_ran = "the packed dropless forward has no W8A8 GEMM"   # it keeps W8A16
+        if fmt is packed_w8.FP4 and getattr(self.experts, "w4a8", False):
+            self._w4a8_ran = "the packed dropless forward has no W4A8 GEMM"   # it keeps W4A16
         self.megablocks_size = megablocks_size
         return y, l_aux
 
@@ -485,7 +487,7 @@ class MOELayer(torch.nn.Module):
     def forward(self, input, gate_index=0, capacity_factor=None, top_k=None, a2a_ffn_overlap_degree=None,
                 reserve_dims=1, inequivalent_tokens=False, adaptive_r=None, megablocks_size=0):
         self._dropless_packed_ran = None   # GraphedForward(dropless_packed=True) asks whether this forward took the packed layout
-        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_activations_ran, _fp8_weights_ran, _fp4_weights_ran: True, or why this forward's experts did not take the engine
+        for engine in _ffn.ENGINES:        # _native_fp32_ran, _fp8_activations_ran, _fp8_weights_ran, _fp4_weights_ran, _w4a8_ran: True, or why this forward's experts did not take the engine
             setattr(self, engine.ran, None)
         if self.skip_moe:
             out = input
@@ -531,6 +533,8 @@ class MOELayer(torch.nn.Module):
             self._fp8_activations_ran = self.experts.w8a8_refusal(x, self)
         if isinstance(self.experts, LlamaFFNNetwork) and self.experts.fp4_weights:
             self._fp4_weights_ran = self.experts.w4_refusal(x, self)
+        if isinstance(self.experts, LlamaFFNNetwork) and self.experts.w4a8:
+            self._w4a8_ran = self.experts.w4a8_refusal(x, self)
         if getattr(self.experts, "fp8_frozen", False):
             # FP8-resident experts: what the ladder knows before routing decides here, in front of every launch -- no path below
             # may reach for 16-bit weights that are gone.  (Walked with megablocks_size 0: the packed FP8 forward takes any; the

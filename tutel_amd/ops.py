@@ -666,6 +666,40 @@ def expert_gemm_w4_glu(a, codes, scales, H, K, act="silu", slot_map=None, R=None
     return _ws_padded("tutel_amd_expert_gemm_w4_glu", a, E_loc, weights, None, H, K, act, slot_map, R, out, row_counts, glu=True)
 
 
+def gemm_w4a8_supported(dtype, N, K):
+    """shapes the W4A8 grouped GEMM (tutel_amd_expert_gemm_w4a8) takes: bf16 / fp16 outputs, K % 64 == 0, N % 32 == 0 -- the library's
+    own answer"""
+    return _ws_supported("tutel_amd_expert_gemm_w4a8", dtype, N, K)
+
+
+def gemm_w4a8_glu_supported(dtype, H, K):
+    """the same for the gate / up GEMM (tutel_amd_expert_gemm_w4a8_glu): K % 64 == 0, H % 16 == 0"""
+    return _ws_supported("tutel_amd_expert_gemm_w4a8_glu", dtype, H, K)
+
+
+def expert_gemm_w4a8(aq, a_scale, codes, scales, bias, N, K, dtype, act="none", slot_map=None, R=None, out=None, row_counts=None):
+    """W4A8: D[e,r,n] = act(acc * a_scale[row] + bias[e,n]) rounded once to `dtype`, acc the fp32 accumulator of the block-scaled
+    matrix instruction over the MXFP4 weight (its e2m1 code under its block's scale byte) and the e4m3 code of the row (the contract of
+    include/tutel_amd.h).
+
+    aq, a_scale, slot_map: expert_gemm_w8a8's -- quantize_rows_a8's outputs, [E_loc, R, K] with a_scale [E_loc * R] or the quantised
+    token array [T, K] with a_scale [T] that fc1 gathers.  codes, scales, bias: expert_gemm_w4's.  Returns None when the library answers
+    ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, codes, scales, bias, out, slot_map, row_counts)
+    E_loc, weights = _w4_image(codes, scales)
+    return _a8_padded("tutel_amd_expert_gemm_w4a8", aq, a_scale, E_loc, weights, bias, N, K, dtype, act, slot_map, R, out, row_counts)
+
+
+def expert_gemm_w4a8_glu(aq, a_scale, codes, scales, H, K, dtype, act="silu", slot_map=None, R=None, out=None, row_counts=None):
+    """W4A8 gate and up products of a SwiGLU expert in ONE launch: expert_gemm_w4_glu over quantised rows, D[e,r,n] =
+    round(float(round(act(gacc * a_scale[row]))) * (uacc * a_scale[row])) -> [E_loc, R, H].  aq, a_scale, slot_map as expert_gemm_w4a8's;
+    codes, scales: expert_gemm_w4_glu's.  Returns None when the library answers ENOTSUP."""
+    _dev(aq, a_scale, codes, scales, out, slot_map, row_counts)
+    E_loc, weights = _w4_image(codes, scales)
+    return _a8_padded("tutel_amd_expert_gemm_w4a8_glu", aq, a_scale, E_loc, weights, None, H, K, dtype, act, slot_map, R, out, row_counts,
+                      glu=True)
+
+
 INT32_MAX = 2 ** 31 - 1
 
 
