@@ -374,6 +374,12 @@ int tutel_amd_expert_gemm_w8a8_glu(const void *Aq, const float *a_scale, int64_t
  * and Xq 8-byte aligned.  Anything else returns TUTEL_AMD_ENOTSUP with nothing enqueued; rows == 0 is a successful no-op. */
 int tutel_amd_quantize_rows_a8_supported(int dtype, int K);
 int tutel_amd_quantize_rows_a8(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale, tutel_stream_t stream);
+/* The same with the row count on the DEVICE: the grid is sized by the host bound `rows`, and a wave whose row is >= *rows_dev returns
+ * without reading or writing anything -- for a packed [rows_bound, K] array whose rows past offsets[E] were never written (the packed
+ * dropless forward passes offsets + E).  Rows below min(rows, *rows_dev): the bits of tutel_amd_quantize_rows_a8 (one kernel body).  No
+ * host read: capturable.  rows_dev: a 4-byte aligned device pointer; the other arguments, conditions and refusals are those above. */
+int tutel_amd_quantize_rows_a8_bounded(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale,
+                                       const int32_t *rows_dev, tutel_stream_t stream);
 
 /* W4A16 (csrc/expert_gemm_w4.hip): the grouped GEMM of bf16 / fp16 experts whose weights are stored as OCP MXFP4 -- e2m1 codes, two
  * per byte, with one e8m0 scale byte per block of 32 values along K.  Activations, bias and output stay in `dtype` (TUTEL_BF16 or
@@ -464,8 +470,8 @@ int tutel_amd_expert_gemm_w4_glu(const void *A, int64_t a_stride_e, int64_t a_st
  * N % 32 == 0; lda and a_stride_e % 16 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K / 2,
  * s_stride_e % 4 == 0 and >= N * ceil(K / 128) * 4; any R >= 1 (tuned for R <= 128; more rows stream the weights once per 128),
  * E_loc * R, the tile count and 16 K below 2^31.  Ragged last tiles clamp their loads and mask their stores: nothing is read or written
- * outside the operands.  NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange layouts, peer stores, the packed dropless
- * layout.  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  Aq, Wq
+ * outside the operands.  NOT covered: row_counts (megablocks), the [W, E_loc, C, *] exchange layouts, peer stores (the packed dropless
+ * layout: tutel_amd_expert_gemm_w4a8_packed below).  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  Aq, Wq
  * and zero_row 16-byte aligned, D and bias 8-byte aligned, Ws and a_scale 4-byte aligned.  Every check precedes the first HIP call. */
 int tutel_amd_expert_gemm_w4a8_supported(int dtype, int N, int K);
 int tutel_amd_expert_gemm_w4a8(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
@@ -521,6 +527,36 @@ int tutel_amd_expert_gemm_w4_glu_packed(const void *A, int lda, const int32_t *a
                                         int64_t w_stride_e, const void *Ws_gu, int64_t s_stride_e, void *D, int ldd, int E,
                                         int rows_bound, int H, int K, int dtype, int act, const int32_t *offsets, const int32_t *tiles,
                                         const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+
+/* The two W4A8 GEMMs above over the PACKED dropless layout (csrc/expert_gemm_w4a8.hip).  Arguments: those of
+ * tutel_amd_expert_gemm_w4_packed / _w4_glu_packed with Aq (e4m3 bytes, lda in BYTES) and a_scale in place of A.
+ *     Without a_rows, packed row r is Aq + r * lda with scale a_scale[r].  With a_rows (the packed slot map), row r is token
+ *     a_rows[r] % T of the quantised token array Aq [T, K] with scale a_scale[a_rows[r] % T]; a slot of -1 reads zero_row (>= K zero
+ *     bytes) with scale 1.0 -- what the padded kernels do with slot_map.
+ *     Every row in [0, offsets[E]) is written, BIT FOR BIT what tutel_amd_expert_gemm_w4a8 / _w4a8_glu write for the same quantised row,
+ *     scale and expert, whichever window form computed it (one tile function: one fp32 accumulator per output, K-tiles ascending, the same
+ *     operand preparation, the same epilogue).  Rows at and past offsets[E] are neither read nor written.
+ * Window forms, TUTEL_AMD_W4A8_PACKED_TILE=wide | halves, read at every call (anything else: the default, WIDE -- DESIGN 4.4 holds
+ * the measurement).  HALVES: the padded kernels' 128-row tile over the two halves of a 256-row table tile, in the W8A16 packed kernels'
+ * order; two workgroups per CU.  WIDE: a work item is (table tile, 128 image channels) and covers all live rows of the window
+ * [tiles[2t+1], +256) clipped by offsets[e + 1]: each K-tile of the weights is fetched and prepared once and feeds up to eight matrix
+ * instructions; 2 x 32 KB of LDS.  Rows of a window past the expert's end clamp their loads to the last live row and mask their
+ * stores; wholly dead 32-row groups issue no matrix instruction.
+ * Covered: the padded W4A8 entry points' conditions without the bucket strides -- bf16 / fp16 outputs, K % 64 == 0, N % 32 == 0
+ * (H % 16 == 0), lda % 16 == 0, ldd and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= one code image, s_stride_e % 4 == 0 and >= one
+ * scale image, act one of TUTEL_ACT_*, 16 K and the halves form's work item count below 2^31.  Anything else returns TUTEL_AMD_ENOTSUP
+ * with its reason and nothing enqueued; E == 0, rows_bound == 0 or tiles_bound == 0 is a successful no-op.  Aq, Wq and zero_row 16-byte
+ * aligned, D and bias 8-byte aligned, Ws and a_scale 4-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w4a8_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T, const void *zero_row,
+                                      const void *Wq, int64_t w_stride_e, const void *Ws, int64_t s_stride_e, const void *bias,
+                                      int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act,
+                                      const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles, int tiles_bound,
+                                      tutel_stream_t stream);
+int tutel_amd_expert_gemm_w4a8_glu_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T,
+                                          const void *zero_row, const void *Wq_gu, int64_t w_stride_e, const void *Ws_gu,
+                                          int64_t s_stride_e, void *D, int ldd, int E, int rows_bound, int H, int K, int dtype, int act,
+                                          const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles, int tiles_bound,
+                                          tutel_stream_t stream);
 
 /* The two W8A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w8.hip): the experts'
  * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value

@@ -50,11 +50,14 @@
 // Built with the default flags: the only fp32 arithmetic is the epilogue's __fmul_rn / __fadd_rn, whose packed forms round each element
 // alike (expert_gemm_w8a8.hip is built the same way).
 //
+// The packed dropless layout (tutel_amd_expert_gemm_w4a8_packed / _glu_packed): the same tile over row windows read from the device
+// tables, as two 128-row halves or as one WIDE 256-row window per table tile (w4a8_tile's MG; the kernels stand behind the padded one).
+//
 // SwiGLU experts (tutel_amd_expert_gemm_w4a8_glu): D = round_T( float(round_T(act(gacc sa))) * (uacc sa) ) over the 16-channel-interleaved
 // gate / up image, register against register as in the other GLU kernels.
 #include "w4_image.h"
 
-#define A8_STAGE (WS_BM * WS_BK)   // one stage of the fp8 token panel: 128 rows x 64 bytes
+#define A8_STAGE (WS_BM * WS_BK)   // one stage of the 128-row fp8 token panel: 128 rows x 64 bytes (the wide window's: two of them)
 
 struct W4A8Args : W4Args {   // A: e4m3 bytes, a_stride_e and lda in bytes
   const float *a_scale;
@@ -83,9 +86,19 @@ __device__ __forceinline__ void w4a8_swap(uint32_t &x, uint32_t &y) {
 // the panel's swizzle (file header)
 __device__ __forceinline__ int w4a8_f(int r) { return ((r >> 1) & 3) ^ ((r >> 3) & 1); }
 
-// One (expert, 128 rows, 128 image channels) work item: expert e, rows [m0, min(m0 + 128, rend)), channel tile tn; slot0: the slot of
-// the bucket's row 0.  GLU: p.N = 2 H image channels, and only the epilogue differs
-template <typename T, int ACT, bool GLU>
+// One (expert, 32 MG rows, 128 image channels) work item: expert e, rows [m0, min(m0 + 32 MG, rend)), channel tile tn; slot0: the slot
+// -- and the index of the row scale -- of the layout's row 0 (e * R in the bucket, 0 on the packed layout, whose rows are absolute).
+// GLU: p.N = 2 H image channels, and only the epilogue differs.
+//   MG = 4: the 128-row tile of the padded kernels and of the packed kernels' halves form.
+//   MG = 8: the WIDE window of the packed layout, a whole 256-row table tile.  A ring slot is fetched and prepared (two swaps, one
+//           shift) ONCE per K-tile and feeds up to eight matrix instructions.  The panel is two stages of 256 rows x 64 bytes (32 KB);
+//           thread `tid` moves chunk tid & 3 of rows 64 i + (tid >> 2), i < 4 (rows 64 apart share f: the swizzle is unchanged).  Live-
+//           group counts 1 .. 4 move two token passes as the 128-row tile does (rows 128 .. 255 of the panel are neither written nor
+//           read).  Counts above four ask for the fragments two groups at a time -- 16 registers, not 64: with 128
+//           accumulators the tile then fits 256 registers and two workgroups per CU -- in front of their two matrix instructions;
+//           a batch's reads are issued behind the previous batch's instructions and land under them.
+// Whatever MG and the count: one fp32 accumulator per output, K-tiles ascending, the same operand, the same epilogue -- the same bits.
+template <typename T, int ACT, bool GLU, int MG>
 __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem, const int e, const int tn, const int m0, const int rend,
                                           const long long slot0) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -94,21 +107,26 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
   const int n0 = tn * WS_BN;
   const int nk = p.K / WS_BK;
   const int NT = p.N >> 5;
-  const int nmi = min(4, (rend - m0 + 31) >> 5);  // live 32-row groups of this tile
+  constexpr int NP = MG / 2;                      // token passes of 64 rows
+  constexpr int STAGE = MG * 32 * WS_BK;          // one stage of the token panel
+  const int nmi = min(MG, (rend - m0 + 31) >> 5); // live 32-row groups of this tile
+  const bool wide = MG > 4 && nmi > 4;            // (block-uniform) the token passes 2 .. NP - 1 are live
 
-  // ---- token rows: thread `tid` moves chunk (tid & 3) of rows 64 i + (tid >> 2), i < 2, of every K-tile; rows past the window's end
+  // ---- token rows: thread `tid` moves chunk (tid & 3) of rows 64 i + (tid >> 2), i < NP, of every K-tile; rows past the window's end
   // read the last row again (their outputs are masked) ------------------------------------------------------------------------------------
-  const unsigned char *rowp[2];
+  const unsigned char *rowp[NP];
   const int tr = tid >> 2, tc = tid & 3;
   const int ldst = tr * WS_BK + ((tc ^ w4a8_f(tr)) << 4);            // + i * 64 rows (rows tr and 64 + tr share f)
   {
-    int slot[2] = {0, 0};
+    int slot[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) slot[i] = 0;
     if (p.slot_map != nullptr) {  // the slots first, so that their loads are in flight together
 #pragma unroll
-      for (int i = 0; i < 2; ++i) slot[i] = p.slot_map[slot0 + min(m0 + 64 * i + tr, rend - 1)];
+      for (int i = 0; i < NP; ++i) slot[i] = p.slot_map[slot0 + min(m0 + 64 * i + tr, rend - 1)];
     }
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int gr = min(m0 + 64 * i + tr, rend - 1);
       const unsigned char *row;
       if (p.slot_map != nullptr) row = slot[i] < 0 ? p.zero_row : p.A + (long long)(slot[i] % p.T) * p.lda;
@@ -116,9 +134,9 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
       rowp[i] = row + tc * 16;
     }
   }
-  auto tstore = [&](unsigned char *stage, const u32x4 (&t)[2]) __attribute__((always_inline)) {
+  auto tstore = [&](unsigned char *stage, const u32x4 (&t)[NP], auto np) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4 *>(stage + i * (64 * WS_BK) + ldst) = t[i];
+    for (int i = 0; i < decltype(np)::value; ++i) *reinterpret_cast<u32x4 *>(stage + i * (64 * WS_BK) + ldst) = t[i];
   };
 
   // ---- weights: the wave's 32-channel group, clamped to the last one (a clamped wave computes and stores nothing new) ---------------------
@@ -129,19 +147,22 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
 #pragma unroll
   for (int d = 0; d < WS_DEPTH; ++d) ring.load(d, d);
 
-  f32x16 acc[4];
+  f32x16 acc[MG];
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
+  for (int mi = 0; mi < MG; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
 
   // token tile 0 goes to LDS here, tile 1 waits in treg[1] (treg[j]: a tile of parity j)
-  u32x4 treg[2][2];
+  u32x4 treg[2][NP];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) treg[0][i] = *reinterpret_cast<const u32x4 *>(rowp[i]);
+  for (int i = 0; i < NP; ++i)
+    if (i < 2 || wide) treg[0][i] = *reinterpret_cast<const u32x4 *>(rowp[i]);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) treg[1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + (long long)min(1, nk - 1) * WS_BK);
-  tstore(smem, treg[0]);
+  for (int i = 0; i < NP; ++i)
+    if (i < 2 || wide) treg[1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + (long long)min(1, nk - 1) * WS_BK);
+  if (wide) tstore(smem, treg[0], std::integral_constant<int, NP>{});
+  else tstore(smem, treg[0], std::integral_constant<int, 2>{});
   __syncthreads();
 
   // the lane's fragment: chunks kg (k = 16 kg .. + 15) and kg + 2 (k = 32 + 16 kg .. + 15) of row 32 mi + l31 -- the fp8 operand's K
@@ -156,6 +177,7 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
 
   auto kloop = [&](auto nmi_c) __attribute__((always_inline)) {
     constexpr int NMI = decltype(nmi_c)::value;
+    constexpr auto np = std::integral_constant<int, (NMI <= 4 ? 2 : NP)>{};   // token passes per K-tile
     for (int kt0 = 0; kt0 < nk; kt0 += WS_DEPTH) {
 #pragma unroll
       for (int d = 0; d < WS_DEPTH; ++d) {
@@ -164,7 +186,7 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
         // token tile kt + 2 (behind the last tile: that tile again -- it is stored into the free stage and never read)
         const long long tnext = (long long)min(kt + 2, nk - 1) * WS_BK;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) treg[d & 1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + tnext);
+        for (int i = 0; i < np(); ++i) treg[d & 1][i] = *reinterpret_cast<const u32x4 *>(rowp[i] + tnext);
         // the K-tile's operand: block kg of the tile in ascending k, its scale byte in byte 0; then the slot's refill
         uint32_t q0 = ring.w[d][0], q1 = ring.w[d][1], q2 = ring.w[d][2], q3 = ring.w[d][3];
         w4a8_swap(q0, q2);
@@ -172,24 +194,33 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
         const i32x8 wa = {(int)q0, (int)q2, (int)q1, (int)q3, 0, 0, 0, 0};
         const uint32_t sc = ring.s[d] >> ssh[d & 1];
         ring.load(d, kt + WS_DEPTH);
-        // every live group's fragment is asked for in front of the first matrix instruction
-        const int so = (kt & 1) * A8_STAGE;
-        u32x4 tb[NMI][2];
+        // a batch of live groups' fragments is asked for in front of the batch's first matrix instruction: every group of the
+        // 128-row loops, two groups at a time above four (the wide window's registers, w4a8_tile's header)
+        const int so = (kt & 1) * STAGE;
+        constexpr int NB = NMI <= 4 ? NMI : 2;
 #pragma unroll
-        for (int mi = 0; mi < NMI; ++mi) {
-          tb[mi][0] = *reinterpret_cast<const u32x4 *>(frag0 + so + mi * (32 * WS_BK));
-          tb[mi][1] = *reinterpret_cast<const u32x4 *>(frag1 + so + mi * (32 * WS_BK));
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        for (int m0g = 0; m0g < NMI; m0g += NB) {
+          u32x4 tb[NB][2];
 #pragma unroll
-        for (int mi = 0; mi < NMI; ++mi) {
-          const i32x8 b = {(int)tb[mi][0][0], (int)tb[mi][0][1], (int)tb[mi][0][2], (int)tb[mi][0][3],
-                           (int)tb[mi][1][0], (int)tb[mi][1][1], (int)tb[mi][1][2], (int)tb[mi][1][3]};
-          acc[mi] = w4a8_mma(wa, b, acc[mi], sc, one);
+          for (int mi = 0; mi < NB; ++mi) {
+            if (m0g + mi < NMI) {
+              tb[mi][0] = *reinterpret_cast<const u32x4 *>(frag0 + so + (m0g + mi) * (32 * WS_BK));
+              tb[mi][1] = *reinterpret_cast<const u32x4 *>(frag1 + so + (m0g + mi) * (32 * WS_BK));
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int mi = 0; mi < NB; ++mi) {
+            if (m0g + mi < NMI) {
+              const i32x8 b = {(int)tb[mi][0][0], (int)tb[mi][0][1], (int)tb[mi][0][2], (int)tb[mi][0][3],
+                               (int)tb[mi][1][0], (int)tb[mi][1][1], (int)tb[mi][1][2], (int)tb[mi][1][3]};
+              acc[m0g + mi] = w4a8_mma(wa, b, acc[m0g + mi], sc, one);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
         // the other stage is free since the last barrier (behind the last tile nobody reads what is stored)
-        tstore(smem + ((kt + 1) & 1) * A8_STAGE, treg[(d + 1) & 1]);
+        tstore(smem + ((kt + 1) & 1) * STAGE, treg[(d + 1) & 1], np);
         __syncthreads();
       }
     }
@@ -198,23 +229,37 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
     case 1: kloop(std::integral_constant<int, 1>{}); break;
     case 2: kloop(std::integral_constant<int, 2>{}); break;
     case 3: kloop(std::integral_constant<int, 3>{}); break;
-    default: kloop(std::integral_constant<int, 4>{}); break;
+    default:
+      if constexpr (MG == 4) {
+        kloop(std::integral_constant<int, 4>{});
+      } else {
+        switch (nmi) {
+          case 4: kloop(std::integral_constant<int, 4>{}); break;
+          case 5: kloop(std::integral_constant<int, 5>{}); break;
+          case 6: kloop(std::integral_constant<int, 6>{}); break;
+          case 7: kloop(std::integral_constant<int, 7>{}); break;
+          default: kloop(std::integral_constant<int, 8>{}); break;
+        }
+      }
+      break;
   }
 
   // ---- epilogue: lane = row m0 + 32 mi + l31; register 4 rg + r of accumulator mi = channel 32 nt + 8 rg + 4 kg + r ---------------------
   if (!wave_live) return;
   // the lane's row scales and bias, all fetched before the first is used
-  float sa[4];
+  float sa[MG];
   {
-    int slot[4] = {0, 0, 0, 0};
+    int slot[MG];
+#pragma unroll
+    for (int mi = 0; mi < MG; ++mi) slot[mi] = 0;
     if (p.slot_map != nullptr) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) slot[mi] = p.slot_map[slot0 + min(m0 + mi * 32 + l31, rend - 1)];
+      for (int mi = 0; mi < MG; ++mi) slot[mi] = p.slot_map[slot0 + min(m0 + mi * 32 + l31, rend - 1)];
     }
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+    for (int mi = 0; mi < MG; ++mi) {
       if (p.slot_map != nullptr) sa[mi] = slot[mi] < 0 ? 1.0f : p.a_scale[slot[mi] % p.T];
-      else sa[mi] = p.a_scale[(long long)e * p.R + min(m0 + mi * 32 + l31, rend - 1)];
+      else sa[mi] = p.a_scale[slot0 + min(m0 + mi * 32 + l31, rend - 1)];
     }
   }
   uint2 bi[4];
@@ -233,7 +278,7 @@ __device__ __forceinline__ void w4a8_tile(const W4A8Args &p, unsigned char *smem
     *reinterpret_cast<uint2 *>(dst) = ov;
   };
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
+  for (int mi = 0; mi < MG; ++mi) {
     const int m = m0 + mi * 32 + l31;
     if (m >= rend) continue;
     uint16_t *drow = p.D + (long long)e * p.d_stride_e + (long long)m * p.ldd + nt * (GLU ? 16 : 32) + kg * 4;
@@ -283,8 +328,33 @@ __global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4a8_kernel(const W
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * A8_STAGE];
   const int b = xcd_work_item((int)gridDim.x);
   const int tn = b % p.ntn, tm = (b / p.ntn) % p.ntm, e = b / (p.ntn * p.ntm);
-  w4a8_tile<T, ACT, GLU>(p, smem, e, tn, tm * WS_BM, p.R, (long long)e * p.R);
+  w4a8_tile<T, ACT, GLU, 4>(p, smem, e, tn, tm * WS_BM, p.R, (long long)e * p.R);
 }
+
+// ---- the packed dropless layout: gemm_wstream.h's work-item order (ws_packed_window), always cut from the live pairs, in two forms -----
+// WIDE: one work item per (table tile, channel tile) owns all live rows of the 256-row window, so an expert above 128 rows streams its
+// weights once and prepares each K-tile's operand once.  No converts and 128 accumulators: the tile is meant to fit 256 registers, two
+// workgroups per CU, 2 x 32 KB of LDS each (profiles/expert_gemm_w4a8_packed_kernel_resources.txt).
+// HALVES: the 128-row tile over the two halves of a table tile, the halves that are not live at the end of every XCD's queue.
+// Both write the padded kernels' bits (w4a8_tile); TUTEL_AMD_W4A8_PACKED_TILE below picks one at every call.
+template <typename T, int ACT, bool GLU>
+__global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4a8_packed_kernel(const W4A8Args p, const WsTables t) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * A8_STAGE];   // two stages of 256 rows
+  WsWindow w;
+  if (!ws_packed_window<1>(p.ntn, t.offsets, t.tiles, t.ntiles, t.tiles_bound, w)) return;
+  w4a8_tile<T, ACT, GLU, 8>(p, smem, w.e, w.tn, w.m0, w.rend, 0);
+}
+
+template <typename T, int ACT, bool GLU>
+__global__ __launch_bounds__(WS_THREADS, 2) void expert_gemm_w4a8_packed_halves_kernel(const W4A8Args p, const WsTables t) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * A8_STAGE];
+  WsWindow w;
+  if (!ws_packed_window<2>(p.ntn, t.offsets, t.tiles, t.ntiles, t.tiles_bound, w)) return;
+  w4a8_tile<T, ACT, GLU, 4>(p, smem, w.e, w.tn, w.m0, w.rend, 0);
+}
+
+// TUTEL_AMD_W4A8_PACKED_TILE below
+#define W4A8_PACKED_DEFAULT_HALVES 0
 
 // ---- host: gemm_wstream.h's ws_run over the W4 image (w4_image.h's checks) and the quantised rows' own operands -------------------------
 struct W4A8Fmt {
@@ -297,13 +367,25 @@ struct W4A8Fmt {
     void fill(W4A8Args &a) const { W4Weights::fill(a); a.a_scale = a_scale; }
   };
   static constexpr WsText TEXT = {
-      {"rows of Aq must stay 16-byte aligned (lda, a_stride_e % 16), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4", ""},
-      {"E_loc * R, the tile count and one channel group's run of 16 K bytes must stay below 2^31", ""},
+      {"rows of Aq must stay 16-byte aligned (lda, a_stride_e % 16), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4",
+       "rows of Aq must stay 16-byte aligned (lda % 16), rows of D and bias 8-byte aligned (% 4), w_stride_e % 16, s_stride_e % 4"},
+      {"E_loc * R, the tile count and one channel group's run of 16 K bytes must stay below 2^31",
+       "the work item count tiles_bound * 2 * ceil(channels / 128) and one channel group's run of 16 K bytes must stay below 2^31"},
       "%s: Aq and Wq must be 16-byte aligned, D and bias 8-byte aligned, Ws and a_scale 4-byte aligned"};
-  static bool packed_halves() { return false; }   // (no packed form)
+  // The form of the packed kernels, read at EVERY call: TUTEL_AMD_W4A8_PACKED_TILE=halves | wide; anything else is the default, which
+  // tools/packed_w4a8_bench.py's A/B decided: WIDE -- 72.5 against 96.0 us at 64 x 160 rows, 59.7 against 59.1 us at 64 x 128
+  // rows (inside the halves arm's spread of 58.1 - 64.0 us); halves stays selectable
+  static bool packed_halves() {
+    const char *s = getenv("TUTEL_AMD_W4A8_PACKED_TILE");
+    if (s != nullptr && strcmp(s, "halves") == 0) return true;
+    if (s != nullptr && strcmp(s, "wide") == 0) return false;
+    return W4A8_PACKED_DEFAULT_HALVES != 0;
+  }
   template <typename T, int ACT, bool GLU>
-  static void launch(const W4A8Args &a, const WsTables *, bool, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL((expert_gemm_w4a8_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a);
+  static void launch(const W4A8Args &a, const WsTables *pk, bool halves, unsigned grid, hipStream_t st) {
+    if (pk == nullptr) hipLaunchKernelGGL((expert_gemm_w4a8_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a);
+    else if (halves) hipLaunchKernelGGL((expert_gemm_w4a8_packed_halves_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a, *pk);
+    else hipLaunchKernelGGL((expert_gemm_w4a8_packed_kernel<T, ACT, GLU>), dim3(grid), dim3(WS_THREADS), 0, st, a, *pk);
   }
 };
 
@@ -334,4 +416,28 @@ extern "C" int tutel_amd_expert_gemm_w4a8_glu(const void *Aq, const float *a_sca
   const WsBucket bk = {a_stride_e, a_stride_w, a_rows_per_w, d_stride_e, d_stride_w, d_rows_per_w, row_counts};
   return ws_run<W4A8Fmt, true>({"tutel_amd_expert_gemm_w4a8_glu", W4_SMALL_GU}, {{Wq_gu, w_stride_e, Ws_gu, s_stride_e}, a_scale, lda, a_stride_e},
                                &bk, nullptr, Aq, lda, slot_map, T, zero_row, nullptr, 0, D, ldd, E_loc, R, H, K, dtype, act, stream);
+}
+
+// The two GEMMs above over the packed dropless layout (the contract: include/tutel_amd.h): the row ranges come from the device tables,
+// a_scale is indexed by the packed row, or by the token where a_rows gathers
+extern "C" int tutel_amd_expert_gemm_w4a8_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T,
+                                                 const void *zero_row, const void *Wq, int64_t w_stride_e, const void *Ws, int64_t s_stride_e,
+                                                 const void *bias, int64_t bias_stride_e, void *D, int ldd, int E, int rows_bound, int N, int K,
+                                                 int dtype, int act, const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles,
+                                                 int tiles_bound, tutel_stream_t stream) {
+  if (!ws_dtype_ok(dtype)) return tutel_notsup("tutel_amd_expert_gemm_w4a8_packed", W4A8_DTYPE);
+  const WsTables pk = {offsets, tiles, ntiles, tiles_bound};
+  return ws_run<W4A8Fmt, false>({"tutel_amd_expert_gemm_w4a8_packed", W4_SMALL}, {{Wq, w_stride_e, Ws, s_stride_e}, a_scale, lda, 0}, nullptr,
+                                &pk, Aq, lda, a_rows, T, zero_row, bias, bias_stride_e, D, ldd, E, rows_bound, N, K, dtype, act, stream);
+}
+
+extern "C" int tutel_amd_expert_gemm_w4a8_glu_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T,
+                                                     const void *zero_row, const void *Wq_gu, int64_t w_stride_e, const void *Ws_gu,
+                                                     int64_t s_stride_e, void *D, int ldd, int E, int rows_bound, int H, int K, int dtype,
+                                                     int act, const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles,
+                                                     int tiles_bound, tutel_stream_t stream) {
+  if (!ws_dtype_ok(dtype)) return tutel_notsup("tutel_amd_expert_gemm_w4a8_glu_packed", W4A8_DTYPE);
+  const WsTables pk = {offsets, tiles, ntiles, tiles_bound};
+  return ws_run<W4A8Fmt, true>({"tutel_amd_expert_gemm_w4a8_glu_packed", W4_SMALL_GU}, {{Wq_gu, w_stride_e, Ws_gu, s_stride_e}, a_scale, lda, 0},
+                               nullptr, &pk, Aq, lda, a_rows, T, zero_row, nullptr, 0, D, ldd, E, rows_bound, H, K, dtype, act, stream);
 }

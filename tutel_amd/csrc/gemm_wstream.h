@@ -326,6 +326,30 @@ __device__ __forceinline__ void ws_packed(const typename Fmt::Args &p, const int
   ws_tile<Fmt, T, ACT, GLU, MG, SPEC>(p, smem, e, tn, m0, rend, 0);
 }
 
+// ws_packed's mapping alone, always cut from the live pairs, for a kernel whose tile is not ws_tile (expert_gemm_w4a8.hip): NH work items
+// per pair (2: halves, 1: wide), ntn channel tiles -> false where this block has no window.  (ws_packed keeps its own copy: routed
+// through this function the W8A16 and W4A16 packed kernels compile to different code, and those kernels are measured as they are)
+struct WsWindow { int e, tn, m0, rend; };   // expert, channel tile, rows [m0, rend): the tile clips them to its form's extent
+
+template <int NH>
+__device__ __forceinline__ bool ws_packed_window(int ntn, const int32_t *off, const int32_t *tiles, const int32_t *ntiles, int tiles_bound,
+                                                 WsWindow &w) {
+  const int live = min(__builtin_amdgcn_readfirstlane(*ntiles), tiles_bound);
+  const int pairs = live * ntn;   // <= tiles_bound * ntn: the host sized the grid for it
+  const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3;
+  const int q = pairs >> 3, r = pairs & 7;
+  const int len = q + (xcd < r ? 1 : 0), start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  if (pos >= NH * len) return false;
+  const int half = pos >= len ? 1 : 0, it = start + pos - half * len;
+  const int ti = it / ntn;
+  w.tn = it % ntn;
+  if (ti >= live) return false;
+  w.e = __builtin_amdgcn_readfirstlane(tiles[2 * ti]);
+  w.m0 = __builtin_amdgcn_readfirstlane(tiles[2 * ti + 1]) + half * WS_BM;
+  w.rend = __builtin_amdgcn_readfirstlane(off[w.e + 1]);
+  return w.m0 < w.rend;
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 static bool ws_dtype_ok(int dtype) { return dtype == TUTEL_BF16 || dtype == TUTEL_F16; }
 static bool ws_shape_ok(int N, int K) { return N >= 32 && N % 32 == 0 && K >= WS_BK && K % WS_BK == 0; }

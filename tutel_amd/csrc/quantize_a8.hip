@@ -15,6 +15,10 @@
 //   codes   lane l of round j holds elements 512 j + 8 l .. + 7: eight codes, ONE 8-byte store, 512 bytes contiguous per wave.
 // K is a multiple of 64: the last round is whole lanes (lane l is live when 512 j + 8 l < K).
 // Byte model: 2 K bytes read and K + 4 bytes written per row.
+//
+// BOUNDED (tutel_amd_quantize_rows_a8_bounded): the same kernel body with the row count on the DEVICE.  The grid is sized by the host
+// bound `rows`; a wave whose row is >= *rows_dev returns before its first load -- the rows of a packed [rows_bound, K] array past
+// offsets[E] were never written and are not read as data.  One scalar load and one wave-uniform branch, no host read: capturable.
 #include "quantize_e4m3.h"
 
 #define QA_THREADS 256
@@ -26,13 +30,17 @@ struct QaArgs {
   unsigned char *Xq; int ldq;        // bytes
   float *scale;
   int rows, K;
+  const int32_t *rows_dev;           // BOUNDED: the live row count, read by every wave
 };
 
-template <typename T, int NR>
+template <typename T, int NR, bool BOUNDED>
 __global__ __launch_bounds__(QA_THREADS) void quantize_rows_a8_kernel(const QaArgs p) {
   const int lane = (int)threadIdx.x & 63;
   const int row = (int)blockIdx.x * QA_ROWS + ((int)threadIdx.x >> 6);
   if (row >= p.rows) return;   // (wave-uniform; the kernel has no barrier)
+  if constexpr (BOUNDED) {
+    if (row >= *p.rows_dev) return;   // (wave-uniform as well)
+  }
   const T *x = reinterpret_cast<const T *>(p.X) + (int64_t)row * p.ldx + lane * 8;
 
   vec16 v[NR];
@@ -73,7 +81,6 @@ __global__ __launch_bounds__(QA_THREADS) void quantize_rows_a8_kernel(const QaAr
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static const char *const QA_NAME = "tutel_amd_quantize_rows_a8";
 
 static const char *qa_shape_refusal(int dtype, int K) {
   if (dtype != TUTEL_BF16 && dtype != TUTEL_F16) return "the rows must be bf16 or fp16";
@@ -84,34 +91,46 @@ static const char *qa_shape_refusal(int dtype, int K) {
 
 extern "C" int tutel_amd_quantize_rows_a8_supported(int dtype, int K) { return qa_shape_refusal(dtype, K) == nullptr ? 1 : 0; }
 
-template <typename T> static void qa_launch(const QaArgs &a, unsigned grid, hipStream_t st) {
-  if (a.K <= 512) hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 1>), dim3(grid), dim3(QA_THREADS), 0, st, a);
-  else if (a.K <= 2048) hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 4>), dim3(grid), dim3(QA_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 16>), dim3(grid), dim3(QA_THREADS), 0, st, a);
+template <typename T, bool BOUNDED> static void qa_launch(const QaArgs &a, unsigned grid, hipStream_t st) {
+  if (a.K <= 512) hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 1, BOUNDED>), dim3(grid), dim3(QA_THREADS), 0, st, a);
+  else if (a.K <= 2048) hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 4, BOUNDED>), dim3(grid), dim3(QA_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((quantize_rows_a8_kernel<T, 16, BOUNDED>), dim3(grid), dim3(QA_THREADS), 0, st, a);
 }
 
-// Every check stands in front of the first HIP call
-extern "C" int tutel_amd_quantize_rows_a8(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale,
-                                          tutel_stream_t stream) {
-  TUTEL_REQUIRE(rows >= 0 && K >= 1, "%s: bad sizes rows=%d K=%d", QA_NAME, rows, K);
+// Both entry points.  Every check stands in front of the first HIP call
+template <bool BOUNDED>
+static int qa_run(const char *name, const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale,
+                  const int32_t *rows_dev, tutel_stream_t stream) {
+  TUTEL_REQUIRE(rows >= 0 && K >= 1, "%s: bad sizes rows=%d K=%d", name, rows, K);
   const char *why = qa_shape_refusal(dtype, K);
-  if (why != nullptr) return tutel_notsup(QA_NAME, why);
-  if (ldx < K || ldq < K) return tutel_notsup(QA_NAME, "ldx and ldq must be at least K");
-  if (ldx % 8 != 0 || ldq % 8 != 0) return tutel_notsup(QA_NAME, "rows of X must stay 16-byte aligned (ldx % 8), rows of Xq 8-byte aligned (ldq % 8)");
+  if (why != nullptr) return tutel_notsup(name, why);
+  if (ldx < K || ldq < K) return tutel_notsup(name, "ldx and ldq must be at least K");
+  if (ldx % 8 != 0 || ldq % 8 != 0) return tutel_notsup(name, "rows of X must stay 16-byte aligned (ldx % 8), rows of Xq 8-byte aligned (ldq % 8)");
   if (rows == 0) return 0;
-  TUTEL_REQUIRE(X != nullptr && Xq != nullptr && scale != nullptr, "%s: null pointer", QA_NAME);
-  if (((uintptr_t)X % 16) != 0 || ((uintptr_t)Xq % 8) != 0) return tutel_notsup(QA_NAME, "X must be 16-byte aligned, Xq 8-byte aligned");
-  TUTEL_REQUIRE(((uintptr_t)scale % 4) == 0, "%s: scale must be 4-byte aligned", QA_NAME);
+  TUTEL_REQUIRE(X != nullptr && Xq != nullptr && scale != nullptr, "%s: null pointer", name);
+  if (((uintptr_t)X % 16) != 0 || ((uintptr_t)Xq % 8) != 0) return tutel_notsup(name, "X must be 16-byte aligned, Xq 8-byte aligned");
+  TUTEL_REQUIRE(((uintptr_t)scale % 4) == 0, "%s: scale must be 4-byte aligned", name);
+  if (BOUNDED) TUTEL_REQUIRE(rows_dev != nullptr && ((uintptr_t)rows_dev % 4) == 0, "%s: rows_dev must be a 4-byte aligned pointer", name);
 
   QaArgs a;
   a.X = (const unsigned char *)X; a.ldx = ldx;
   a.Xq = (unsigned char *)Xq; a.ldq = ldq;
   a.scale = scale;
-  a.rows = rows; a.K = K;
+  a.rows = rows; a.K = K; a.rows_dev = rows_dev;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)((rows + QA_ROWS - 1) / QA_ROWS);
-  if (dtype == TUTEL_BF16) qa_launch<bf16_t>(a, grid, st);
-  else qa_launch<f16_t>(a, grid, st);
-  TUTEL_CHECK_LAUNCH(QA_NAME);
+  if (dtype == TUTEL_BF16) qa_launch<bf16_t, BOUNDED>(a, grid, st);
+  else qa_launch<f16_t, BOUNDED>(a, grid, st);
+  TUTEL_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int tutel_amd_quantize_rows_a8(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale,
+                                          tutel_stream_t stream) {
+  return qa_run<false>("tutel_amd_quantize_rows_a8", X, dtype, ldx, rows, K, Xq, ldq, scale, nullptr, stream);
+}
+
+extern "C" int tutel_amd_quantize_rows_a8_bounded(const void *X, int dtype, int ldx, int rows, int K, void *Xq, int ldq, float *scale,
+                                                  const int32_t *rows_dev, tutel_stream_t stream) {
+  return qa_run<true>("tutel_amd_quantize_rows_a8_bounded", X, dtype, ldx, rows, K, Xq, ldq, scale, rows_dev, stream);
 }

@@ -111,6 +111,9 @@ class MOELayer(torch.nn.Module):
         self.dropless_packed_fp8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_FP8", "0")) != 0
         # opt-in: the same forward for experts with fp4_weights (the W4A16 GEMMs over the packed tables); with both on FP8 runs
         self.dropless_packed_fp4 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_FP4", "0")) != 0
+        # opt-in, on top of dropless_packed_fp4 and experts.w4a8: the rows quantised to e4m3 and the W4A8 GEMMs over the packed tables
+        # (eight launches, capturable).  Where the W4A8 ladder refuses, the reason is in _w4a8_ran and the packed FP4 forward runs
+        self.dropless_packed_w4a8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_W4A8", "0")) != 0
         # gradient accumulation over micro-batches: the packed training step adds the expert gradients into p.main_grad (fp32) inside
         # the gradient kernels and returns no autograd gradient for them (impls/packed_train.py).  A forward that cannot do so raises
         self.dropless_packed_main_grad = int(os.environ.get("TUTEL_AMD_PACKED_MAIN_GRAD", "0")) != 0
@@ -372,9 +375,11 @@ class MOELayer(torch.nn.Module):
         if not (getattr(self, fmt.switch) and cf <= 0 and self.dropless_packed and getattr(self.experts, fmt.weights, False)
                 and isinstance(self.experts, (FusedExpertsNetwork, LlamaFFNNetwork))):
             return None
+        if fmt is packed_w8.W4A8 and not self.dropless_packed_fp4:   # (it sits on top of the FP4 format's switch)
+            return None
         T, E = logits.shape[0], logits.shape[-1]
         k = min(top_k, E)
-        frozen = getattr(self.experts, fmt.frozen, False)   # no 16-bit packed forward to fall back to: a refusal raises
+        frozen = bool(fmt.frozen) and getattr(self.experts, fmt.frozen, False)   # no 16-bit packed forward to fall back to: a refusal raises
         plan, why = None, packed_w8.ROUTING_REASON
         if x.is_cuda and logits.dim() == 2 and self._plan("before_routing", x, logits, *plan_args, packed_fp8=True) == "native_moe":
             plan, why = ep_native.packed_cover(self, T, E, k, x.shape[1], x.dtype, ep_native.dropless_row_limit(T, E, k, cf), alignment)
@@ -406,7 +411,7 @@ class MOELayer(torch.nn.Module):
         setattr(self, fmt.engine.ran, True)
         if fmt is packed_w8.FP8 and getattr(self.experts, "fp8_activations", False):
             self._fp8_activations_ran = "the packed dropless forward has no W8A8 GEMM"   # it keeps W8A16
-        if fmt is packed_w8.FP4 and getattr(self.experts, "w4a8", False):
+        if fmt is packed_w8.FP4 and getattr(self.experts, "w4a8", False) and not self.dropless_packed_w4a8:
             self._w4a8_ran = "the packed dropless forward has no W4A8 GEMM"   # it keeps W4A16
         self.megablocks_size = megablocks_size
         return y, l_aux

@@ -21,6 +21,12 @@ MXFP4 weights are the same forward under another Format (below): the W4A16 GEMMs
 tutel_amd_expert_gemm_w4_packed / _glu_packed), the W4 ladders, the W4 images, no scale multiply
 in the formulas above; the bits of the padded dropless FP4 forward.  Opt-in: layer.dropless_packed_fp4 (TUTEL_AMD_DROPLESS_PACKED_FP4=1)
 on top of layer.dropless_packed and experts.fp4_weights.  With both formats switched on FP8 runs (the W4 ladder's own rung).
+
+W4A8 is a third Format over the same MXFP4 images: the rows are quantised per row to e4m3 (ops.quantize_rows_a8 -- the TOKENS whole,
+once, since fc1 gathers them; the packed hidden rows up to offsets[E], the bound read on the device) and the GEMMs are the block-scaled
+fp4 x fp8 ones over the packed tables (csrc/expert_gemm_w4a8.hip, tutel_amd_expert_gemm_w4a8_packed / _glu_packed): eight launches, the
+bits of the padded dropless W4A8 forward.  Opt-in: layer.dropless_packed_w4a8 (TUTEL_AMD_DROPLESS_PACKED_W4A8=1) on top of the FP4
+format's switches and experts.w4a8; asked in front of FP4, which runs where the W4A8 ladder refuses.
 """
 from typing import NamedTuple
 
@@ -40,7 +46,7 @@ class Format(NamedTuple):
     name: str          # "FP8" / "FP4", as the messages spell it
     switch: str        # the layer's switch
     weights: str       # the experts' engine switch
-    frozen: str        # the experts' attribute that is True once they are resident in this format
+    frozen: str        # the experts' attribute that is True once they are resident in this format ("": a refusal never raises)
     refused: str       # what a resident module's refusal raises, in front of the reason
     engine: object     # the `ffn` experts' engine (experts/ffn.py: its ladder, and `ran`, the layer's report)
     glu_refusal: str   # the SwiGLU experts' method that walks their ladder
@@ -53,7 +59,21 @@ FP8 = Format("FP8", "dropless_packed_fp8", "fp8_weights", "fp8_frozen", fp8_resi
              ops.expert_gemm_w8_packed, ops.expert_gemm_w8_glu_packed)
 FP4 = Format("FP4", "dropless_packed_fp4", "fp4_weights", "fp4_frozen", fp8_resident.REFUSED_FP4, _ffn.W4, "w4_refusal", "w4_params",
              ops.expert_gemm_w4_packed, ops.expert_gemm_w4_glu_packed)
-FORMATS = (FP8, FP4)   # the order the layer asks them in: with both switched on FP8 runs
+
+
+def _quantised(packed_gemm):
+    """a W4A8 packed GEMM in a Format's shape: quantise the rows of `a`, then the GEMM over the codes and scales"""
+    def gemm(a, codes, scales, *args, gather=None, **kw):
+        lay = args[-1]
+        q = ops.quantize_rows_a8(a, rows_dev=None if gather else lay.offsets[lay.E:])
+        return None if q is None else packed_gemm(q[0], q[1], codes, scales, *args[:-1], a.dtype, lay, gather=gather, **kw)
+    return gemm
+
+
+# (frozen "": FP4 is asked behind it and raises for an FP4-resident module that no packed forward can run)
+W4A8 = Format("W4A8", "dropless_packed_w4a8", "w4a8", "", fp8_resident.REFUSED_FP4, _ffn.W4A8, "w4a8_refusal", "w4_params",
+              _quantised(ops.expert_gemm_w4a8_packed), _quantised(ops.expert_gemm_w4a8_glu_packed))
+FORMATS = (FP8, W4A8, FP4)   # the order the layer asks them in: with both weight formats switched on FP8 runs; W4A8 in front of FP4
 
 
 def refusal(fmt, layer, x):

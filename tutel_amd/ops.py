@@ -546,12 +546,14 @@ def quantize_rows_a8_supported(dtype, K):
     return dtype in _DT and bool(_lib.lib().tutel_amd_quantize_rows_a8_supported(_DT[dtype], int(K)))
 
 
-def quantize_rows_a8(x, out=None, scale=None):
+def quantize_rows_a8(x, out=None, scale=None, rows_dev=None):
     """x [rows, K] bf16 / fp16 (rows may be strided) -> (codes [rows, K] uint8, scale [rows] fp32): per row, bit for bit
     experts/w8.py::quantize_e4m3(x.unsqueeze(0), True) -- scale = amax / 448, e4m3 codes of x / scale (the contract of
     include/tutel_amd.h).  A row with a non-finite value gets scale NaN and code 0x7F throughout; no host read, capturable.
-    out / scale: written in place when given (contiguous).  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
-    _dev(x, out, scale)
+    out / scale: written in place when given (contiguous).  rows_dev (device int32 [1]): the live row count -- rows at and past it are
+    neither read nor written (tutel_amd_quantize_rows_a8_bounded: the packed layout's rows past offsets[E] hold no data).  Returns None
+    when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(x, out, scale, rows_dev)
     assert x.dim() == 2 and x.stride(1) == 1
     x = _a16(x)
     rows, K = x.shape
@@ -561,9 +563,12 @@ def quantize_rows_a8(x, out=None, scale=None):
         scale = torch.empty([rows], dtype=torch.float32, device=x.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (rows, K)
     assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == rows
-    rc = _lib.lib().tutel_amd_quantize_rows_a8(_ptr(x), _DT.get(x.dtype, -1), x.stride(0) if rows > 1 else max(x.stride(0), K), rows, K,
-                                               _ptr(out), K, _ptr(scale), _stream())
-    return _unless_notsup(rc, "tutel_amd_quantize_rows_a8", (out, scale))
+    args = (_ptr(x), _DT.get(x.dtype, -1), x.stride(0) if rows > 1 else max(x.stride(0), K), rows, K, _ptr(out), K, _ptr(scale))
+    if rows_dev is None:
+        return _unless_notsup(_lib.lib().tutel_amd_quantize_rows_a8(*args, _stream()), "tutel_amd_quantize_rows_a8", (out, scale))
+    assert rows_dev.dtype == torch.int32 and rows_dev.numel() >= 1
+    return _unless_notsup(_lib.lib().tutel_amd_quantize_rows_a8_bounded(*args, _ptr(rows_dev), _stream()),
+                          "tutel_amd_quantize_rows_a8_bounded", (out, scale))
 
 
 def _a8_padded(entry, aq, a_scale, E_loc, weights, bias, N, K, dtype, act, slot_map, R, out, row_counts, glu=False):
@@ -955,6 +960,54 @@ def expert_gemm_w4_glu_packed(a, codes, scales, H, K, layout, act="silu", gather
     _dev(a, codes, scales, out, zero_row)
     E, weights = _w4_image(codes, scales)
     return _ws_packed("tutel_amd_expert_gemm_w4_glu_packed", a, E, weights, None, H, K, layout, act, gather, zero_row, out, glu=True)
+
+
+def _a8_packed(entry, aq, a_scale, E, weights, bias, N, K, dtype, layout, act, gather, zero_row, out, glu=False):
+    """The packed W4A8 wrappers behind their weight checks, in _ws_packed's shape: aq is uint8 (e4m3 codes) with a_scale fp32 per row of
+    aq (per token when gather), zero_row at least K zero BYTES of any dtype, and the output's dtype is an argument of its own"""
+    if aq.dtype == torch.float8_e4m3fn:
+        aq = aq.view(torch.uint8)
+    assert E == layout.E and aq.dim() == 2 and aq.is_contiguous() and aq.shape[1] == K and aq.dtype == torch.uint8
+    assert a_scale.dtype == torch.float32 and a_scale.is_contiguous() and a_scale.numel() == aq.shape[0]
+    aq = _a16(aq)
+    if gather:
+        assert zero_row is not None and zero_row.numel() * zero_row.element_size() >= K
+    else:
+        assert aq.shape[0] >= layout.rows_bound
+    if out is None:
+        out = torch.empty([layout.rows_bound, N], dtype=dtype, device=aq.device)
+    assert out.shape == (layout.rows_bound, N) and out.is_contiguous() and out.dtype == dtype
+    if bias is not None:
+        assert bias.dim() == 2 and bias.shape == (E, N) and bias.stride(1) == 1 and bias.dtype == dtype
+    bias_args = () if glu else (_ptr(bias), (bias.stride(0) if bias is not None else 0))
+    rc = getattr(_lib.lib(), entry)(
+        _ptr(aq), _ptr(a_scale), K, (_ptr(layout.slot_map) if gather else None), (aq.shape[0] if gather else 0),
+        (_ptr(zero_row) if gather else None), *weights, *bias_args, _ptr(out), N, E, layout.rows_bound, N, K,
+        _DT.get(dtype, -1), ACT_CODES[act], _ptr(layout.offsets), _ptr(layout.tiles), _ptr(layout.ntiles), layout.tiles_bound, _stream())
+    return _unless_notsup(rc, entry, out)
+
+
+def expert_gemm_w4a8_packed(aq, a_scale, codes, scales, bias, N, K, dtype, layout, act="none", gather=None, zero_row=None, out=None):
+    """expert_gemm_w4a8 over the packed dropless layout: D[r] = act(acc * a_scale[row] + bias[e]) for the packed rows r of expert e
+    -> [rows_bound, N] in `dtype`, bit for bit what expert_gemm_w4a8 writes for the same quantised row, scale and expert (the contract
+    of include/tutel_amd.h).  aq [rows_bound, K] uint8 with a_scale [rows_bound] -- quantize_rows_a8's outputs, its rows past
+    layout.offsets[E] never read -- or with gather=True the quantised token array [T, K] with a_scale [T] read through layout.slot_map
+    (zero_row, >= K zero bytes, for pad rows, whose scale is 1); codes / scales / bias as expert_gemm_w4's.  Rows past layout.offsets[E]
+    are left unwritten.  TUTEL_AMD_W4A8_PACKED_TILE=wide | halves (read at every call) picks the window form, the same bits.  Returns None
+    when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, codes, scales, bias, out, zero_row)
+    E, weights = _w4_image(codes, scales)
+    return _a8_packed("tutel_amd_expert_gemm_w4a8_packed", aq, a_scale, E, weights, bias, N, K, dtype, layout, act, gather, zero_row, out)
+
+
+def expert_gemm_w4a8_glu_packed(aq, a_scale, codes, scales, H, K, dtype, layout, act="silu", gather=None, zero_row=None, out=None):
+    """expert_gemm_w4a8_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w4a8_glu writes for the same
+    quantised row, scale and expert.  aq, a_scale, gather, zero_row as expert_gemm_w4a8_packed's; codes / scales: the interleaved gate /
+    up images.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, codes, scales, out, zero_row)
+    E, weights = _w4_image(codes, scales)
+    return _a8_packed("tutel_amd_expert_gemm_w4a8_glu_packed", aq, a_scale, E, weights, None, H, K, dtype, layout, act, gather, zero_row, out,
+                      glu=True)
 
 
 def _grad_out_dtype(out_dtype, operand_dtype):
