@@ -338,9 +338,9 @@ int tutel_amd_expert_gemm_w8_glu(const void *A, int64_t a_stride_e, int64_t a_st
  * N % 32 == 0; lda and a_stride_e % 16 == 0, ldd, d_stride_e and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= N * K; any
  * R >= 1 (tuned for R <= 128; more rows stream the weights once per 128), E_loc * R and the tile count below 2^31.  Ragged last tiles
  * clamp their loads and mask their stores: nothing is read or written outside the operands.  NOT covered: row_counts (megablocks), the
- * [W, E_loc, C, *] exchange layouts, peer stores, the packed dropless layout.  Anything not covered returns TUTEL_AMD_ENOTSUP with
- * nothing enqueued; E_loc == 0 or R == 0 is a successful no-op.  Aq, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte
- * aligned.  Every check precedes the first HIP call. */
+ * [W, E_loc, C, *] exchange layouts, peer stores.  Anything not covered returns TUTEL_AMD_ENOTSUP with nothing enqueued; E_loc == 0 or
+ * R == 0 is a successful no-op.  Aq, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte aligned.  Every check precedes the first
+ * HIP call.  The packed dropless layout has entry points of its own: tutel_amd_expert_gemm_w8a8_packed below. */
 int tutel_amd_expert_gemm_w8a8_supported(int dtype, int N, int K);
 int tutel_amd_expert_gemm_w8a8(const void *Aq, const float *a_scale, int64_t a_stride_e, int64_t a_stride_w, int a_rows_per_w, int lda,
                                const void *Wq, int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e, void *D,
@@ -557,6 +557,32 @@ int tutel_amd_expert_gemm_w4a8_glu_packed(const void *Aq, const float *a_scale, 
                                           int64_t s_stride_e, void *D, int ldd, int E, int rows_bound, int H, int K, int dtype, int act,
                                           const int32_t *offsets, const int32_t *tiles, const int32_t *ntiles, int tiles_bound,
                                           tutel_stream_t stream);
+
+/* The two W8A8 GEMMs above over the PACKED dropless layout (csrc/expert_gemm_w8a8.hip).  Arguments: those of
+ * tutel_amd_expert_gemm_w4a8_packed / _w4a8_glu_packed with the W8 weight operands (Wq, w_stride_e, scale: tutel_amd_expert_gemm_w8a8's)
+ * in place of the W4 ones; Aq, a_scale, lda (BYTES), a_rows, T and zero_row mean what they mean there.
+ *     Every row in [0, offsets[E]) is written, BIT FOR BIT what tutel_amd_expert_gemm_w8a8 / _w8a8_glu write for the same quantised row,
+ *     scale and expert, whichever window form computed it (one tile function: one fp32 accumulator per output, K ascending in steps of
+ *     16, the same operands, the same epilogue).  Rows at and past offsets[E] are neither read nor written.
+ * Window forms, TUTEL_AMD_W8A8_PACKED_TILE=wide | halves, read at every call (anything else: the default, HALVES -- DESIGN 4.4 holds
+ * the measurement and the resource table that decided it).  HALVES: the padded kernels' 128-row tile over the two halves of a 256-row
+ * table tile, in the W8A16 packed kernels' order; 2 x 8 KB of LDS.  WIDE: a work item is (table tile, 128 image channels) and covers all
+ * live rows of the window [tiles[2t+1], +256) clipped by offsets[e + 1]: each K-tile of the weights is fetched and split into its four
+ * operands once and feeds up to 32 matrix instructions; 2 x 16 KB of LDS.  Rows of a window past the expert's end clamp their loads to
+ * the last live row and mask their stores; wholly dead 32-row groups of a wide window issue no matrix instruction.
+ * Covered: the padded W8A8 entry points' conditions without the bucket strides -- bf16 / fp16 outputs, K % 64 == 0, N % 32 == 0
+ * (H % 16 == 0), lda % 16 == 0, ldd and bias_stride_e % 4 == 0, w_stride_e % 16 == 0 and >= one image, act one of TUTEL_ACT_*, the halves
+ * form's work item count below 2^31.  Anything else returns TUTEL_AMD_ENOTSUP with its reason and nothing enqueued; E == 0,
+ * rows_bound == 0 or tiles_bound == 0 is a successful no-op.  Aq, Wq, scale and zero_row 16-byte aligned, D and bias 8-byte aligned,
+ * a_scale 4-byte aligned.  Every check precedes the first HIP call. */
+int tutel_amd_expert_gemm_w8a8_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T, const void *zero_row,
+                                      const void *Wq, int64_t w_stride_e, const float *scale, const void *bias, int64_t bias_stride_e,
+                                      void *D, int ldd, int E, int rows_bound, int N, int K, int dtype, int act, const int32_t *offsets,
+                                      const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
+int tutel_amd_expert_gemm_w8a8_glu_packed(const void *Aq, const float *a_scale, int lda, const int32_t *a_rows, int T,
+                                          const void *zero_row, const void *Wq_gu, int64_t w_stride_e, const float *scale_gu, void *D,
+                                          int ldd, int E, int rows_bound, int H, int K, int dtype, int act, const int32_t *offsets,
+                                          const int32_t *tiles, const int32_t *ntiles, int tiles_bound, tutel_stream_t stream);
 
 /* The two W8A16 GEMMs above over the PACKED dropless layout (tutel_amd_packed_layout below; csrc/expert_gemm_w8.hip): the experts'
  * rows lie back to back and every row range is read from the device tables, so the launch depends on no routing-dependent host value

@@ -147,6 +147,8 @@ SIGNATURES.update({
     "tutel_amd_expert_gemm_w4_glu_packed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
     "tutel_amd_expert_gemm_w4a8_packed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
     "tutel_amd_expert_gemm_w4a8_glu_packed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
+    "tutel_amd_expert_gemm_w8a8_packed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
+    "tutel_amd_expert_gemm_w8a8_glu_packed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp] + [_i] * 7 + [_vp] * 3 + [_i, _vp]),
     "tutel_amd_expert_wgrad_packed": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "tutel_amd_expert_bgrad_packed": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "tutel_amd_expert_wgrad_packed_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),

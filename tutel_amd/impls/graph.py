@@ -20,7 +20,8 @@ take it: `ffn`, and SwiGLU (`llama_ffn`, with the fused gate/up GEMM).  Experts 
 `layer.dropless_packed_fp8` is on (impls/packed_w8.py; the warm-up forwards cache the quantised images), else on their 16-bit weights;
 experts with `fp4_weights` are captured reading MXFP4 when `layer.dropless_packed_fp4` is on (the same forward over the W4A16 packed
 GEMMs), and FP4-resident experts (fp4_freeze) can be captured only that way; with `layer.dropless_packed_w4a8` and `experts.w4a8` on
-top of it the rows are quantised to e4m3 inside the graph and the W4A8 packed GEMMs run.
+top of it the rows are quantised to e4m3 inside the graph and the W4A8 packed GEMMs run.  In the same way `layer.dropless_packed_w8a8`
+and `experts.fp8_activations` on top of `layer.dropless_packed_fp8` capture the W8A8 packed GEMMs (fp8 rows x fp8 weights).
 
 GraphedForward is forward-only.  A dropless TRAINING step of `ffn` experts (ReLU; bf16 / fp16 parameters, or fp32 masters under autocast) on the packed layout
 (`layer.dropless_packed = True`, impls/packed_train.py) needs no host synchronisation in its forward or backward either, so

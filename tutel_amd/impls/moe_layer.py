@@ -114,6 +114,10 @@ class MOELayer(torch.nn.Module):
         # opt-in, on top of dropless_packed_fp4 and experts.w4a8: the rows quantised to e4m3 and the W4A8 GEMMs over the packed tables
         # (eight launches, capturable).  Where the W4A8 ladder refuses, the reason is in _w4a8_ran and the packed FP4 forward runs
         self.dropless_packed_w4a8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_W4A8", "0")) != 0
+        # opt-in, on top of dropless_packed_fp8, fp8_weights (or an FP8-resident module) and experts.fp8_activations: the rows quantised
+        # to e4m3 and the W8A8 GEMMs over the packed tables (eight launches, capturable).  Where the W8A8 ladder refuses, the reason is
+        # in _fp8_activations_ran and the packed FP8 forward runs
+        self.dropless_packed_w8a8 = int(os.environ.get("TUTEL_AMD_DROPLESS_PACKED_W8A8", "0")) != 0
         # gradient accumulation over micro-batches: the packed training step adds the expert gradients into p.main_grad (fp32) inside
         # the gradient kernels and returns no autograd gradient for them (impls/packed_train.py).  A forward that cannot do so raises
         self.dropless_packed_main_grad = int(os.environ.get("TUTEL_AMD_PACKED_MAIN_GRAD", "0")) != 0
@@ -377,6 +381,8 @@ class MOELayer(torch.nn.Module):
             return None
         if fmt is packed_w8.W4A8 and not self.dropless_packed_fp4:   # (it sits on top of the FP4 format's switch)
             return None
+        if fmt is packed_w8.W8A8 and not self.dropless_packed_fp8:   # (and this one on top of the FP8 format's)
+            return None
         T, E = logits.shape[0], logits.shape[-1]
         k = min(top_k, E)
         frozen = bool(fmt.frozen) and getattr(self.experts, fmt.frozen, False)   # no 16-bit packed forward to fall back to: a refusal raises
@@ -409,7 +415,7 @@ class MOELayer(torch.nn.Module):
                                      min(top_k, logits.shape[1]), cf, alignment, plan)
         self._dropless_packed_ran = True
         setattr(self, fmt.engine.ran, True)
-        if fmt is packed_w8.FP8 and getattr(self.experts, "fp8_activations", False):
+        if fmt is packed_w8.FP8 and getattr(self.experts, "fp8_activations", False) and not self.dropless_packed_w8a8:
             self._fp8_activations_ran = "the packed dropless forward has no W8A8 GEMM"   # it keeps W8A16
         if fmt is packed_w8.FP4 and getattr(self.experts, "w4a8", False) and not self.dropless_packed_w4a8:
             self._w4a8_ran = "the packed dropless forward has no W4A8 GEMM"   # it keeps W4A16

@@ -27,6 +27,12 @@ once, since fc1 gathers them; the packed hidden rows up to offsets[E], the bound
 fp4 x fp8 ones over the packed tables (csrc/expert_gemm_w4a8.hip, tutel_amd_expert_gemm_w4a8_packed / _glu_packed): eight launches, the
 bits of the padded dropless W4A8 forward.  Opt-in: layer.dropless_packed_w4a8 (TUTEL_AMD_DROPLESS_PACKED_W4A8=1) on top of the FP4
 format's switches and experts.w4a8; asked in front of FP4, which runs where the W4A8 ladder refuses.
+
+W8A8 is the fourth: the FP8 Format's images and channel scales under rows quantised the same way, on the unscaled fp8 x fp8 matrix
+instruction over the packed tables (csrc/expert_gemm_w8a8.hip, tutel_amd_expert_gemm_w8a8_packed / _glu_packed): eight launches, the
+bits of the padded dropless W8A8 forward.  Opt-in: layer.dropless_packed_w8a8 (TUTEL_AMD_DROPLESS_PACKED_W8A8=1) on top of the FP8
+format's switches and experts.fp8_activations; asked in front of FP8, which runs where the W8A8 ladder refuses (the reason stays in
+layer._fp8_activations_ran).
 """
 from typing import NamedTuple
 
@@ -62,7 +68,7 @@ FP4 = Format("FP4", "dropless_packed_fp4", "fp4_weights", "fp4_frozen", fp8_resi
 
 
 def _quantised(packed_gemm):
-    """a W4A8 packed GEMM in a Format's shape: quantise the rows of `a`, then the GEMM over the codes and scales"""
+    """a W4A8 / W8A8 packed GEMM in a Format's shape: quantise the rows of `a`, then the GEMM over the codes and scales"""
     def gemm(a, codes, scales, *args, gather=None, **kw):
         lay = args[-1]
         q = ops.quantize_rows_a8(a, rows_dev=None if gather else lay.offsets[lay.E:])
@@ -73,7 +79,11 @@ def _quantised(packed_gemm):
 # (frozen "": FP4 is asked behind it and raises for an FP4-resident module that no packed forward can run)
 W4A8 = Format("W4A8", "dropless_packed_w4a8", "w4a8", "", fp8_resident.REFUSED_FP4, _ffn.W4A8, "w4a8_refusal", "w4_params",
               _quantised(ops.expert_gemm_w4a8_packed), _quantised(ops.expert_gemm_w4a8_glu_packed))
-FORMATS = (FP8, W4A8, FP4)   # the order the layer asks them in: with both weight formats switched on FP8 runs; W4A8 in front of FP4
+# (frozen "": FP8 is asked behind it and raises for an FP8-resident module that no packed forward can run)
+W8A8 = Format("W8A8", "dropless_packed_w8a8", "fp8_activations", "", fp8_resident.REFUSED, _ffn.W8A8, "w8a8_refusal", "w8_params",
+              _quantised(ops.expert_gemm_w8a8_packed), _quantised(ops.expert_gemm_w8a8_glu_packed))
+# the order the layer asks them in: with both weight formats switched on FP8 runs; W8A8 in front of FP8 and W4A8 in front of FP4
+FORMATS = (W8A8, FP8, W4A8, FP4)
 
 
 def refusal(fmt, layer, x):

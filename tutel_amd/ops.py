@@ -963,7 +963,7 @@ def expert_gemm_w4_glu_packed(a, codes, scales, H, K, layout, act="silu", gather
 
 
 def _a8_packed(entry, aq, a_scale, E, weights, bias, N, K, dtype, layout, act, gather, zero_row, out, glu=False):
-    """The packed W4A8 wrappers behind their weight checks, in _ws_packed's shape: aq is uint8 (e4m3 codes) with a_scale fp32 per row of
+    """The packed W4A8 and W8A8 wrappers behind their weight checks, in _ws_packed's shape: aq is uint8 (e4m3 codes) with a_scale fp32 per row of
     aq (per token when gather), zero_row at least K zero BYTES of any dtype, and the output's dtype is an argument of its own"""
     if aq.dtype == torch.float8_e4m3fn:
         aq = aq.view(torch.uint8)
@@ -1007,6 +1007,27 @@ def expert_gemm_w4a8_glu_packed(aq, a_scale, codes, scales, H, K, dtype, layout,
     _dev(aq, a_scale, codes, scales, out, zero_row)
     E, weights = _w4_image(codes, scales)
     return _a8_packed("tutel_amd_expert_gemm_w4a8_glu_packed", aq, a_scale, E, weights, None, H, K, dtype, layout, act, gather, zero_row, out,
+                      glu=True)
+
+
+def expert_gemm_w8a8_packed(aq, a_scale, image, scale, bias, N, K, dtype, layout, act="none", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8a8 over the packed dropless layout: D[r] = act((acc * a_scale[row]) * scale[e] + bias[e]) for the packed rows r of
+    expert e -> [rows_bound, N] in `dtype`, bit for bit what expert_gemm_w8a8 writes for the same quantised row, scale and expert (the
+    contract of include/tutel_amd.h).  aq, a_scale, gather, zero_row as expert_gemm_w4a8_packed's; image / scale / bias as
+    expert_gemm_w8's.  Rows past layout.offsets[E] are left unwritten.  TUTEL_AMD_W8A8_PACKED_TILE=wide | halves (read at every call)
+    picks the window form, the same bits.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, image, scale, bias, out, zero_row)
+    E, weights = _w8_image(image, scale, N)
+    return _a8_packed("tutel_amd_expert_gemm_w8a8_packed", aq, a_scale, E, weights, bias, N, K, dtype, layout, act, gather, zero_row, out)
+
+
+def expert_gemm_w8a8_glu_packed(aq, a_scale, image, scale, H, K, dtype, layout, act="silu", gather=None, zero_row=None, out=None):
+    """expert_gemm_w8a8_glu over the packed dropless layout -> [rows_bound, H], bit for bit what expert_gemm_w8a8_glu writes for the same
+    quantised row, scale and expert.  aq, a_scale, gather, zero_row as expert_gemm_w8a8_packed's; image / scale: the interleaved gate /
+    up image and its [E, 2 H] scales.  Returns None when the library answers ENOTSUP (nothing was enqueued)."""
+    _dev(aq, a_scale, image, scale, out, zero_row)
+    E, weights = _w8_image(image, scale, 2 * H)
+    return _a8_packed("tutel_amd_expert_gemm_w8a8_glu_packed", aq, a_scale, E, weights, None, H, K, dtype, layout, act, gather, zero_row, out,
                       glu=True)
 
 
